@@ -28,6 +28,12 @@ terms -- device PCG fit plus all hyper-parameter gradients -- with its phases.
 `python bench.py --gpus N` launches its own N ranks (one process per GPU,
 torch.distributed.run) when it is not already running under a launcher; `--sim-ranks N` times
 on ONE GPU the step a rank of an N-GPU job runs.  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the outputs of
+the last timed step with --dump-outputs DIR, and the line (metric, value, unit, ms_per_step,
+per-step times, the configuration).  Everything else above -- the per-kernel profile and
+rooflines, the fit / predict split, the parity checks, the PCG back end, the other
+configurations, the obfit evaluations and the CPU baseline -- runs with --full.
 """
 import argparse
 import ctypes as C
@@ -46,6 +52,7 @@ sys.path.insert(0, ROOT)
 FP64_MFMA_PEAK_TFLOPS = 78.6   # MI355X datasheet FP64 matrix (dense); see DESIGN.md
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md "HBM3E peak BW"
 LDS_PEAK_GBS = 256 * 256 * 2.4  # 256 B/clk/CU (ds_read_b64) x 256 CUs x 2.4 GHz = 157 TB/s
+DUMP_MAX_ROWS = 4_000_000      # --dump-outputs: 32 MB of float64 predictions; larger shards are sampled
 
 
 def parse():
@@ -66,6 +73,16 @@ def parse():
                     help="0 automatic, 3 fused MFMA 4x4x4 (no staging memory), 4 staged design matrix MFMA 4x4x4")
     ap.add_argument("--dump", default=None,
                     help="rank 0 writes theta and its first 1000 de-standardised predictions here (.npz)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed as DIR/<name>.npy (float64): "
+                         "theta, the de-standardised predictions `mean` of its rows (a fixed, seeded sample "
+                         "of %d rows, their indices in mean_rows.npy, above that) and meansd"
+                         % DUMP_MAX_ROWS)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-kernel profile and rooflines, fit / predict "
+                         "split, parity checks against the oracle, the PCG back end, the other BASELINE.json "
+                         "configurations, obfit evaluations and the CPU baseline (the --no-* switches "
+                         "below trim this set)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-alt-backend", action="store_true")
     ap.add_argument("--no-obfit-eval", action="store_true",
@@ -628,6 +645,70 @@ def obfit_evaluation(kinds, knots, p, n, torch, _lib, reps=3, maxlev=None, what=
     return out
 
 
+def dump_outputs(path, hp, torch, np):
+    """What the last timed step handed its caller, as DIR/<name>.npy: theta (p), the
+    de-standardised predictions of this rank's rows (`mean`; above DUMP_MAX_ROWS rows a fixed,
+    seeded sample, the sampled row indices in mean_rows.npy) and meansd = (mean of y, sd of y,
+    rows).  The inputs are seeded, so equal arguments give equal inputs from run to run."""
+    os.makedirs(path, exist_ok=True)
+    out = {"theta": hp.theta, "meansd": hp.meansd}
+    if hp.n > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(0).choice(hp.n, DUMP_MAX_ROWS, replace=False))
+        out["mean"] = hp.mean[torch.from_numpy(rows).to(hp.mean.device)]
+        out["mean_rows"] = rows.astype(np.float64)
+    else:
+        out["mean"] = hp.mean
+    for name, a in out.items():
+        if torch.is_tensor(a):
+            a = a.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def headline_line(args, hp, kinds, world, n_total, n_local, elapsed, per_step, vworld, transport):
+    """The result line's headline: points/s of the timed steps and the configuration."""
+    p = args.p
+    pts = float(n_total) * args.steps
+    out = {
+        "metric": "fit+predict points/sec, d=%d n=%g p=%d" % (args.d, n_total, p),
+        "value": pts / elapsed,
+        "unit": "points/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "median_step_ms": statistics.median(per_step),
+        "value_at_median_step": float(n_total) / (statistics.median(per_step) * 1e-3),
+        "step_ms": per_step,
+        "higher_is_better": True,
+        "scaling": "weak" if args.weak else "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {
+            "workload": "%s: d=%d n=%d (%d rows on each of %d GPU(s)) p=%d, %s, %d knots/dim, "
+                        "fit (%s) + predict on n fresh rows"
+                        % (which_config(args.d, n_total, n_local, p), args.d, n_total, n_local,
+                           world, p, "/".join(sorted(set(kinds))), args.knots,
+                           "Gram+Cholesky" if args.backend == "newton" else "PCG"),
+            "backend": args.backend,
+            "rows_total": n_total, "rows_per_gpu": n_local, "d": args.d, "p": p,
+            "terms_nnz": hp.terms_info["nnz_total"], "basis_columns": hp.ncols,
+            "parallelism": ("one rank: nothing to exchange (y standardised first, one B^T y pass)"
+                            if world == 1 else
+                            "rows sharded over %d rank(s); per fit 24 bytes for mean / sd of y and one "
+                            "exchange buffer (packed triangle of G, B^T y)" % world),
+        },
+    }
+    if transport:
+        out["sim_ranks"] = vworld
+        out["config"]["parallelism"] = (
+            "REHEARSAL on one GPU: %d virtual ranks that all hold this GPU's %d rows "
+            "(obhip_comm_init_sim: every sum is one device pass buf *= ranks); the step is what one "
+            "rank of a %d-GPU job runs without the wire, `value` counts this GPU's rows only"
+            % (vworld, n_local, vworld))
+    return out
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -695,6 +776,24 @@ def main():
         sys.stderr.flush()
 
     elapsed, per_step = timed_steps(hp, args.steps, args.warmup, sync, torch, dist, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, hp, torch, np)
+
+    if not args.full:
+        # a plain run: the headline and nothing else
+        if rank == 0:
+            if args.dump:
+                np.savez(args.dump, theta=hp.theta.cpu().numpy(), mean=hp.mean[:1000].cpu().numpy(),
+                         meansd=hp.meansd.cpu().numpy(), n_total=n_total, world=world)
+            out = headline_line(args, hp, kinds, world, n_total, n_local, elapsed, per_step, vworld, transport)
+            out["exchange"] = dict(hp.comm_info(), selftest_result=selftest)
+            print(json.dumps(out))
+            sys.stdout.flush()
+        hp.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     prof = kernel_profile(hp, _lib, torch)
 
     # fit-only and predict-only wall times, outside the timed region
@@ -858,38 +957,9 @@ def main():
         return
 
     p = args.p
-    pts = float(n_total) * args.steps
     ms_per_step = elapsed / args.steps * 1e3
-    out = {
-        "metric": "fit+predict points/sec, d=%d n=%g p=%d" % (args.d, n_total, p),
-        "value": pts / elapsed,
-        "unit": "points/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "median_step_ms": statistics.median(per_step),
-        "value_at_median_step": float(n_total) / (statistics.median(per_step) * 1e-3),
-        "step_ms": per_step,
-        "higher_is_better": True,
-        "scaling": "weak" if args.weak else "strong",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {
-            "workload": "%s: d=%d n=%d (%d rows on each of %d GPU(s)) p=%d, %s, %d knots/dim, "
-                        "fit (%s) + predict on n fresh rows"
-                        % (which_config(args.d, n_total, n_local, p), args.d, n_total, n_local,
-                           world, p, "/".join(sorted(set(kinds))), args.knots,
-                           "Gram+Cholesky" if args.backend == "newton" else "PCG"),
-            "backend": args.backend,
-            "rows_total": n_total, "rows_per_gpu": n_local, "d": args.d, "p": p,
-            "terms_nnz": hp.terms_info["nnz_total"], "basis_columns": hp.ncols,
-            "parallelism": ("one rank: nothing to exchange (y standardised first, one B^T y pass)"
-                            if world == 1 else
-                            "rows sharded over %d rank(s); per fit 24 bytes for mean / sd of y and one "
-                            "exchange buffer (packed triangle of G, B^T y)" % world),
-        },
+    out = headline_line(args, hp, kinds, world, n_total, n_local, elapsed, per_step, vworld, transport)
+    out.update({
         "exchange": dict(comm_info, allreduce_ms=prof.get("exchange", {}).get("avg_ms"),
                          selftest_result=selftest),
         "fit_predict_split": split,
@@ -904,16 +974,9 @@ def main():
         "configs": others,
         "obfit_eval": obfit_eval,
         "obfit_eval_mat25pow_d8": obfit_eval_pow,
-    }
+    })
     if config0 is not None:
         out["configs"] = [config0] + out["configs"]
-    if transport:
-        out["sim_ranks"] = vworld
-        out["config"]["parallelism"] = (
-            "REHEARSAL on one GPU: %d virtual ranks that all hold this GPU's %d rows "
-            "(obhip_comm_init_sim: every sum is one device pass buf *= ranks); the step is what one "
-            "rank of a %d-GPU job runs without the wire, `value` counts this GPU's rows only"
-            % (vworld, n_local, vworld))
     if "gram" in prof and args.backend == "newton":
         flops = float(n_local) * p * (p + 1)  # p(p+1) flop per point
         ach = flops / (prof["gram"]["avg_ms"] * 1e-3) / 1e12

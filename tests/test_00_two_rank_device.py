@@ -155,7 +155,7 @@ def test_bench_self_launch_two_ranks(tmp_path):
     predictions must be those of the 1-rank run on the same 200 000 rows."""
     import json
     bench = os.path.join(ROOT, "bench.py")
-    base = [sys.executable, bench, "--rows", "200000", "--steps", "2", "--warmup", "1",
+    base = [sys.executable, bench, "--rows", "200000", "--steps", "2", "--warmup", "1", "--full",
             "--no-cpu-baseline", "--no-config3", "--no-configs", "--fit-parity-rows", "6000"]
     env = dict(os.environ, OBHIP_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("RANK", None)

@@ -333,15 +333,16 @@ def test_glue_declares_only_abi_symbols():
                             "covf_mat25pow", "covf_mat25ang"}
 
 
-def test_glue_covers_the_reference_module_surface():
-    """Every function, class, method and field of the reference's RCPP_MODULE(obmod)
-    (src/interfaceR.cpp:661-793) has a counterpart of the same name in the glue.  Needs the
-    reference checkout (study only: the file is read as text); skipped where it is absent."""
-    ref = "/root/reference/src/interfaceR.cpp"
-    if not os.path.exists(ref):
-        pytest.skip("reference checkout not present")
+def test_glue_keeps_its_module_surface():
+    """Every function, class, method and field of the glue's RCPP_MODULE(obmod) -- the names of
+    the reference's module (src/interfaceR.cpp:661-793) -- recorded in
+    tests/golden/module_surface.json is still there under the same name."""
+    import json
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    rf, rc = _module_surface(open(ref).read())
+    rec = json.load(open(os.path.join(root, "tests", "golden", "module_surface.json")))
+    rf = set(rec["functions"])
+    rc = {cls: set(names) for cls, names in rec["classes"].items()}
+    assert rf and len(rc) == 13
     gf, gc = _module_surface(open(os.path.join(root, "glue", "obhip_glue.cpp")).read())
     assert rf == gf
     assert set(rc) == set(gc)

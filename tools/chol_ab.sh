@@ -9,6 +9,6 @@ d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d["kernels_ms"]; prin
 timeout -k 10 600 python3 -m pytest tests/test_gpu_parity.py -q -x -m gpu -k "newton or cholesky" 2>&1 | tail -2 || exit 1
 for setting in "${@:-DEFAULT=1}"; do
   echo "== $setting"
-  env $setting timeout -k 10 300 python3 bench.py --rows 125000 --steps 10 --warmup 2 --no-cpu-baseline --no-alt-backend --no-config3 2>/dev/null | python3 -c "$show" || exit 1
-  env $setting timeout -k 10 300 python3 bench.py --rows 60000 --d 40 --p 16384 --kinds mat25,mat25pow,mat25ang --steps 3 --warmup 1 --no-cpu-baseline --no-alt-backend --no-config3 2>/dev/null | python3 -c "$show" || exit 1
+  env $setting timeout -k 10 300 python3 bench.py --full --rows 125000 --steps 10 --warmup 2 --no-cpu-baseline --no-alt-backend --no-config3 2>/dev/null | python3 -c "$show" || exit 1
+  env $setting timeout -k 10 300 python3 bench.py --full --rows 60000 --d 40 --p 16384 --kinds mat25,mat25pow,mat25ang --steps 3 --warmup 1 --no-cpu-baseline --no-alt-backend --no-config3 2>/dev/null | python3 -c "$show" || exit 1
 done

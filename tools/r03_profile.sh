@@ -35,10 +35,10 @@ if [ "$1" = "--check" ]; then
   exit $?
 fi
 TAG=${1:-a}
-timeout -k 10 900 python3 bench.py > $OUT/bench_line_$TAG.json 2> $OUT/bench_$TAG.err || { tail -5 $OUT/bench_$TAG.err; exit 1; }
+timeout -k 10 900 python3 bench.py --full > $OUT/bench_line_$TAG.json 2> $OUT/bench_$TAG.err || { tail -5 $OUT/bench_$TAG.err; exit 1; }
 echo "bench ok"
 ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$TAG -o p -- \
-  python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-alt-backend --no-config3 \
+  python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-alt-backend --no-config3 \
   > $OUT/bench_line_profiled_$TAG.json 2> $OUT/stats_$TAG.err ) || { tail -5 $OUT/stats_$TAG.err; exit 1; }
 rm -f $OUT/stats_$TAG/*kernel_trace.csv
 echo "stats ok"
@@ -48,12 +48,12 @@ for set in "MfmaUtil VALUBusy" "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_s
 done
 rm -f $OUT/bench_lines_shard_sizes_$TAG.jsonl
 for rows in 125000 250000 500000; do
-  timeout -k 10 300 python3 bench.py --rows $rows --steps 10 --warmup 2 --no-cpu-baseline --no-alt-backend --no-config3 \
+  timeout -k 10 300 python3 bench.py --full --rows $rows --steps 10 --warmup 2 --no-cpu-baseline --no-alt-backend --no-config3 \
     >> $OUT/bench_lines_shard_sizes_$TAG.jsonl 2>> $OUT/bench_$TAG.err || exit 1
 done
 echo "shard sizes ok"
 ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats125_$TAG -o p -- \
-  python3 $R/bench.py --rows 125000 --steps 5 --warmup 1 --no-cpu-baseline --no-alt-backend --no-config3 \
+  python3 $R/bench.py --full --rows 125000 --steps 5 --warmup 1 --no-cpu-baseline --no-alt-backend --no-config3 \
   > /dev/null 2> $OUT/stats125_$TAG.err ) || { tail -5 $OUT/stats125_$TAG.err; exit 1; }
 rm -f $OUT/stats125_$TAG/*kernel_trace.csv
 echo "all ok"

@@ -6,7 +6,7 @@ out=gpurun_out/r04/hm_ab.txt
 : > $out
 run() {
   echo "== $1" >> $out
-  env $1 python bench.py --backend cg --steps 3 --warmup 1 --no-cpu-baseline --no-configs --no-config3 \
+  env $1 python bench.py --full --backend cg --steps 3 --warmup 1 --no-cpu-baseline --no-configs --no-config3 \
       --no-fit-parity > gpurun_out/r04/hm_ab_line.json 2>> gpurun_out/r04/hm_ab.err || return 1
   python - >> $out <<'PY'
 import json

@@ -36,7 +36,7 @@ if [ "$1" = "--check" ]; then
 fi
 TAG=${1:-a}
 ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$TAG -o p -- \
-  python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-alt-backend --no-config3 --no-configs --no-fit-parity --no-obfit-eval \
+  python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-alt-backend --no-config3 --no-configs --no-fit-parity --no-obfit-eval \
   > $OUT/bench_line_profiled_$TAG.json 2> $OUT/stats_$TAG.err ) || { tail -5 $OUT/stats_$TAG.err; exit 1; }
 rm -f $OUT/stats_$TAG/*kernel_trace.csv
 echo "stats ok"
@@ -47,11 +47,11 @@ done
 # the full bench line AFTER the PMC passes, with profiles/r04_gram_traffic.json of this very
 # library in place on the box, so that its roofline.traffic / mfma_util / l2_hit_rate are filled
 python3 tools/r04_summarise.py $TAG > $OUT/summarise_on_box_$TAG.log 2>&1 || { tail -5 $OUT/summarise_on_box_$TAG.log; exit 1; }
-timeout -k 10 900 python3 bench.py > $OUT/bench_line_$TAG.json 2> $OUT/bench_$TAG.err || { tail -5 $OUT/bench_$TAG.err; exit 1; }
+timeout -k 10 900 python3 bench.py --full > $OUT/bench_line_$TAG.json 2> $OUT/bench_$TAG.err || { tail -5 $OUT/bench_$TAG.err; exit 1; }
 echo "bench ok"
 # the per-rank step of an N-GPU job on this one GPU: N virtual ranks (obhip_comm_init_sim: the real
 # exchange-buffer layout, pack, unpack, replicated solve; the sum itself is one device pass)
-LEAN="--no-cpu-baseline --no-alt-backend --no-config3 --no-configs --no-fit-parity --no-obfit-eval"
+LEAN="--full --no-cpu-baseline --no-alt-backend --no-config3 --no-configs --no-fit-parity --no-obfit-eval"
 rm -f $OUT/bench_lines_shard_sizes_$TAG.jsonl
 for spec in "125000 8" "250000 4" "500000 2"; do
   set -- $spec

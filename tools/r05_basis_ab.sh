@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
 mkdir -p gpurun_out/r05
-LEAN="--no-cpu-baseline --no-alt-backend --no-config3 --no-configs --no-fit-parity --no-obfit-eval"
+LEAN="--full --no-cpu-baseline --no-alt-backend --no-config3 --no-configs --no-fit-parity --no-obfit-eval"
 for w in 4 8 16 4 8 16; do
 OBHIP_BB_WAVES=$w python bench.py --steps 5 --warmup 1 $LEAN > gpurun_out/r05/basis_line.json 2>> gpurun_out/r05/basis.err || exit 1
 python - $w <<'PY'

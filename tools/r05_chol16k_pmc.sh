@@ -6,7 +6,7 @@ cd $R
 OUT=$R/gpurun_out/r05_chol16k
 mkdir -p $OUT
 ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --pmc MfmaUtil VALUBusy --output-format csv \
-    -d $OUT/pmc -o p -- python3 $R/bench.py --rows 60000 --d 40 --p 16384 --kinds mat25,mat25pow,mat25ang --steps 1 --warmup 0 \
+    -d $OUT/pmc -o p -- python3 $R/bench.py --full --rows 60000 --d 40 --p 16384 --kinds mat25,mat25pow,mat25ang --steps 1 --warmup 0 \
     --no-cpu-baseline --no-alt-backend --no-config3 --no-configs --no-fit-parity --no-obfit-eval > $OUT/pmc.log 2>&1 ) || { tail -5 $OUT/pmc.log; exit 1; }
 f=$(find $OUT/pmc -name "*counter_collection.csv" | head -1)
 python3 - $f <<'PY' | tee $OUT/pmc_mfma_util.txt
@@ -17,7 +17,7 @@ for r in rows:
     if "k_chol" in r["Kernel_Name"]:
         m = re.search(r"k_\w+(<[^>]*>)?", r["Kernel_Name"])
         agg[m.group(0)][r["Counter_Name"]].append(float(r["Counter_Value"]))
-print("rocprofv3 --kernel-trace --pmc MfmaUtil VALUBusy -- python3 bench.py --rows 60000 --d 40 --p 16384 --kinds mat25,mat25pow,mat25ang --steps 1 --warmup 0 (...): per kernel, mean over its dispatches (and over the 10 % with the highest value: the large trailing passes)")
+print("rocprofv3 --kernel-trace --pmc MfmaUtil VALUBusy -- python3 bench.py --full --rows 60000 --d 40 --p 16384 --kinds mat25,mat25pow,mat25ang --steps 1 --warmup 0 (...): per kernel, mean over its dispatches (and over the 10 % with the highest value: the large trailing passes)")
 for k, v in agg.items():
     for name, vals in sorted(v.items()):
         vals.sort()

@@ -12,5 +12,5 @@ for k in ("obfit_eval", "obfit_eval_mat25pow_d8"):
     if e: print("  %s %.2f ms: " % (k, e["ms_per_evaluation"]) + ", ".join("%s %.2f" % (n, v["ms_per_evaluation"]) for n, v in e["phases"].items()))'
 for f in 0 1 2; do
   echo "== OBHIP_GE0_FOURS=$f"
-  OBHIP_GE0_FOURS=$f timeout -k 10 300 python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-alt-backend --no-config3 --no-configs --no-fit-parity 2>/dev/null | python3 -c "$show" || exit 1
+  OBHIP_GE0_FOURS=$f timeout -k 10 300 python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-alt-backend --no-config3 --no-configs --no-fit-parity 2>/dev/null | python3 -c "$show" || exit 1
 done

@@ -6,7 +6,7 @@
 mkdir -p gpurun_out/r05
 out=gpurun_out/r05/overlap_ab.txt
 : > $out
-LEAN="--no-cpu-baseline --no-alt-backend --no-config3 --no-configs --no-fit-parity --no-obfit-eval"
+LEAN="--full --no-cpu-baseline --no-alt-backend --no-config3 --no-configs --no-fit-parity --no-obfit-eval"
 run() {
   echo "== $1" >> $out
   env $1 python bench.py --steps 5 --warmup 1 $LEAN > gpurun_out/r05/overlap_line.json 2>> gpurun_out/r05/overlap.err || return 1
