@@ -459,6 +459,74 @@ int obhip_normal_eq_exchange_dev(obhip_comm *comm, uint64_t p, uint64_t n_local,
                                  double *d_g, const double *d_b1, const double *d_sum2,
                                  double *d_buf, uint64_t buf_count, double *d_meansd);
 
+/* ---- several responses over one design (no reference counterpart) ---------------------
+ * The reference fits one y (obfit, R/fitting.R:40-120); what it has for several columns are the
+ * matrix forms of prodmm_ / tprodmm_ (src/linalg.cpp:481-637).  Here q responses Y (n x q,
+ * column-major, leading dimension ldy >= n) over one x share the model, the terms, sigma and
+ * rho, hence G = B^T B, H and its Cholesky factor, which are formed ONCE; B^T Y, the
+ * triangular solves and the predictor are batched over the responses in blocks of 16 columns
+ * (64 per pass, so the scratch does not grow with q).  Theta is p x q, mean n_new x q, both
+ * column-major without padding; any q >= 1.  Response 0 takes the single-response code path
+ * throughout (with q = 1 every entry below gives the bits of its single-response twin).
+ * obfit's standardisation (R/fitting.R:55-57) of every column on its own, like
+ * obhip_standardise_dev: two passes, n - 1 denominator, summed over the ranks of comm in TWO
+ * exchanges for the whole batch (2 q and q doubles).  d_Y_raw, d_Y: n x q with leading
+ * dimension ldy (may be the same buffer); d_meansd: q triples (mean, sd, rows of all ranks).  A
+ * constant column gets what obhip_standardise_dev gives it (sd = 0, NaN entries); the other
+ * columns are not affected. */
+int obhip_standardise_multi_dev(obhip_comm *comm, const double *d_Y_raw, uint64_t n, uint64_t q,
+                                uint64_t ldy, double *d_Y, double *d_meansd);
+/* obpred's de-standardisation (R/fitting.R:152) per column, in place: v = mean_j + sd_j v, or
+ * with squared != 0 v = sd_j^2 v (variances).  d_V: n x q, leading dimension ldv. */
+int obhip_destandardise_multi_dev(double *d_V, uint64_t n, uint64_t q, uint64_t ldv,
+                                  const double *d_meansd, int squared);
+/* doubles of exchange buffer obhip_fit_newton_multi_dev needs: [packed upper triangle of G :
+ * p (p + 1) / 2][B^T Y : p q, column-major][zero padding to a multiple of 2 nranks]; with
+ * q = 1 this is obhip_fit_newton_count */
+int obhip_fit_newton_multi_count(uint64_t p, uint64_t q, int nranks, uint64_t *count);
+/* bytes of device workspace of the two entries below: obhip_newton_workspace_bytes(p) plus the
+ * right-hand sides of one pass of the batched substitutions (the same for every q) */
+int obhip_newton_multi_workspace_bytes(uint64_t p, uint64_t q, uint64_t *bytes);
+/* obhip_newton_solve_dev (lpdf::optnewton, fit.cpp:98-131) for q right-hand sides d_G_rhs
+ * (p x q: B^T Y): H is formed from the caller's raw G and factorised once, d_Theta (p x q) =
+ * solve(H, e^{-2 sigma} B^T Y) by blocked forward and backward substitution on the factor (no
+ * inverse of L is formed).  d_G is overwritten by the factor; d_diagH (p) may be NULL. */
+int obhip_newton_multi_solve_dev(const obhip_model *m, const obhip_terms *t, double *d_G,
+                                 const double *d_G_rhs, uint64_t q, double sigma, double rho,
+                                 double *d_Theta, double *d_diagH, void *d_workspace,
+                                 uint64_t workspace_bytes);
+/* obhip_fit_newton_sharded_dev with q right-hand sides, same contract and error codes
+ * (OBHIP_ERR_NUMERIC for a Hessian that is not positive definite): d_Y this rank's rows,
+ * already standardised; d_G_rhs (p x q) receives B^T Y over all ranks; on return the lower
+ * triangle of d_H holds the Cholesky factor; d_exbuf: obhip_fit_newton_multi_count doubles
+ * whose padding the caller zeroed once; d_workspace: obhip_newton_multi_workspace_bytes.
+ * comm = NULL: one rank, d_exbuf is not used.  B^T Y is one pass over the staged design matrix
+ * for up to 64 responses; where that matrix is not resident as a whole (row chunks, Gram
+ * backend 3), or fewer than eight responses are left beside response 0 (a batched pass costs
+ * the same for 1 to 16 columns), it is one pass over the basis per response. */
+int obhip_fit_newton_multi_dev(obhip_comm *comm, const obhip_basis *b, const obhip_terms *t,
+                               const obhip_model *m, const double *d_Y, uint64_t q, uint64_t ldy,
+                               double sigma, double rho, double *d_H, double *d_G_rhs,
+                               double *d_Theta, double *d_diagH, double *d_exbuf,
+                               uint64_t exbuf_count, void *d_workspace, uint64_t workspace_bytes);
+/* obhip_predict_dev for q coefficient vectors: column j of d_mean (n x q) = B(x) Theta[:, j],
+ * the term products formed once per row and term for all responses.  d_var (n, may be NULL,
+ * needs d_coeffvar) = B^2 coeffvar + e^{2 sigma} as obhip_predict_dev gives it: in standardised
+ * units it is the same for every response.  Terms on more basis columns than the fused kernel's
+ * LDS tile holds (and OBHIP_FORCE_GENERIC), and fewer than eight responses beside response 0,
+ * take obhip_predict_dev's path column by column. */
+int obhip_predict_multi_dev(const obhip_model *m, const obhip_terms *t, const double *d_Theta,
+                            uint64_t q, const double *d_x, uint64_t n, double *d_mean,
+                            const double *d_coeffvar, double sigma, double *d_var);
+/* host-buffer conveniences like obhip_fit_newton / obhip_predict: Y (n x q, ldy; standardised
+ * by the caller), Theta (p x q), diagH (p, may be NULL); x n x d with ldx, mean n x q, var n */
+int obhip_fit_newton_multi(const obhip_basis *b, const obhip_terms *t, const obhip_model *m,
+                           const double *Y, uint64_t q, uint64_t ldy, double sigma, double rho,
+                           double *Theta, double *diagH);
+int obhip_predict_multi(const obhip_model *m, const obhip_terms *t, const double *Theta,
+                        uint64_t q, const double *x, uint64_t n, uint64_t ldx, double *mean,
+                        const double *coeffvar, double sigma, double *var);
+
 /* ---- predictor ---------------------------------------------------------- */
 /* predictor$update(x) + $mean() (+ $var() of pred_gauss):
  * loglik_gauss.cpp:214-227, loglik_std.cpp:239-248.  The basis at xnew is

@@ -12,10 +12,13 @@ from .obmod import (covf, covf_mat25, covf_mat25ang, covf_mat25pow, gethyp, getp
                     listcov, loglik_gauss, loglik_gda, loglik_std, logpr_gauss, lpdf, lpdfvec,
                     outerbase, outermod, predictor, setcovfs, setknot)
 from .fitting import BFGS_lpdf, BFGS_std, obfit, obpred
+from .multi import MultiFit, fit_newton_multi
+from .driver import HotPath, MultiHotPath
 
 __all__ = [
     "ObhipError", "device_count", "covf", "covf_mat25", "covf_mat25ang", "covf_mat25pow", "gethyp",
     "getpara", "hypnames", "listcov", "loglik_gauss", "loglik_gda", "loglik_std", "logpr_gauss",
     "lpdf", "lpdfvec", "outerbase", "outermod", "predictor", "setcovfs", "setknot",
     "BFGS_lpdf", "BFGS_std", "obfit", "obpred",
+    "MultiFit", "fit_newton_multi", "HotPath", "MultiHotPath",
 ]

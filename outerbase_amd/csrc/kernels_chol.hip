@@ -623,6 +623,11 @@ uint64_t newton_workspace_bytes(uint64_t p) {
          sizeof(double);
 }
 
+// where launch_newton_solve keeps the inverses of the 16 x 16 diagonal sub-blocks in its workspace
+const double *newton_workspace_iinv(uint64_t p, const void *d_ws) {
+  return (const double *)d_ws + p + 64 + (uint64_t)chol_panels(p) * NB * chol_pitch(p) + NB * NB;
+}
+
 int launch_form_hessian(uint64_t p, double *d_G, const double *d_prec, double e2, double *d_diagH) {
   ProfScope ps("form_hessian");
   const size_t total = (size_t)p * p;

@@ -511,6 +511,20 @@ int launch_newton_solve(uint64_t p, double *d_H, const double *d_rhs,
                         double *d_theta, void *d_ws, uint64_t ws_bytes);
 int launch_form_hessian(uint64_t p, double *d_G, const double *d_prec,
                         double e2, double *d_diagH);
+const double *newton_workspace_iinv(uint64_t p, const void *d_ws);
+// kernels_multi.hip: the batched passes of the multi-response fit and predictor (fit_multi.cpp)
+uint64_t multi_solve_scratch_bytes(uint64_t p);
+// Fewest columns worth a batched pass of B^T Y or the predictor: one pass costs the same for 1 to 16
+// columns (d=20, n=1e6, p=4096: 5.6 ms and 9.1 ms) where the single-column kernels take 0.77 ms and
+// 1.14 ms per column, so below eight columns the column loop is the faster one.
+constexpr uint64_t kMultiMinCols = 8;
+int launch_aty_multi(obhip_basis &b, const obhip_terms &t, const double *d_Y, uint64_t ldy, uint64_t q,
+                     double *d_out, uint64_t ldo);
+int launch_trsm_multi(uint64_t p, const double *d_L, const double *d_Iinv, const double *d_R, uint64_t ldr,
+                      uint64_t q, double e2, double *d_Theta, void *d_scratch);
+bool predict_multi_supports(const obhip_terms &t);
+int launch_predict_multi(const obhip_model &m, obhip_terms &t, const double *d_Theta, uint64_t q,
+                         const double *d_x, uint64_t n, double *d_mean);
 // kernels_predict.hip
 int launch_predict(const obhip_model &m, obhip_terms &t, const double *d_theta,
                    const double *d_x, uint64_t n, double *d_mean,

@@ -316,3 +316,87 @@ def getsteps(numb, sampsize, sigtonoiseratio=1e-3, tol=0.001):
     kapp = 1000.0 if r == 1.0 else min(1000.0, (1 + r) ** 2 / (1 - r) ** 2)
     iterest = 0.5 * math.sqrt(kapp) * math.log(2 * sampsize * sigtonoiseratio / tol)
     return int(math.ceil(2 * iterest))
+
+
+class MultiHotPath(HotPath):
+    """HotPath for `responses` = q outputs over the same rows: one Gram, one Cholesky
+    factorisation, B^T Y, the triangular solves and the prediction batched over the responses
+    (obhip_fit_newton_multi_dev, obhip_predict_multi_dev).  Same constructor plus responses=q,
+    same setup / fit / predict / step / close; Newton back end only.
+
+    The synthetic responses are built on the device from the rows obhip_synth_xy_dev makes (the
+    same x): with y its response and x_l the inputs,
+        Y[:, j] = cos(0.37 j) y + sin(0.37 j) y x_(j mod d),
+    so column 0 is y itself and the others are deterministic, column-dependent, smooth transforms
+    of the same rows.  Y, Theta, mean are stored (q, n) / (q, p) row-major, i.e. column-major
+    n x q / p x q as the library wants them; y, theta, g, mean, meansd of the base class are views
+    of response 0, so its checks (newton_residual_rel, y_cent, ...) speak of that response."""
+
+    def __init__(self, *args, responses=1, **kw):
+        super().__init__(*args, **kw)
+        if responses < 1:
+            raise ValueError("responses must be at least 1")
+        if self.backend != "newton":
+            raise ValueError("MultiHotPath has the Newton back end only")
+        self.q = int(responses)
+        self.Y_raw = None
+
+    def setup(self):
+        super().setup()
+        torch, q, p, n = self.torch, self.q, self.p, self.n
+        dev, f64 = self.x.device, torch.float64
+        self.Y = torch.empty((q, n), dtype=f64, device=dev)
+        self.Mean = torch.empty((q, n), dtype=f64, device=dev)
+        self.Grhs = torch.empty((q, p), dtype=f64, device=dev)
+        self.Theta = torch.zeros((q, p), dtype=f64, device=dev)
+        self.Meansd = torch.zeros((q, 3), dtype=f64, device=dev)
+        self.y, self.mean, self.g = self.Y[0], self.Mean[0], self.Grhs[0]
+        self.theta, self.meansd = self.Theta[0], self.Meansd[0]
+        wsb, cnt = C.c_uint64(0), C.c_uint64(0)
+        call("obhip_newton_multi_workspace_bytes", p, q, C.byref(wsb))
+        self.ws = torch.empty(wsb.value, dtype=torch.uint8, device=dev)
+        self.wsb = wsb.value
+        call("obhip_fit_newton_multi_count", p, q, self.world, C.byref(cnt))
+        self.ex_count = cnt.value
+        # [packed triangle of G | B^T Y, p x q | zero padding]
+        self.exbuf = torch.zeros(self.ex_count, dtype=f64, device=dev) if self.world > 1 else None
+
+    def setup_inputs(self):
+        torch = self.torch
+        if self.Y_raw is None:
+            self.Y_raw = torch.empty((self.q, self.n), dtype=torch.float64, device=self.x.device)
+        self.y_raw = self.Y_raw[0]
+        super().setup_inputs()
+        y = self.Y_raw[0]
+        for j in range(1, self.q):
+            self.Y_raw[j] = math.cos(0.37 * j) * y + math.sin(0.37 * j) * y * self.x[j % self.d]
+        torch.cuda.synchronize()
+
+    def standardise(self):
+        """every column (y_j - mean_j) / sd_j over ALL ranks, two exchanges for the batch"""
+        call("obhip_standardise_multi_dev", self.comm, self.Y_raw.data_ptr(), self.n, self.q, self.n,
+             self.Y.data_ptr(), self.Meansd.data_ptr())
+        self.sigma = math.log(0.01)  # loglik_std.cpp:51 on standardised responses
+
+    def fit(self):
+        torch = self.torch
+        call("obhip_set_stream", C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if self.basis is None:
+            h = C.c_void_p()
+            call("obhip_basis_create_dev", C.byref(h), self.om._h, self.x.data_ptr(), self.n,
+                 self.caps.ctypes.data)
+            self.basis = h
+        else:
+            call("obhip_basis_rebuild", self.basis)
+        self.standardise()
+        call("obhip_fit_newton_multi_dev", self.comm, self.basis, self.t._h, self.om._h,
+             self.Y.data_ptr(), self.q, self.n, self.sigma, self.rho, self.G.data_ptr(),
+             self.Grhs.data_ptr(), self.Theta.data_ptr(), self.diagH.data_ptr(),
+             None if self.exbuf is None else self.exbuf.data_ptr(), self.ex_count,
+             self.ws.data_ptr(), self.wsb)
+
+    def predict(self):
+        call("obhip_predict_multi_dev", self.om._h, self.t._h, self.Theta.data_ptr(), self.q,
+             self.xnew.data_ptr(), self.n, self.Mean.data_ptr(), None, self.sigma, None)
+        call("obhip_destandardise_multi_dev", self.Mean.data_ptr(), self.n, self.q, self.n,
+             self.Meansd.data_ptr(), 0)

@@ -1,0 +1,129 @@
+"""Newton fit and prediction of several responses over one design.
+
+Computer codes rarely return one number: q outputs (time steps, sensors, grid cells) over the
+same inputs x share the model, the term set, sigma and rho, hence the Gram B^T B, the Hessian
+and its Cholesky factor.  fit_newton_multi forms those once and batches what depends on Y over
+the responses (include/obhip.h, "several responses over one design"); every response is
+standardised on its own as obfit standardises its y (R/fitting.R:55-57).
+
+torch holds the device memory; all arithmetic is in libobhip.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import obmod
+from ._lib import call
+
+DEFAULT_RHO = 6.0  # logpr_gauss.cpp:48
+
+
+def _check_xy(om, x, Y):
+    x = np.asarray(x, dtype=np.float64)
+    Y = np.asarray(Y, dtype=np.float64)
+    if Y.ndim == 1:
+        Y = Y[:, None]
+    if x.ndim != 2 or x.shape[1] != om.d:
+        raise ValueError("x must be n x d")
+    if Y.ndim != 2:
+        raise ValueError("Y must be n x q")
+    if Y.shape[0] != x.shape[0]:
+        raise ValueError("Y has %d rows, x has %d" % (Y.shape[0], x.shape[0]))
+    if Y.shape[1] == 0:
+        raise ValueError("Y has no columns")
+    if x.shape[0] < 2:
+        raise ValueError("the standard deviation of a response needs two rows")
+    if not np.all(np.isfinite(Y)):
+        raise ValueError("Y must be finite")
+    return x, Y
+
+
+class MultiFit:
+    """Result of fit_newton_multi: coeff (p x q), y_cent / y_sca (q each), diagH (p)."""
+
+    def __init__(self, om, t, coeff, meansd, diagH, sigma, rho):
+        self.om, self._t = om, t
+        self.coeff = coeff
+        self.y_cent = meansd[:, 0].copy()
+        self.y_sca = meansd[:, 1].copy()
+        self._meansd = meansd
+        self.diagH = diagH
+        self.sigma, self.rho = sigma, rho
+        self.q = coeff.shape[1]
+
+    def predict(self, xnew, var=False):
+        """De-standardised mean (n x q) at xnew; with var=True also the predictive variance
+        (n x q) of the diagonal form B^2 coeffvar + e^{2 sigma} (obhip_predict_dev) with
+        coeffvar = 1 / diagH, scaled by the square of every response's standard deviation."""
+        import torch
+        xnew = np.asarray(xnew, dtype=np.float64)
+        if xnew.ndim != 2 or xnew.shape[1] != self.om.d:
+            raise ValueError("xnew must be n x d")
+        n, q, f64 = xnew.shape[0], self.q, torch.float64
+        if n == 0:
+            z = np.zeros((0, q))
+            return (z, z.copy()) if var else z
+        dev = torch.device("cuda", torch.cuda.current_device())
+        call("obhip_set_stream", C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        dx = torch.from_numpy(np.ascontiguousarray(xnew.T)).to(dev)          # column-major n x d
+        dth = torch.from_numpy(np.ascontiguousarray(self.coeff.T)).to(dev)   # column-major p x q
+        dms = torch.from_numpy(np.ascontiguousarray(self._meansd)).to(dev)
+        mean = torch.empty((q, n), dtype=f64, device=dev)
+        dcv = dvar = None
+        if var:
+            dcv = torch.from_numpy(1.0 / self.diagH).to(dev)
+            dvar = torch.empty(n, dtype=f64, device=dev)
+        call("obhip_predict_multi_dev", self.om._h, self._t._h, dth.data_ptr(), q, dx.data_ptr(), n,
+             mean.data_ptr(), None if dcv is None else dcv.data_ptr(), self.sigma,
+             None if dvar is None else dvar.data_ptr())
+        call("obhip_destandardise_multi_dev", mean.data_ptr(), n, q, n, dms.data_ptr(), 0)
+        if not var:
+            return mean.cpu().numpy().T
+        vq = dvar.repeat(q, 1).contiguous()
+        call("obhip_destandardise_multi_dev", vq.data_ptr(), n, q, n, dms.data_ptr(), 1)
+        return mean.cpu().numpy().T, vq.cpu().numpy().T
+
+
+def fit_newton_multi(om, terms, x, Y, sigma=None, rho=DEFAULT_RHO, comm=None):
+    """One Newton step from coeff = 0 of lpdfvec(loglik_std, logpr_gauss) (lpdf::optnewton,
+    fit.cpp:98-131) for every column of Y (n x q) over the rows x (n x d): one Gram, one
+    Cholesky factorisation, batched passes for what depends on Y.  sigma=None: log(0.01), what
+    loglik_std starts from for a standardised response (loglik_std.cpp:51).  comm: an obhip_comm
+    handle of a row-sharded job (x, Y are then this rank's rows), None = one rank."""
+    x, Y = _check_xy(om, x, Y)
+    import torch
+    if sigma is None:
+        sigma = math.log(0.01)
+    t = obmod._terms_of(om, terms)
+    n, q, p, f64 = x.shape[0], Y.shape[1], t.p, torch.float64
+    dev = torch.device("cuda", torch.cuda.current_device())
+    call("obhip_set_stream", C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    dx = torch.from_numpy(np.ascontiguousarray(x.T)).to(dev)
+    dY = torch.from_numpy(np.ascontiguousarray(Y.T)).to(dev)
+    meansd = torch.empty((q, 3), dtype=f64, device=dev)
+    call("obhip_standardise_multi_dev", comm, dY.data_ptr(), n, q, n, dY.data_ptr(), meansd.data_ptr())
+    caps = t.maxlevels()
+    basis = C.c_void_p()
+    call("obhip_basis_create_dev", C.byref(basis), om._h, dx.data_ptr(), n, caps.ctypes.data)
+    try:
+        wsb, cnt, nr = C.c_uint64(0), C.c_uint64(0), C.c_int(1)
+        call("obhip_newton_multi_workspace_bytes", p, q, C.byref(wsb))
+        exbuf = None
+        if comm is not None:
+            call("obhip_comm_info", comm, C.byref(nr), None, None, None, None)
+            call("obhip_fit_newton_multi_count", p, q, nr.value, C.byref(cnt))
+            exbuf = torch.zeros(cnt.value, dtype=f64, device=dev)
+        ws = torch.empty(wsb.value, dtype=torch.uint8, device=dev)
+        H = torch.empty((p, p), dtype=f64, device=dev)
+        rhs = torch.empty((q, p), dtype=f64, device=dev)
+        theta = torch.empty((q, p), dtype=f64, device=dev)
+        diagH = torch.empty(p, dtype=f64, device=dev)
+        call("obhip_fit_newton_multi_dev", comm, basis, t._h, om._h, dY.data_ptr(), q, n, sigma, rho,
+             H.data_ptr(), rhs.data_ptr(), theta.data_ptr(), diagH.data_ptr(),
+             None if exbuf is None else exbuf.data_ptr(), cnt.value, ws.data_ptr(), wsb.value)
+        torch.cuda.synchronize()
+    finally:
+        call("obhip_basis_destroy", basis)
+    return MultiFit(om, t, theta.cpu().numpy().T.copy(), meansd.cpu().numpy(), diagH.cpu().numpy(),
+                    sigma, rho)
