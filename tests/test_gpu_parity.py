@@ -596,6 +596,8 @@ def test_gradhyp_with_more_hyperparameters_than_one_pass_holds(kinds, nhyp):
     bo = O.OuterBase(om_o, x, dograd=True)
     bd = ob.outerbase(om_d, x)
     a, v = rng.standard_normal(p), rng.standard_normal(n)
+    # (test_gpu_extended.py::test_gradhyp_against_extended_reference holds the same five models per
+    # entry, each against its own conditioning bound in long double)
     tol = 1e-9 if terms.max() < 8 else 2e-7
     assert relerr(bd.matmul_gradhyp(terms, a), O.ob_mm_gradhyp(bo, terms, a)[1]) < tol
     assert relerr(bd.tmatmul_gradhyp(terms, v), O.ob_tmm_gradhyp(bo, terms, v)[1]) < tol
@@ -1172,6 +1174,8 @@ def test_term_per_lane_variants(max_nnz, p, maxlev):
         # (levels 12-14 of 16 knots lie beyond `maxlevel`, where lambda_j / lambda_0 < 1e-11 and
         # the eigenpairs are rounding noise amplified by rotmat ~ 1 / lambda: kernel variants
         # are what this case is for, not parity)
+        # (test_gpu_extended.py::test_products_against_extended_reference, "random d10 W6": a random
+        # set of this model per entry against its own conditioning bound in long double)
         tol = 1e-5 if maxlev >= 12 else (1e-6 if maxlev >= 5 else 1e-9)
         Bd = bd.getmat(terms)
         got, gotsq = bd.tmatmul(terms, v), bd.sqtmm(terms, v)
@@ -1584,6 +1588,8 @@ def test_gram_diagonal_tiles_packed_four_into_three_blocks(n, p, monkeypatch):
     B = O.ob_getmat(O.OuterBase(om_o, x), terms)
     # (4096 terms of eight dimensions reach levels whose knot sums lose digits on both sides, as in
     # test_gram_backends: the two schedules pin each other to 1e-13 above, the oracle loosely)
+    # (test_gpu_extended.py::test_gram_against_extended_reference holds the same four shapes, the
+    # [1500-4096] one included, per entry on a column sample that reaches every 64 x 64 quadrant)
     assert relerr(got["1"], B.T @ B) < (1e-9 if p <= 2048 else 1e-6)
 
 

@@ -106,6 +106,8 @@ def test_star_kernels_on_selected_terms(kinds, p, want_w):
     rng = np.random.default_rng(p)
     # (high levels lose digits in the knot sums on both sides: the oracle pins loosely there, the
     # device's own design matrix tightly)
+    # (test_gpu_extended.py::test_products_against_extended_reference holds the same four term sets
+    # per entry, each against its own conditioning bound in long double: the "star ..." cases)
     tol = 1e-5 if terms.max() >= 12 else (1e-6 if terms.max() >= 5 else 1e-9)
     for n in (1, 300, 5000):
         check_products(om_o, om_d, kinds, terms, n, rng, tol)
