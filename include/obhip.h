@@ -65,6 +65,9 @@ typedef struct obhip_predictor obhip_predictor; /* class predictor, fit.h:352-36
 typedef struct obhip_comm obhip_comm;   /* the ranks of a row-sharded job (no reference
                                            counterpart: the reference is one process,
                                            modandbase.cpp:464) */
+typedef struct obhip_normal_acc obhip_normal_acc; /* the normal equations of the rows seen so far
+                                                     (no reference counterpart: obfit takes all
+                                                     rows at once, R/fitting.R:40-120) */
 
 /* ---- library ----------------------------------------------------------- */
 /* 5.  (2 -> 3: obhip_standardise_dev, obhip_destandardise_dev, obhip_fit_newton_count,
@@ -526,6 +529,78 @@ int obhip_fit_newton_multi(const obhip_basis *b, const obhip_terms *t, const obh
 int obhip_predict_multi(const obhip_model *m, const obhip_terms *t, const double *Theta,
                         uint64_t q, const double *x, uint64_t n, uint64_t ldx, double *mean,
                         const double *coeffvar, double sigma, double *var);
+
+/* ---- streaming Newton fit: rows come and go, one pass over each (no reference counterpart) ----
+ * obfit (R/fitting.R:40-120) and every fit entry above take all rows at once and form the whole
+ * Gram again per call.  An obhip_normal_acc keeps, in HBM, the sufficient statistics of the Newton
+ * step for the rows it has been given -- the algebra of "the one exchange of back end A" with the
+ * shards spread over time instead of over ranks, standardising AFTER the sum:
+ * B^T ((y - cent) / sd) = (B^T y - cent B^T 1) / sd.  State, obhip_normal_acc_bytes(p, q) / 8 doubles:
+ *   [upper triangle of G = B^T B, row-major packed as in obhip_normal_eq_count : p (p + 1) / 2]
+ *   [R = B^T (Y - c) : p x q, column-major][B^T 1 : p][per response c, mu, M2, n : 4 q]
+ * c_j is a fixed shift of response j (its first row ever added), mu_j = mean(y_j) - c_j and
+ * M2_j = sum (y_j - mean(y_j))^2 over the rows in the state; batches and accumulators merge by the
+ * pairwise update of Chan, Golub and LeVeque and leave by its inverse, all in differences from c, so
+ * a mean far from zero costs no digits.  Removal SUBTRACTS sums: its rounding error is that of the
+ * rows that were ever in the state, not of those that remain.
+ * An accumulator is bound to one model and one term set (the caller keeps both alive) and to the
+ * model's hyper-parameters and knots as they are when its first rows come in: any later change
+ * makes add / combine / solve fail with OBHIP_ERR_STATE until obhip_normal_acc_reset.  Argument
+ * errors are OBHIP_ERR_INVALID, and every check runs before the first launch: a refused call leaves
+ * the accumulator unchanged.  Handles are used by one thread at a time; the _dev entries enqueue on
+ * the library's stream and do not synchronise, with one exception: obhip_normal_acc_solve_dev waits
+ * for its factorisation like the other solve entries (that is how OBHIP_ERR_NUMERIC is reported),
+ * and uploads the prior precisions when the model or rho differ from its last call.  q >= 1
+ * responses (at most 65534). */
+int obhip_normal_acc_create(obhip_normal_acc **out, const obhip_model *m, const obhip_terms *t,
+                            uint64_t q);
+int obhip_normal_acc_destroy(obhip_normal_acc *acc);
+/* back to no rows (and free to follow the model's current hyper-parameters) */
+int obhip_normal_acc_reset(obhip_normal_acc *acc);
+/* terms, responses, rows in the state, batches added and not removed; any pointer may be NULL */
+int obhip_normal_acc_info(const obhip_normal_acc *acc, uint64_t *p, uint64_t *q, uint64_t *rows,
+                          uint64_t *batches);
+/* bytes of device memory of one accumulator: 8 (p (p + 1) / 2 + p q + p + 4 q); host arithmetic */
+int obhip_normal_acc_bytes(uint64_t p, uint64_t q, uint64_t *bytes);
+/* the state as laid out above into d_out (device, count >= obhip_normal_acc_bytes / 8 doubles) */
+int obhip_normal_acc_export_dev(const obhip_normal_acc *acc, double *d_out, uint64_t count);
+/* sign = +1: add the rows of `basis` (built on the accumulator's model, after its last change;
+ * another model: OBHIP_ERR_INVALID) with their RAW responses d_Y_raw (n_b x q, column-major, leading
+ * dimension ldy); sign = -1: take out a batch that was added before (more rows than the state
+ * holds: OBHIP_ERR_STATE; a state left without rows is reset).  The batch's Gram is formed by the
+ * Gram kernels of obhip_gram_dev into a packed triangle in scratch, B^T [Y - c | 1] as
+ * obhip_fit_newton_multi_dev forms B^T Y, and one pass folds both into the state: the cost is that
+ * of a fit of n_b rows without its Cholesky.  Scratch: one more state's worth of pooled device
+ * memory plus n_b (q + 1) doubles, for the duration of the call.  A basis of no rows cannot exist;
+ * callers skip empty batches. */
+int obhip_normal_acc_add_dev(obhip_normal_acc *acc, const obhip_basis *basis, const double *d_Y_raw,
+                             uint64_t ldy, int sign);
+/* dst = dst + sign src (sign = +1 / -1) for two accumulators of the same model, terms and q:
+ * triangle, right-hand sides (src's moved to dst's shift) and moments; src is not written */
+int obhip_normal_acc_combine_dev(obhip_normal_acc *dst, const obhip_normal_acc *src, int sign);
+/* The Newton step of obhip_newton_multi_solve_dev (lpdf::optnewton, fit.cpp:98-131, from
+ * coeff = 0) on the rows in acc -- with minus != NULL on the rows of acc without those of minus,
+ * which must be among them -- every response standardised over exactly those rows as obfit does
+ * (R/fitting.R:55-57, n - 1 denominator).  Neither accumulator is written.  d_H (p x p) receives
+ * H = e^{-2 sigma} (T - T_minus) + diag(1 / (sd e^rho)^2) and then, in its lower triangle, the
+ * Cholesky factor; d_Theta p x q; d_diagH (p) may be NULL; d_meansd: q triples (mean, sd, rows) as
+ * from obhip_standardise_multi_dev; d_workspace: obhip_newton_multi_workspace_bytes(p, q).  Fewer
+ * than two rows left: OBHIP_ERR_STATE; a Hessian that is not positive definite (possible after a
+ * removal that cancels most of G): OBHIP_ERR_NUMERIC, as the other solve entries report it.  A
+ * response that is constant over the rows that remain -- or whose M2 a removal has cancelled to
+ * zero -- gets sd = 0 and non-finite coefficients without an error, as obhip_standardise_multi_dev
+ * treats a constant column; d_meansd shows it. */
+int obhip_normal_acc_solve_dev(const obhip_normal_acc *acc, const obhip_normal_acc *minus,
+                               double sigma, double rho, double *d_H, double *d_Theta,
+                               double *d_diagH, double *d_meansd, void *d_workspace,
+                               uint64_t workspace_bytes);
+/* Held-out score of a cross-validation fold: d_out[2 j] = sum over the n rows of
+ * (mean_j + sd_j d_mean[i, j] - d_Y_raw[i, j])^2, the squared error in raw units of the
+ * standardised predictions d_mean (d_meansd = NULL: d_mean is in raw units already), and
+ * d_out[2 j + 1] = n.  d_mean, d_Y_raw: n x q, column-major, leading dimension ld.  One two-stage
+ * reduction in a fixed order, no atomics: the same bits on every run. */
+int obhip_cv_score_dev(const double *d_mean, const double *d_Y_raw, uint64_t n, uint64_t q,
+                       uint64_t ld, const double *d_meansd, double *d_out);
 
 /* ---- predictor ---------------------------------------------------------- */
 /* predictor$update(x) + $mean() (+ $var() of pred_gauss):

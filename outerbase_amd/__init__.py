@@ -14,6 +14,7 @@ from .obmod import (covf, covf_mat25, covf_mat25ang, covf_mat25pow, gethyp, getp
 from .fitting import BFGS_lpdf, BFGS_std, obfit, obpred
 from .multi import MultiFit, fit_newton_multi
 from .driver import HotPath, MultiHotPath
+from .stream import CVResult, NewtonAccumulator, cv_folds, cv_newton_multi
 
 __all__ = [
     "ObhipError", "device_count", "covf", "covf_mat25", "covf_mat25ang", "covf_mat25pow", "gethyp",
@@ -21,4 +22,5 @@ __all__ = [
     "lpdf", "lpdfvec", "outerbase", "outermod", "predictor", "setcovfs", "setknot",
     "BFGS_lpdf", "BFGS_std", "obfit", "obpred",
     "MultiFit", "fit_newton_multi", "HotPath", "MultiHotPath",
+    "NewtonAccumulator", "cv_newton_multi", "cv_folds", "CVResult",
 ]

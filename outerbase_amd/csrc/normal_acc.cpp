@@ -1,0 +1,269 @@
+// Streaming Newton fit (no reference counterpart: obfit, R/fitting.R:40-120, takes all rows at
+// once).  An obhip_normal_acc keeps the sufficient statistics of lpdfvec(loglik_std, logpr_gauss)'s
+// Newton step for the rows it has been given -- the packed upper triangle of G = B^T B, B^T (Y - c),
+// B^T 1 and per response (c, mean - c, M2, n), one device buffer laid out as kernels_acc.hip says --
+// so that rows are passed over once, ever:
+//   add / remove   the batch's Gram goes through launch_gram_to with a packed sink into scratch,
+//                  B^T [Y - c | 1] as fit_multi.cpp forms B^T Y (column 0 with the staging pass, the
+//                  others by k_aty_multi or a column loop), then one fold with the sign;
+//   combine        the same fold of one accumulator into another;
+//   solve          H = e^{-2 sigma} (T - T_minus) + diag(prec) unpacked from the triangle(s), the
+//                  moments of the remaining rows and the right-hand sides standardised AFTER the sum,
+//                  B^T ((y - cent) / sd) = (B^T y - cent B^T 1) / sd, then launch_newton_solve and the
+//                  batched substitutions of the multi-response fit.  Neither state is written.
+// G depends on the model's hyper-parameters, so a state is tied to the model version of its first
+// batch.  Every check that can refuse a call runs before the first launch: a refused call leaves the
+// accumulator as it was.
+#include <algorithm>
+#include <cmath>
+#include <new>
+#include <string>
+
+#include "obhip_internal.h"
+#include "vec_ops.h"
+
+using namespace obhip;
+
+namespace obhip {
+std::vector<double> prior_prec_of(const obhip_model &m, const obhip_terms &t, double rho);
+int check_compat_of(const obhip_model *m, const obhip_terms *t);
+// kernels_acc.hip
+int launch_acc_batch_moments(const double *d_Y, uint64_t ldy, uint64_t n, uint64_t q, bool empty,
+                             const double *d_mom_state, double *d_mom_batch, double *d_Ys, double *d_part);
+int launch_acc_fold(uint64_t p, uint64_t q, double *d_dst, const double *d_src, bool dst_empty, double sign);
+int launch_acc_form(uint64_t p, const double *d_tri, const double *d_tri_minus, double *d_H, double e2,
+                    const double *d_prec, double *d_diagH);
+int launch_acc_rhs(uint64_t p, uint64_t q, const double *d_state, const double *d_minus, double e2, double *d_rhs,
+                   double *d_meansd);
+int launch_cv_score(const double *d_mean, const double *d_Y, uint64_t n, uint64_t q, uint64_t ld,
+                    const double *d_meansd, double *d_out, double *d_part);
+}  // namespace obhip
+
+struct obhip_normal_acc {
+  const obhip_model *model = nullptr;
+  const obhip_terms *terms = nullptr;
+  uint64_t p = 0, q = 0;
+  uint64_t rows = 0, batches = 0;
+  uint64_t version = 0;  // of the model when the first batch came in (rows > 0)
+  DevBuf<double> st;     // [tri][R p x q][b1 p][moments 4 q]
+};
+
+namespace {
+
+constexpr uint64_t kMaxResponses = 65534;  // grid.y of the column passes holds q + 1
+
+uint64_t state_count(uint64_t p, uint64_t q) { return p * (p + 1) / 2 + p * q + p + 4 * q; }
+
+int zero_state(obhip_normal_acc *a) {
+  OB_HIP(hipMemsetAsync(a->st.p, 0, a->st.n * sizeof(double), cur_stream()));
+  a->rows = a->batches = 0;
+  return 0;
+}
+
+// the same term set: one handle, or two uploads of the same levels
+bool same_terms(const obhip_terms *a, const obhip_terms *b) {
+  return a == b || (a->p == b->p && a->d == b->d && a->lev == b->lev);
+}
+
+// the model must be what it was when the state's first rows came in
+int check_version(const obhip_normal_acc *a, const char *who) {
+  if (a->rows > 0 && a->version != a->model->version)
+    return fail(OBHIP_ERR_STATE, std::string(who) +
+                                     ": the model's hyper-parameters or knots changed since the accumulator's first "
+                                     "batch (G depends on them): reset it and add the rows again");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int obhip_normal_acc_bytes(uint64_t p, uint64_t q, uint64_t *bytes) {
+  if (!bytes || p == 0 || q == 0 || q > kMaxResponses) return fail(OBHIP_ERR_INVALID, "normal_acc_bytes: bad argument");
+  *bytes = state_count(p, q) * sizeof(double);
+  return 0;
+}
+
+int obhip_normal_acc_create(obhip_normal_acc **out, const obhip_model *m, const obhip_terms *t, uint64_t q) {
+  if (!out || !m || !t || q == 0 || q > kMaxResponses) return fail(OBHIP_ERR_INVALID, "normal_acc_create: bad argument");
+  OB_TRY(check_compat_of(m, t));
+  OB_TRY(require_device());
+  obhip_normal_acc *a = new (std::nothrow) obhip_normal_acc();
+  if (!a) return fail(OBHIP_ERR_INVALID, "normal_acc_create: out of host memory");
+  a->model = m;
+  a->terms = t;
+  a->p = t->p;
+  a->q = q;
+  int rc = a->st.alloc(state_count(a->p, q));
+  if (!rc) rc = zero_state(a);
+  if (rc) {
+    delete a;
+    return rc;
+  }
+  *out = a;
+  return 0;
+}
+
+int obhip_normal_acc_destroy(obhip_normal_acc *acc) {
+  delete acc;
+  return 0;
+}
+
+int obhip_normal_acc_reset(obhip_normal_acc *acc) {
+  if (!acc) return fail(OBHIP_ERR_INVALID, "normal_acc_reset: null argument");
+  return zero_state(acc);
+}
+
+int obhip_normal_acc_info(const obhip_normal_acc *acc, uint64_t *p, uint64_t *q, uint64_t *rows, uint64_t *batches) {
+  if (!acc) return fail(OBHIP_ERR_INVALID, "normal_acc_info: null argument");
+  if (p) *p = acc->p;
+  if (q) *q = acc->q;
+  if (rows) *rows = acc->rows;
+  if (batches) *batches = acc->batches;
+  return 0;
+}
+
+int obhip_normal_acc_export_dev(const obhip_normal_acc *acc, double *d_out, uint64_t count) {
+  if (!acc || !d_out) return fail(OBHIP_ERR_INVALID, "normal_acc_export_dev: null argument");
+  if (count < acc->st.n) return fail(OBHIP_ERR_INVALID, "normal_acc_export_dev: buffer too small");
+  OB_HIP(hipMemcpyAsync(d_out, acc->st.p, acc->st.n * sizeof(double), hipMemcpyDeviceToDevice, cur_stream()));
+  return 0;
+}
+
+int obhip_normal_acc_add_dev(obhip_normal_acc *acc, const obhip_basis *bc, const double *d_Y_raw, uint64_t ldy,
+                             int sign) {
+  if (!acc || !bc || (sign != 1 && sign != -1)) return fail(OBHIP_ERR_INVALID, "normal_acc_add_dev: bad argument");
+  if (bc->model != acc->model)
+    return fail(OBHIP_ERR_INVALID, "normal_acc_add_dev: the basis was built on another model than the accumulator");
+  const uint64_t n = bc->n, p = acc->p, q = acc->q;
+  if (n == 0) return 0;
+  if (!d_Y_raw || ldy < n) return fail(OBHIP_ERR_INVALID, "normal_acc_add_dev: Y is null or ldy below the rows of the basis");
+  OB_TRY(check_compat_of(acc->model, acc->terms));
+  OB_TRY(check_version(acc, "normal_acc_add_dev"));
+  if (bc->md.model_version != acc->model->version)
+    return fail(OBHIP_ERR_STATE, "normal_acc_add_dev: the basis was built before the model last changed");
+  if (sign < 0 && n > acc->rows)
+    return fail(OBHIP_ERR_STATE, "normal_acc_add_dev: removing " + std::to_string(n) + " rows from an accumulator that holds " +
+                                     std::to_string(acc->rows));
+  OB_TRY(require_device());
+  obhip_terms &t = *const_cast<obhip_terms *>(acc->terms);
+  obhip_basis &b = *const_cast<obhip_basis *>(bc);
+  const uint64_t tri = p * (p + 1) / 2, nrb = p * (q + 1);
+  DevBuf<double> scratch, Ys, part;
+  OB_TRY(scratch.alloc(state_count(p, q)));
+  OB_TRY(Ys.alloc(n * (q + 1)));
+  OB_TRY(part.alloc(512 * q));
+  const bool empty = acc->rows == 0;
+  double *s_rb = scratch.p + tri, *s_mom = scratch.p + tri + nrb;
+  OB_TRY(launch_acc_batch_moments(d_Y_raw, ldy, n, q, empty, acc->st.p + tri + nrb, s_mom, Ys.p, part.p));
+  GramSink sink;
+  sink.out = scratch.p;
+  sink.packed = true;
+  GramFuse fuse;
+  fuse.y = Ys.p;
+  fuse.g = s_rb;
+  OB_TRY(launch_gram_to(b, t, sink, &fuse));
+  // column 0 as the single fit takes it: with the staging pass, or by its own pass over the basis
+  if (!fuse.done) OB_TRY(launch_tmm(b, t, Ys.p, s_rb, false));
+  // columns 1 .. q - 1 of Y - c, then the ones column: B^T 1
+  if (q >= kMultiMinCols && b.bmat.p && t.uid != 0 && b.bmat_terms == t.uid) {
+    OB_TRY(launch_aty_multi(b, t, Ys.p + n, n, q, s_rb + p, p));
+  } else {
+    for (uint64_t j = 1; j <= q; ++j) OB_TRY(launch_tmm(b, t, Ys.p + j * n, s_rb + j * p, false));
+  }
+  OB_TRY(launch_acc_fold(p, q, acc->st.p, scratch.p, empty, (double)sign));
+  if (empty) acc->version = acc->model->version;
+  if (sign > 0) {
+    acc->rows += n;
+    acc->batches += 1;
+  } else {
+    acc->rows -= n;
+    acc->batches -= acc->batches > 0 ? 1 : 0;
+    // nothing left: the sums are rounding residue of what was there, the state starts afresh
+    if (acc->rows == 0) OB_TRY(zero_state(acc));
+  }
+  return 0;
+}
+
+int obhip_normal_acc_combine_dev(obhip_normal_acc *dst, const obhip_normal_acc *src, int sign) {
+  if (!dst || !src || (sign != 1 && sign != -1)) return fail(OBHIP_ERR_INVALID, "normal_acc_combine_dev: bad argument");
+  if (dst == src) return fail(OBHIP_ERR_INVALID, "normal_acc_combine_dev: an accumulator cannot be combined with itself");
+  if (dst->model != src->model || !same_terms(dst->terms, src->terms) || dst->p != src->p || dst->q != src->q)
+    return fail(OBHIP_ERR_INVALID, "normal_acc_combine_dev: the accumulators differ in model, terms or responses");
+  if (src->rows == 0) return 0;
+  OB_TRY(check_version(dst, "normal_acc_combine_dev"));
+  OB_TRY(check_version(src, "normal_acc_combine_dev"));
+  if (sign < 0 && src->rows > dst->rows)
+    return fail(OBHIP_ERR_STATE, "normal_acc_combine_dev: removing " + std::to_string(src->rows) +
+                                     " rows from an accumulator that holds " + std::to_string(dst->rows));
+  OB_TRY(require_device());
+  const bool empty = dst->rows == 0;
+  OB_TRY(launch_acc_fold(dst->p, dst->q, dst->st.p, src->st.p, empty, (double)sign));
+  if (empty) dst->version = src->version;
+  if (sign > 0) {
+    dst->rows += src->rows;
+    dst->batches += src->batches;
+  } else {
+    dst->rows -= src->rows;
+    dst->batches -= std::min(dst->batches, src->batches);
+    if (dst->rows == 0) OB_TRY(zero_state(dst));
+  }
+  return 0;
+}
+
+int obhip_normal_acc_solve_dev(const obhip_normal_acc *acc, const obhip_normal_acc *minus, double sigma, double rho,
+                               double *d_H, double *d_Theta, double *d_diagH, double *d_meansd, void *d_workspace,
+                               uint64_t workspace_bytes) {
+  if (!acc || !d_H || !d_Theta || !d_meansd || !d_workspace)
+    return fail(OBHIP_ERR_INVALID, "normal_acc_solve_dev: null argument");
+  if (minus && (minus->model != acc->model || !same_terms(minus->terms, acc->terms) || minus->p != acc->p || minus->q != acc->q))
+    return fail(OBHIP_ERR_INVALID, "normal_acc_solve_dev: the accumulators differ in model, terms or responses");
+  const obhip_model *m = acc->model;
+  OB_TRY(check_compat_of(m, acc->terms));
+  OB_TRY(check_version(acc, "normal_acc_solve_dev"));
+  if (minus) OB_TRY(check_version(minus, "normal_acc_solve_dev"));
+  if (minus && minus->rows > acc->rows)
+    return fail(OBHIP_ERR_STATE, "normal_acc_solve_dev: more rows to take out than the accumulator holds");
+  const uint64_t left = acc->rows - (minus ? minus->rows : 0);
+  if (left < 2)
+    return fail(OBHIP_ERR_STATE, "normal_acc_solve_dev: " + std::to_string(left) +
+                                     " rows left, the standard deviation of a response needs two");
+  const uint64_t p = acc->p, q = acc->q;
+  uint64_t need = 0, single = 0;
+  OB_TRY(obhip_newton_multi_workspace_bytes(p, q, &need));
+  OB_TRY(obhip_newton_workspace_bytes(p, &single));
+  if (workspace_bytes < need) return fail(OBHIP_ERR_INVALID, "normal_acc_solve_dev: workspace too small");
+  OB_TRY(require_device());
+  obhip_terms &t = *const_cast<obhip_terms *>(acc->terms);
+  if (!t.prec_dev.p || t.prec_model != m || t.prec_version != m->version || t.prec_rho != rho) {
+    const std::vector<double> prec = prior_prec_of(*m, t, rho);
+    OB_TRY(t.prec_dev.upload(prec.data(), p));  // (synchronises: prec is a local)
+    t.prec_model = m;
+    t.prec_version = m->version;
+    t.prec_rho = rho;
+  }
+  const double e2 = std::exp(-2.0 * sigma);
+  const double *d_minus = minus && minus->rows > 0 ? minus->st.p : nullptr;
+  DevBuf<double> rhs;
+  OB_TRY(rhs.alloc(p * q));
+  OB_TRY(launch_acc_form(p, acc->st.p, d_minus, d_H, e2, t.prec_dev.p, d_diagH));
+  OB_TRY(launch_acc_rhs(p, q, acc->st.p, d_minus, e2, rhs.p, d_meansd));
+  void *d_cholws = (double *)d_workspace + 2 * p;
+  OB_TRY(launch_newton_solve(p, d_H, rhs.p, d_Theta, d_cholws, newton_workspace_bytes(p)));
+  if (q == 1) return 0;
+  // the right-hand sides carry e^{-2 sigma} already
+  return launch_trsm_multi(p, d_H, newton_workspace_iinv(p, d_cholws), rhs.p + p, p, q - 1, 1.0, d_Theta + p,
+                           (char *)d_workspace + single);
+}
+
+int obhip_cv_score_dev(const double *d_mean, const double *d_Y_raw, uint64_t n, uint64_t q, uint64_t ld,
+                       const double *d_meansd, double *d_out) {
+  if (!d_out || q == 0 || q > kMaxResponses || (n != 0 && (!d_mean || !d_Y_raw || ld < n)))
+    return fail(OBHIP_ERR_INVALID, "cv_score_dev: bad argument");
+  OB_TRY(require_device());
+  DevBuf<double> part;
+  OB_TRY(part.alloc(512 * q));
+  return launch_cv_score(d_mean, d_Y_raw, n, q, ld, d_meansd, d_out, part.p);
+}
+
+}  // extern "C"

@@ -19,7 +19,7 @@ from ._lib import call
 DEFAULT_RHO = 6.0  # logpr_gauss.cpp:48
 
 
-def _check_xy(om, x, Y):
+def _check_xy(om, x, Y, min_rows=2):
     x = np.asarray(x, dtype=np.float64)
     Y = np.asarray(Y, dtype=np.float64)
     if Y.ndim == 1:
@@ -32,7 +32,7 @@ def _check_xy(om, x, Y):
         raise ValueError("Y has %d rows, x has %d" % (Y.shape[0], x.shape[0]))
     if Y.shape[1] == 0:
         raise ValueError("Y has no columns")
-    if x.shape[0] < 2:
+    if x.shape[0] < min_rows:
         raise ValueError("the standard deviation of a response needs two rows")
     if not np.all(np.isfinite(Y)):
         raise ValueError("Y must be finite")

@@ -1,0 +1,303 @@
+"""Streaming Newton fit: rows come and go, every row is passed over once.
+
+fit_newton_multi takes all rows at once and pays the whole Gram per call.  A NewtonAccumulator
+keeps the normal equations of the rows it has been given on the device (include/obhip.h,
+"streaming Newton fit"): the packed upper triangle of G = B^T B, B^T (Y - c), B^T 1 and per
+response the moments (n, mean, M2) in merge form.  Adding a batch costs the Gram of that batch,
+a fit one Cholesky factorisation; batches can be taken out again, and a fit can leave the rows of
+another accumulator out without touching either -- which makes K-fold cross-validation over a
+grid of (sigma, rho) one pass over the rows plus K x C factorisations (cv_newton_multi).
+
+torch holds the device memory; all arithmetic is in libobhip.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import obmod
+from ._lib import call, lib
+from .multi import DEFAULT_RHO, MultiFit, _check_xy
+
+
+def _stream():
+    import torch
+    call("obhip_set_stream", C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+class NewtonAccumulator:
+    """The normal equations of a growing / shrinking set of rows for q responses over one model and
+    term set.  Device memory: 8 (p (p + 1) / 2 + p q + p + 4 q) bytes (obhip_normal_acc_bytes), and
+    as much again as pooled scratch while a batch is added."""
+
+    def __init__(self, om, terms, q=1):
+        q = int(q)
+        if q < 1:
+            raise ValueError("q must be at least 1")
+        self.om, self._t, self.q = om, obmod._terms_of(om, terms), q
+        self.p = self._t.p
+        self._h = None          # made on first use: nothing here touches the device
+        self._closed = False
+        self._bufs = None
+
+    # -- life time ---------------------------------------------------------------------------
+    def close(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.obhip_normal_acc_destroy(self._h)
+        self._h = None
+        self._closed = True
+        self._bufs = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def _need(self):
+        if self._closed:
+            raise RuntimeError("the accumulator is closed")
+        if not self._h:
+            h = C.c_void_p()
+            call("obhip_normal_acc_create", C.byref(h), self.om._h, self._t._h, self.q)
+            self._h = h
+
+    # -- state -------------------------------------------------------------------------------
+    def _info(self):
+        self._need()
+        v = [C.c_uint64(0) for _ in range(4)]
+        call("obhip_normal_acc_info", self._h, *[C.byref(a) for a in v])
+        return [a.value for a in v]
+
+    @property
+    def rows(self):
+        return self._info()[2]
+
+    @property
+    def batches(self):
+        return self._info()[3]
+
+    def reset(self):
+        self._need()
+        call("obhip_normal_acc_reset", self._h)
+
+    def state(self):
+        """Host copy of the state: tri (packed upper triangle of G), rhs (p x q: B^T (Y - shift)),
+        b1 (B^T 1), shift, mu (mean - shift), M2, n (q each)."""
+        import torch
+        self._need()
+        dev = _stream()
+        p, q = self.p, self.q
+        nb = C.c_uint64(0)
+        call("obhip_normal_acc_bytes", p, q, C.byref(nb))
+        buf = torch.empty(nb.value // 8, dtype=torch.float64, device=dev)
+        call("obhip_normal_acc_export_dev", self._h, buf.data_ptr(), buf.numel())
+        s = buf.cpu().numpy()
+        tri = p * (p + 1) // 2
+        mom = s[tri + p * q + p:].reshape(q, 4)
+        return dict(tri=s[:tri].copy(), rhs=s[tri:tri + p * q].reshape(q, p).T.copy(), b1=s[tri + p * q:tri + p * q + p].copy(),
+                    shift=mom[:, 0].copy(), mu=mom[:, 1].copy(), M2=mom[:, 2].copy(), n=mom[:, 3].copy())
+
+    # -- rows in and out ---------------------------------------------------------------------
+    def _check(self, x, Y):
+        x, Y = _check_xy(self.om, x, Y, min_rows=0)
+        if Y.shape[1] != self.q:
+            raise ValueError("Y has %d columns, the accumulator %d responses" % (Y.shape[1], self.q))
+        if not np.all(np.isfinite(x)):
+            raise ValueError("x must be finite")
+        return x, Y
+
+    def _batch_dev(self, dx, dY, n, sign):
+        """dx (d, n), dY (q, n): device tensors, column-major n x d and n x q"""
+        self._need()
+        caps = self._t.maxlevels()
+        basis = C.c_void_p()
+        call("obhip_basis_create_dev", C.byref(basis), self.om._h, dx.data_ptr(), n, caps.ctypes.data)
+        try:
+            call("obhip_normal_acc_add_dev", self._h, basis, dY.data_ptr(), n, sign)
+            import torch
+            torch.cuda.synchronize()
+        finally:
+            call("obhip_basis_destroy", basis)
+
+    def _batch(self, x, Y, sign):
+        x, Y = self._check(x, Y)
+        self._need()
+        n = x.shape[0]
+        if n == 0:
+            return self
+        import torch
+        dev = _stream()
+        dx = torch.from_numpy(np.ascontiguousarray(x.T)).to(dev)
+        dY = torch.from_numpy(np.ascontiguousarray(Y.T)).to(dev)
+        self._batch_dev(dx, dY, n, sign)
+        return self
+
+    def add(self, x, Y):
+        """Add the rows x (n x d) with their raw responses Y (n x q, or n for q = 1); n = 0 is a
+        no-op.  The basis of the batch is built, used once and destroyed."""
+        return self._batch(x, Y, +1)
+
+    def remove(self, x, Y):
+        """Take out rows that were added before (the same x and Y)."""
+        return self._batch(x, Y, -1)
+
+    def merge(self, other, sign=+1):
+        """self += sign * other (another accumulator of the same model, terms and q)"""
+        if not isinstance(other, NewtonAccumulator):
+            raise TypeError("merge takes a NewtonAccumulator")
+        if sign not in (1, -1):
+            raise ValueError("sign must be +1 or -1")
+        self._need()
+        other._need()
+        _stream()
+        call("obhip_normal_acc_combine_dev", self._h, other._h, int(sign))
+        return self
+
+    # -- the fit -----------------------------------------------------------------------------
+    def _solve_dev(self, sigma, rho, minus=None):
+        """-> Theta (q, p), diagH (p), meansd (q, 3): device tensors, reused by the next call"""
+        import torch
+        self._need()
+        if minus is not None:
+            if not isinstance(minus, NewtonAccumulator):
+                raise TypeError("minus must be a NewtonAccumulator")
+            minus._need()
+        dev = _stream()
+        p, q, f64 = self.p, self.q, torch.float64
+        if self._bufs is None or self._bufs["H"].device != dev:
+            wsb = C.c_uint64(0)
+            call("obhip_newton_multi_workspace_bytes", p, q, C.byref(wsb))
+            self._bufs = dict(ws=torch.empty(wsb.value, dtype=torch.uint8, device=dev),
+                              H=torch.empty((p, p), dtype=f64, device=dev),
+                              theta=torch.empty((q, p), dtype=f64, device=dev),
+                              diagH=torch.empty(p, dtype=f64, device=dev),
+                              meansd=torch.empty((q, 3), dtype=f64, device=dev))
+        b = self._bufs
+        call("obhip_normal_acc_solve_dev", self._h, None if minus is None else minus._h, sigma, rho,
+             b["H"].data_ptr(), b["theta"].data_ptr(), b["diagH"].data_ptr(), b["meansd"].data_ptr(),
+             b["ws"].data_ptr(), b["ws"].numel())
+        return b["theta"], b["diagH"], b["meansd"]
+
+    def fit(self, sigma=None, rho=DEFAULT_RHO, minus=None):
+        """One Newton step from coeff = 0 (lpdf::optnewton, fit.cpp:98-131) on the rows in the
+        accumulator -- with minus, on those rows without the rows of that accumulator, neither being
+        changed -- every response standardised over exactly those rows.  -> MultiFit, as
+        fit_newton_multi returns it.  sigma=None: log(0.01)."""
+        import torch
+        if sigma is None:
+            sigma = math.log(0.01)
+        theta, diagH, meansd = self._solve_dev(float(sigma), float(rho), minus)
+        torch.cuda.synchronize()
+        return MultiFit(self.om, self._t, theta.cpu().numpy().T.copy(), meansd.cpu().numpy(), diagH.cpu().numpy(),
+                        float(sigma), float(rho))
+
+
+def cv_folds(n, folds, seed=0):
+    """Fold of every row: a seeded permutation dealt round-robin, so the fold sizes differ by at
+    most one and the same (n, folds, seed) always gives the same assignment."""
+    n, folds = int(n), int(folds)
+    if folds < 2 or folds > n:
+        raise ValueError("folds must be between 2 and the number of rows")
+    perm = np.random.default_rng(seed).permutation(n)
+    fold_of = np.empty(n, dtype=np.int64)
+    fold_of[perm] = np.arange(n) % folds
+    return fold_of
+
+
+class CVResult:
+    """candidates: the C pairs (sigma, rho), sigma-major; rmse (C x q): held-out root mean squared
+    error per response in raw units; score (C): mean over the responses of rmse / sd(y);
+    best: its argmin (the first among equals); sigma, rho: that candidate; heldout (n x q): every
+    row's prediction by the fit that did not see it, at the best candidate; fit: the MultiFit of all
+    rows at the best candidate; fold_of (n)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def cv_newton_multi(om, terms, x, Y, folds=5, sigmas=(math.log(0.01),), rhos=(DEFAULT_RHO,), seed=0):
+    """K-fold cross-validation of the Newton fit over the grid sigmas x rhos.
+
+    Rows are dealt to K folds by cv_folds(n, folds, seed).  Every fold's rows go through the Gram
+    kernels ONCE into an accumulator of their own, and the K accumulators are summed into one more:
+    the Gram work is one pass over the n rows whatever K and the grid are.  For every candidate and
+    fold the fit of `all rows minus the fold` is one unpack of two triangles and one Cholesky
+    factorisation (NewtonAccumulator.fit(minus=...)); the fold's rows are predicted with
+    obhip_predict_multi_dev and scored on the device (obhip_cv_score_dev).
+
+    Device memory: K + 1 accumulators -- (K + 1) x 8 (p (p + 1) / 2 + p q + p + 4 q) bytes, 67 MB
+    each at p = 4096 -- plus one more as scratch while the folds are added, the p x p Hessian, and
+    x, Y and two n x q prediction buffers.
+
+    -> CVResult"""
+    x, Y = _check_xy(om, x, Y)
+    if not np.all(np.isfinite(x)):
+        raise ValueError("x must be finite")
+    sigmas = [float(s) for s in np.atleast_1d(sigmas)]
+    rhos = [float(r) for r in np.atleast_1d(rhos)]
+    if not sigmas or not rhos or not np.all(np.isfinite(sigmas + rhos)):
+        raise ValueError("sigmas and rhos must be non-empty and finite")
+    n, q = Y.shape
+    fold_of = cv_folds(n, folds, seed)
+    K = int(folds)
+    if n - int(np.bincount(fold_of, minlength=K).max()) < 2:
+        raise ValueError("a fit needs two rows outside every fold")
+    import torch
+    dev = _stream()
+    t = obmod._terms_of(om, terms)
+    f64 = torch.float64
+    idx = [np.nonzero(fold_of == k)[0] for k in range(K)]
+    accs, total = [], None
+    try:
+        dxs, dYs = [], []
+        for k in range(K):
+            a = NewtonAccumulator(om, t, q)
+            accs.append(a)
+            dxs.append(torch.from_numpy(np.ascontiguousarray(x[idx[k]].T)).to(dev))
+            dYs.append(torch.from_numpy(np.ascontiguousarray(Y[idx[k]].T)).to(dev))
+            a._batch_dev(dxs[k], dYs[k], len(idx[k]), +1)
+        total = NewtonAccumulator(om, t, q)
+        for a in accs:
+            total.merge(a)
+        cands = [(s, r) for s in sigmas for r in rhos]
+        sd = Y.std(axis=0, ddof=1)
+        rmse = np.empty((len(cands), q))
+        score = np.empty(len(cands))
+        held = [[torch.empty((q, len(i)), dtype=f64, device=dev) for i in idx] for _ in range(2)]
+        out = torch.empty((K, q, 2), dtype=f64, device=dev)
+        best, cur = -1, 0
+        for c, (s, r) in enumerate(cands):
+            for k in range(K):
+                theta, _, meansd = total._solve_dev(s, r, minus=accs[k])
+                m, nk = held[cur][k], len(idx[k])
+                call("obhip_predict_multi_dev", om._h, t._h, theta.data_ptr(), q, dxs[k].data_ptr(), nk, m.data_ptr(),
+                     None, s, None)
+                call("obhip_cv_score_dev", m.data_ptr(), dYs[k].data_ptr(), nk, q, nk, meansd.data_ptr(),
+                     out[k].data_ptr())
+                call("obhip_destandardise_multi_dev", m.data_ptr(), nk, q, nk, meansd.data_ptr(), 0)
+            torch.cuda.synchronize()
+            o = out.cpu().numpy()
+            sse = np.zeros(q)
+            for k in range(K):          # fold after fold: a fixed order
+                sse += o[k, :, 0]
+            assert int(o[:, 0, 1].sum()) == n
+            rmse[c] = np.sqrt(sse / n)
+            score[c] = float(np.mean(rmse[c] / sd))
+            if best < 0 or score[c] < score[best]:
+                best, cur = c, 1 - cur
+        heldout = np.empty((n, q))
+        for k in range(K):
+            heldout[idx[k]] = held[1 - cur][k].cpu().numpy().T
+        fit = total.fit(cands[best][0], cands[best][1])
+    finally:
+        for a in accs:
+            a.close()
+        if total is not None:
+            total.close()
+    return CVResult(candidates=cands, rmse=rmse, score=score, best=best, sigma=cands[best][0], rho=cands[best][1],
+                    heldout=heldout, fit=fit, fold_of=fold_of)
