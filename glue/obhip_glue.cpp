@@ -425,6 +425,15 @@ public:
   void update(NumericMatrix x) { ck(obhip_predictor_update(h, x.begin(), x.nrow(), x.nrow())); }
   NumericVector mean() { uint64_t n; ck(obhip_predictor_n(h, &n)); NumericVector out(n); ck(obhip_predictor_mean(h, out.begin())); return out; }
   NumericVector var() { uint64_t n; ck(obhip_predictor_n(h, &n)); NumericVector out(n); ck(obhip_predictor_var(h, out.begin())); return out; }
+  // d mean / d x at the rows of the last update(), n x d (the reference has no counterpart)
+  NumericMatrix gradmean() {
+    uint64_t n, d;
+    ck(obhip_predictor_n(h, &n));
+    ck(obhip_predictor_d(h, &d));
+    NumericMatrix out(n, d);
+    ck(obhip_predictor_gradmean(h, out.begin()));
+    return out;
+  }
   void setnthreads(int k) { ck(obhip_predictor_setnthreads(h, k)); }
 };
 
@@ -495,6 +504,7 @@ RCPP_MODULE(obmod) {                                       // ref src/interfaceR
       .method("update", &predictor::update)
       .method("mean", &predictor::mean)
       .method("var", &predictor::var)
+      .method("gradmean", &predictor::gradmean)
       .method("setnthreads", &predictor::setnthreads);
 
   class_<loglik_std>("loglik_std")

@@ -616,6 +616,39 @@ int obhip_predict(const obhip_model *m, const obhip_terms *t,
                   const double *theta, const double *x, uint64_t n,
                   uint64_t ldx, double *mean, const double *coeffvar,
                   double sigma, double *var);
+/* Gradients of the predictive mean and variance by the inputs, at new rows.  The reference has no
+ * counterpart.  With R_l = cov_l(x_l, knots_l) . rotmat_l, R'_l = (dcov_l / dx_l) . rotmat_l and, per
+ * row, s = prod_l R_l0, r_lt = R_lt / R_l0, rho_l = R'_l0 / R_l0, r'_lt = (R'_lt - r_lt R'_l0) / R_l0,
+ * P_k = prod_{l: t_kl > 0} r_l,t_kl and E_kl = P_k without dimension l's factor (a product, never a
+ * quotient):
+ *   mean       = s sum_k theta_k P_k
+ *   dmean/dx_l = s (rho_l sum_k theta_k P_k + sum_{k: t_kl > 0} theta_k E_kl r'_l,t_kl)
+ *   var        = s^2 sum_k c_k P_k^2 + e^{2 sigma}
+ *   dvar/dx_l  = 2 s^2 (rho_l sum_k c_k P_k^2 + sum_{k: t_kl > 0} c_k P_k E_kl r'_l,t_kl)
+ * dcov/dx, with h2 = h (1 + |h|) e^{-|h|} and w = (1 + h) e^{-h}:
+ *   mat25     u = x / e^{2 th0}, h = u - u_knot:                    -(1/3) h2 / e^{2 th0}
+ *   mat25pow  a = e^{th1/4}, t = x^a / e^{2 th0 + th1/4}, h = t - t_knot:   -(1/3) h2 a t / x
+ *   mat25ang  hs = (sin x - sin k) / e^{2 th0}, hc = (cos x - cos k) / e^{2 th1}, h = sqrt(hs^2 + hc^2):
+ *             -(1/3) w (hs cos x / e^{2 th0} - hc sin x / e^{2 th1})   -- nothing divides by h
+ * One fused kernel per call; neither the basis nor its derivative is written to HBM while the
+ * terms use at most 8 factors and 2 Mu + d + 31 <= 320 (Mu used basis columns).  Beyond that, and
+ * under OBHIP_FORCE_GENERIC, the same contraction runs from a pooled HBM tile per block (any term
+ * set obhip_predict_dev accepts).  No atomics: two calls give the same bits.
+ * d_grad, d_gradvar: n x d column-major, ld = n (the layout of d_x).  d_mean may be NULL.
+ * d_coeffvar (p) NULL: d_var and d_gradvar are untouched (d_gradvar without d_coeffvar is an
+ * error); with it each of d_var (n) and d_gradvar may be NULL.  n = 0 is a no-op; at most 2^40
+ * rows per call.  Argument errors return OBHIP_ERR_INVALID before any device call. */
+int obhip_predict_grad_dev(const obhip_model *m, const obhip_terms *t, const double *d_theta,
+                           const double *d_x, uint64_t n, double *d_mean, double *d_grad,
+                           const double *d_coeffvar, double sigma, double *d_var, double *d_gradvar);
+/* the same on host buffers: x n x d with ldx, grad / gradvar n x d with ldg */
+int obhip_predict_grad(const obhip_model *m, const obhip_terms *t, const double *theta, const double *x,
+                       uint64_t n, uint64_t ldx, double *mean, double *grad, uint64_t ldg,
+                       const double *coeffvar, double sigma, double *var, double *gradvar);
+/* the terms that have dimension dim (0-based) at a level > 0, in term order: what the gradient by
+ * x_dim sums over beside the dense part.  *count always; terms_out (count entries) may be NULL.
+ * Host only. */
+int obhip_terms_dimview(const obhip_terms *t, uint64_t dim, uint64_t *count, uint32_t *terms_out);
 /* predr_std (loglik_std.cpp:218-256), the predictor of the loglik_std model with the full
  * posterior covariance of the coefficients: mean = B theta, var_i = b_i^T inv(H) b_i +
  * e^{2 sigma} (:249-256; the reference uses arma::inv; here H = L L^T by the library's own
@@ -744,6 +777,10 @@ int obhip_predictor_n(const obhip_predictor *p, uint64_t *n);
 /* predictor$mean() / $var(): n values */
 int obhip_predictor_mean(obhip_predictor *p, double *out);
 int obhip_predictor_var(obhip_predictor *p, double *out);
+/* d mean / d x at the rows of the last update(): n x d column-major (obhip_predict_grad_dev; no
+ * reference counterpart).  The mean is the same B theta for all three likelihoods. */
+int obhip_predictor_gradmean(obhip_predictor *p, double *out);
+int obhip_predictor_d(const obhip_predictor *p, uint64_t *d); /* input dimensions of its model */
 
 /* ---- synthetic workload of BASELINE.md section 3 (benchmark input) ------ */
 /* rows [row0, row0+n) of the counter-based SplitMix64 stream; d_x is n x d

@@ -10,8 +10,8 @@ from . import _lib
 from ._lib import ObhipError, device_count
 from .obmod import (covf, covf_mat25, covf_mat25ang, covf_mat25pow, gethyp, getpara, hypnames,
                     listcov, loglik_gauss, loglik_gda, loglik_std, logpr_gauss, lpdf, lpdfvec,
-                    outerbase, outermod, predictor, setcovfs, setknot)
-from .fitting import BFGS_lpdf, BFGS_std, obfit, obpred
+                    outerbase, outermod, predict_grad, predictor, setcovfs, setknot, term_dim_views)
+from .fitting import BFGS_lpdf, BFGS_std, obfit, obpred, obpred_grad
 from .multi import MultiFit, fit_newton_multi
 from .driver import HotPath, MultiHotPath
 from .stream import CVResult, NewtonAccumulator, cv_folds, cv_newton_multi
@@ -23,4 +23,5 @@ __all__ = [
     "BFGS_lpdf", "BFGS_std", "obfit", "obpred",
     "MultiFit", "fit_newton_multi", "HotPath", "MultiHotPath",
     "NewtonAccumulator", "cv_newton_multi", "cv_folds", "CVResult",
+    "predict_grad", "obpred_grad", "term_dim_views",
 ]

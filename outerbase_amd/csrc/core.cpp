@@ -441,6 +441,7 @@ int obhip_terms::prepare(const std::vector<int64_t> &cap,
   std::vector<int32_t> hpos(Mc, -1);
   for (size_t u = 0; u < used.size(); ++u) hpos[used[u]] = (int32_t)u;
   OB_TRY(cpos.upload(hpos.data(), hpos.size()));
+  cpos_h = hpos;
   cached_cap = cap;
   return 0;
 }

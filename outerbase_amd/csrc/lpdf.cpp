@@ -1523,4 +1523,20 @@ int obhip_predictor_var(obhip_predictor *p, double *out) {
   return d2h(out, p->dvar.p, p->n * sizeof(double));
 }
 
+int obhip_predictor_d(const obhip_predictor *p, uint64_t *d) {
+  if (!p || !d) return fail(OBHIP_ERR_INVALID, "predictor_d: null argument");
+  *d = p->om->d;
+  return 0;
+}
+
+int obhip_predictor_gradmean(obhip_predictor *p, double *out) {
+  if (!p || !out) return fail(OBHIP_ERR_INVALID, "predictor_gradmean: null argument");
+  DevBuf<double> dth, dg;
+  OB_TRY(dth.upload(p->coeff.data(), p->coeff.size()));
+  OB_TRY(dg.alloc(p->n * p->om->d));
+  OB_TRY(obhip_predict_grad_dev(p->om, p->t, dth.p, p->x.p, p->n, nullptr, dg.p, nullptr, p->para[0], nullptr,
+                                nullptr));
+  return d2h(out, dg.p, p->n * p->om->d * sizeof(double));
+}
+
 }  // extern "C"

@@ -281,6 +281,7 @@ struct obhip_terms {
   obhip::DevBuf<uint32_t> ucol;       // Mu compact column ids (used list)
   obhip::DevBuf<uint32_t> sperm;      // p_pad: terms ordered by falling number of factors (stable)
   obhip::DevBuf<int32_t> cpos;        // compact column -> used index or -1 (Mc)
+  std::vector<int32_t> cpos_h;        // host copy (the dimension views of the input-gradient predictor)
   uint64_t p_pad = 0;
   // star tables (shared sub-products, csrc/share.cpp); sh.ok false: the kernels take sperm / cols
   obhip::ShareTables sh;              // (host copies dropped after the upload; counts kept)
@@ -323,6 +324,20 @@ struct obhip_terms {
   // device view of the model capped at maxlev, for the fused predictor
   obhip::ModelDev pred_md;
   const obhip_model *pred_model = nullptr;
+  // input-gradient predictor (kernels_predict_dx.hip, predict_dx.cpp): per dimension l the view of
+  // the terms that have l -- entry = W / 2 words of the term's OTHER used columns (own slot = the
+  // ones column), its own used column, its term index -- and the derivative interval tables
+  struct Dx {
+    std::vector<uint64_t> voff;      // d + 1: first view entry of every dimension (host; from lev alone)
+    std::vector<uint32_t> vterm;     // term index of every view entry (host)
+    std::vector<int64_t> cap;        // level caps (= column layout) the device tables were packed for
+    obhip::DevBuf<uint32_t> vw;      // entries x (W / 2 + 2) words
+    obhip::DevBuf<uint32_t> voff_dev;
+    obhip::DevBuf<double> dtab;      // layout of ModelDev::tab, the sums of dk/du in place of those of k
+    const obhip_model *tab_model = nullptr;
+    uint64_t tab_version = ~0ull;
+    std::vector<int64_t> tab_cap;
+  } dx;
   // prior precisions 1 / (sd e^rho)^2 of these terms on the device, for the model state and rho
   // they were last asked for (the device-side Newton fit: no upload, no host sync per fit)
   obhip::DevBuf<double> prec_dev;
@@ -529,6 +544,13 @@ int launch_predict_multi(const obhip_model &m, obhip_terms &t, const double *d_T
 int launch_predict(const obhip_model &m, obhip_terms &t, const double *d_theta,
                    const double *d_x, uint64_t n, double *d_mean,
                    const double *d_coeffvar, double e2sigma, double *d_var);
+// kernels_predict_dx.hip / predict_dx.cpp: mean, variance and their gradients by the inputs
+bool predict_dx_supports(const obhip_terms &t);
+void build_dim_views_host(obhip_terms &t);               // t.dx.voff / vterm (no device needed)
+int ensure_dx_tables(const obhip_model &m, obhip_terms &t);  // after t.prepare(t.pred_md.cap, ...)
+int launch_predict_dx(const obhip_model &m, obhip_terms &t, const double *d_theta, const double *d_x, uint64_t n,
+                      double *d_mean, double *d_grad, const double *d_coeffvar, double e2sigma, double *d_var,
+                      double *d_gradvar);
 // small vector kernels (kernels_misc.hip)
 int launch_synth(uint64_t seed, uint64_t row0, uint64_t n, uint64_t d,
                  const int *d_kinds, double *d_x, double *d_y);

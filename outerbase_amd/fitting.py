@@ -391,3 +391,11 @@ def obpred(obmodel, x):
     p.update(np.asarray(x, dtype=np.float64))
     return dict(mean=obmodel["y_cent"] + obmodel["y_sca"] * p.mean(),
                 var=obmodel["y_sca"] ** 2 * p.var())
+
+
+def obpred_grad(obmodel, x):
+    """obpred plus the gradient of the mean by the inputs: dict(mean, var, gradmean), gradmean n x d,
+    de-standardised like the mean (no reference counterpart)."""
+    out = obpred(obmodel, x)
+    out["gradmean"] = obmodel["y_sca"] * obmodel["predobj"].gradmean()
+    return out

@@ -84,6 +84,46 @@ class MultiFit:
         call("obhip_destandardise_multi_dev", vq.data_ptr(), n, q, n, dms.data_ptr(), 1)
         return mean.cpu().numpy().T, vq.cpu().numpy().T
 
+    def predict_grad(self, xnew, var=False):
+        """De-standardised (mean n x q, grad n x d x q) at xnew, grad[i, l, j] = d mean_ij / d x_il;
+        with var=True also (var n x q, gradvar n x d x q).  One obhip_predict_grad_dev call per
+        response (a batched form is not built); the variance and its gradient are computed once, with
+        response 0, and scaled by y_sca^2 as predict does with the variance."""
+        import torch
+        xnew = np.asarray(xnew, dtype=np.float64)
+        if xnew.ndim != 2 or xnew.shape[1] != self.om.d:
+            raise ValueError("xnew must be n x d")
+        n, q, d, f64 = xnew.shape[0], self.q, self.om.d, torch.float64
+        if n == 0:
+            z, g = np.zeros((0, q)), np.zeros((0, d, q))
+            return (z, g, z.copy(), g.copy()) if var else (z, g)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        call("obhip_set_stream", C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        dx = torch.from_numpy(np.ascontiguousarray(xnew.T)).to(dev)          # column-major n x d
+        dth = torch.from_numpy(np.ascontiguousarray(self.coeff.T)).to(dev)   # column-major p x q
+        mean = torch.empty((q, n), dtype=f64, device=dev)
+        grad = torch.empty((q, d, n), dtype=f64, device=dev)
+        dcv = dvar = dgv = None
+        if var:
+            dcv = torch.from_numpy(1.0 / self.diagH).to(dev)
+            dvar = torch.empty(n, dtype=f64, device=dev)
+            dgv = torch.empty((d, n), dtype=f64, device=dev)
+        for j in range(q):
+            first = var and j == 0
+            call("obhip_predict_grad_dev", self.om._h, self._t._h, dth[j].data_ptr(), dx.data_ptr(), n,
+                 mean[j].data_ptr(), grad[j].data_ptr(), dcv.data_ptr() if first else None, self.sigma,
+                 dvar.data_ptr() if first else None, dgv.data_ptr() if first else None)
+        sca = torch.from_numpy(self.y_sca).to(dev)
+        cent = torch.from_numpy(self.y_cent).to(dev)
+        mean = mean * sca[:, None] + cent[:, None]
+        grad = grad * sca[:, None, None]
+        out = (mean.cpu().numpy().T, grad.permute(2, 1, 0).cpu().numpy())
+        if not var:
+            return out
+        s2 = sca * sca
+        return out + ((dvar[None, :] * s2[:, None]).cpu().numpy().T,
+                      (dgv[None, :, :] * s2[:, None, None]).permute(2, 1, 0).cpu().numpy())
+
 
 def fit_newton_multi(om, terms, x, Y, sigma=None, rho=DEFAULT_RHO, comm=None):
     """One Newton step from coeff = 0 of lpdfvec(loglik_std, logpr_gauss) (lpdf::optnewton,

@@ -735,3 +735,51 @@ class predictor:
         out = np.empty(self._n())
         call("obhip_predictor_var", self._h, ptr(out))
         return out
+
+    def gradmean(self):
+        """d mean / d x at the rows of the last update(): n x d (no reference counterpart)"""
+        out = np.empty((self._n(), self.om.d), order="F")
+        call("obhip_predictor_gradmean", self._h, ptr(out))
+        return out
+
+
+# ----------------------------------------------------------------------------
+# input gradients of the predictor (include/obhip.h obhip_predict_grad_dev; no reference counterpart)
+# ----------------------------------------------------------------------------
+def predict_grad(om, terms, coeff, xnew, coeffvar=None, sigma=None):
+    """(mean, grad) at the rows xnew (n x d) of the model om with the terms and coefficients given:
+    mean = B(x) coeff (n) and grad[i, l] = d mean_i / d x_il (n x d).  With coeffvar (p) also
+    (var, gradvar) of var = B^2 coeffvar + e^{2 sigma} (sigma=None: 0): (mean, grad, var, gradvar)."""
+    t = _terms_of(om, terms)
+    x = _fmat(xnew)
+    if x.ndim != 2 or x.shape[1] != om.d:
+        raise ValueError("xnew must be n x d")
+    coeff = _f64(coeff)
+    if coeff.shape != (t.p,):
+        raise ValueError("coeff must have one entry per term")
+    n = x.shape[0]
+    mean, grad = np.empty(n), np.empty((n, om.d), order="F")
+    cv = var = gradvar = None
+    if coeffvar is not None:
+        cv = _f64(coeffvar)
+        if cv.shape != (t.p,):
+            raise ValueError("coeffvar must have one entry per term")
+        var, gradvar = np.empty(n), np.empty((n, om.d), order="F")
+    call("obhip_predict_grad", om._h, t._h, ptr(coeff), ptr(x), n, max(n, 1), ptr(mean), ptr(grad), max(n, 1),
+         ptr(cv), 0.0 if sigma is None else float(sigma), ptr(var), ptr(gradvar))
+    return (mean, grad) if cv is None else (mean, grad, var, gradvar)
+
+
+def term_dim_views(om, terms):
+    """per dimension the indices of the terms that have it at a level > 0, in term order: the lists
+    the gradient kernel sums over (obhip_terms_dimview; host only)"""
+    t = _terms_of(om, terms)
+    out = []
+    for l in range(t.d):
+        cnt = C.c_uint64(0)
+        call("obhip_terms_dimview", t._h, l, C.byref(cnt), None)
+        idx = np.empty(cnt.value, dtype=np.uint32)
+        if cnt.value:
+            call("obhip_terms_dimview", t._h, l, C.byref(cnt), ptr(idx))
+        out.append(idx.astype(np.int64))
+    return out
