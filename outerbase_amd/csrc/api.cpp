@@ -24,6 +24,10 @@ std::vector<double> term_var(const obhip_model &m, const obhip_terms &t) {
   return v;
 }
 
+}  // namespace
+
+namespace obhip {
+
 // logpr_gauss::diaghess (logpr_gauss.cpp:122-124)
 std::vector<double> prior_prec(const obhip_model &m, const obhip_terms &t, double rho) {
   std::vector<double> v = term_var(m, t);
@@ -45,6 +49,10 @@ int check_compat(const obhip_model *m, const obhip_terms *t) {
   return 0;
 }
 
+}  // namespace obhip
+
+namespace {
+
 int basis_setup(obhip_basis *b, const obhip_model *m, const int64_t *levelcap) {
   std::vector<int64_t> cap;
   if (levelcap) cap.assign(levelcap, levelcap + m->d);
@@ -57,25 +65,8 @@ int basis_setup(obhip_basis *b, const obhip_model *m, const int64_t *levelcap) {
   return launch_build_basis(*b);
 }
 
-}  // namespace
-
-namespace obhip {
-std::vector<double> prior_prec_of(const obhip_model &m, const obhip_terms &t, double rho) {
-  return prior_prec(m, t, rho);
-}
-int check_compat_of(const obhip_model *m, const obhip_terms *t) { return check_compat(m, t); }
-}  // namespace obhip
-
-namespace {
-
 constexpr size_t kScratch = 2048;  // doubles of scratch of the two-stage reductions: taken from
                                    // the pool per call (keyed by device and stream)
-
-int d2h(void *dst, const void *src, size_t bytes) {
-  OB_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, cur_stream()));
-  OB_HIP(hipStreamSynchronize(cur_stream()));
-  return 0;
-}
 
 }  // namespace
 
@@ -93,14 +84,7 @@ int obhip_basis_create(obhip_basis **out, const obhip_model *m, const double *x,
   b->n_pad = (n + kTileRows - 1) / kTileRows * kTileRows;
   b->d = m->d;
   (void)hipGetDevice(&b->device);
-  int rc = 0;
-  if (ldx == n) {
-    rc = b->x.upload(x, n * m->d);
-  } else {
-    std::vector<double> xc(n * m->d);
-    for (uint64_t l = 0; l < m->d; ++l) std::memcpy(&xc[l * n], x + l * ldx, n * sizeof(double));
-    rc = b->x.upload(xc.data(), xc.size());
-  }
+  int rc = upload_cols(b->x, x, n, m->d, ldx);
   if (!rc) rc = basis_setup(b, m, levelcap);
   if (rc) {
     delete b;
@@ -849,13 +833,7 @@ int obhip_predict(const obhip_model *m, const obhip_terms *t, const double *thet
   OB_TRY(check_compat(m, t));
   OB_TRY(require_device());
   DevBuf<double> dx, dth, dmean, dcv, dvar;
-  if (ldx == n) {
-    OB_TRY(dx.upload(x, n * m->d));
-  } else {
-    std::vector<double> xc(n * m->d);
-    for (uint64_t l = 0; l < m->d; ++l) std::memcpy(&xc[l * n], x + l * ldx, n * sizeof(double));
-    OB_TRY(dx.upload(xc.data(), xc.size()));
-  }
+  OB_TRY(upload_cols(dx, x, n, m->d, ldx));
   OB_TRY(dth.upload(theta, t->p));
   OB_TRY(dmean.alloc(n));
   const bool do_var = coeffvar && var;

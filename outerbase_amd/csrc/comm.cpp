@@ -414,15 +414,6 @@ int obhip_comm_allreduce_dev(obhip_comm *c, double *d_buf, uint64_t count) {
 }  // extern "C"
 
 // ---- the one-buffer exchange of back end A -------------------------------------------------
-namespace obhip {
-uint64_t normal_eq_tail(uint64_t p);
-int launch_pack_normal_eq(uint64_t p, bool with_tri, const double *d_G, const double *d_g,
-                          const double *d_b1, const double *d_sum2, double nlocal, double *d_buf,
-                          uint64_t count);
-int launch_unpack_normal_eq(uint64_t p, bool with_tri, const double *d_buf, double *d_G, double *d_g,
-                            double *d_meansd);
-}  // namespace obhip
-
 extern "C" {
 
 int obhip_normal_eq_count(uint64_t p, int nranks, uint64_t *count) {
@@ -462,13 +453,6 @@ int obhip_normal_eq_exchange_dev(obhip_comm *comm, uint64_t p, uint64_t n_local,
 // pattern instead: 64 rounds of "how many elements, over all ranks, are <= this midpoint",
 // for all columns and all wanted order statistics at once.  Exact: the result is the element
 // a sort of the whole column would put at that position, and the interpolation is R's.
-namespace obhip {
-int quantile_max_targets();
-int launch_count_le(const double *d_x, uint64_t n, uint64_t d, const uint64_t *d_mids, int T,
-                    unsigned long long *d_counts);
-int launch_u64_to_f64(const unsigned long long *d_in, uint64_t n, double *d_out);
-}  // namespace obhip
-
 namespace {
 
 double key_to_double(uint64_t k) {

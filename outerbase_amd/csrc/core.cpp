@@ -45,6 +45,19 @@ int require_device() {
 hipStream_t cur_stream() { return g_stream; }
 void set_cur_stream(hipStream_t s) { g_stream = s; }
 
+int d2h(void *dst, const void *src, size_t bytes) {
+  OB_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, cur_stream()));
+  OB_HIP(hipStreamSynchronize(cur_stream()));
+  return 0;
+}
+
+int upload_cols(DevBuf<double> &d, const double *src, uint64_t rows, uint64_t cols, uint64_t ld) {
+  if (ld == rows) return d.upload(src, rows * cols);
+  std::vector<double> xc(rows * cols);
+  for (uint64_t j = 0; j < cols; ++j) std::memcpy(&xc[j * rows], src + j * ld, rows * sizeof(double));
+  return d.upload(xc.data(), xc.size());
+}
+
 // ---- device memory pool (see obhip_internal.h) ------------------------------------------
 namespace {
 struct PoolBlock {
@@ -687,10 +700,6 @@ int obhip_memcpy_d2d(void *d_dst, const void *d_src, uint64_t bytes) {
   return 0;
 }
 
-int obhip_memcpy_d2h(void *dst, const void *d_src, uint64_t bytes) {
-  OB_HIP(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, cur_stream()));
-  OB_HIP(hipStreamSynchronize(cur_stream()));
-  return 0;
-}
+int obhip_memcpy_d2h(void *dst, const void *d_src, uint64_t bytes) { return obhip::d2h(dst, d_src, bytes); }
 
 }  // extern "C"

@@ -11,14 +11,11 @@
 // All kernels stream HBM once, index with 64 bits (p = 16384: 1.34e8 triangle entries) and sum in
 // a fixed order: no atomics.
 #include "obhip_internal.h"
+#include "vec_ops.h"
 
 namespace obhip {
 
 namespace {
-
-__device__ __forceinline__ uint64_t tri_off(uint64_t i, uint64_t p) {
-  return i * p - i * (i - 1) / 2;  // start of row i (entries j >= i) in the packed triangle
-}
 
 // (c, mu, M2, n) of a state whose shift is moved to c_to
 struct Mom {
@@ -69,53 +66,6 @@ k_acc_shift_y(const double *__restrict__ Y, uint64_t ldy, uint64_t n, int q,
   const double c = j < q ? mom_batch[4 * j] : 0.0;
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256)
     Ys[(uint64_t)j * n + i] = j < q ? Y[(uint64_t)j * ldy + i] - c : 1.0;
-}
-
-// column sums of the shifted batch in the summation order of vsum (vec_ops.h): grid (blocks, q);
-// MODE 0: sum v, MODE 1: sum (v - mu)^2 with mu = mom_batch[4 j + 1]
-template <int MODE>
-__global__ void __launch_bounds__(256)
-k_acc_colsum1(const double *__restrict__ Ys, uint64_t n, const double *__restrict__ mom_batch,
-              double *__restrict__ part) {
-  __shared__ double red[256];
-  const int j = blockIdx.y;
-  const double *y = Ys + (uint64_t)j * n;
-  const double mu = MODE == 1 ? mom_batch[4 * j + 1] : 0.0;
-  double acc = 0.0;
-  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
-    if (MODE == 0) {
-      acc += y[i];
-    } else {
-      const double c = y[i] - mu;
-      acc = fma(c, c, acc);
-    }
-  }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int off = 128; off >= 1; off >>= 1) {
-    if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) part[(uint64_t)j * gridDim.x + blockIdx.x] = red[0];
-}
-
-// one wave per column; MODE 0: mu = sum / n and n; MODE 1: M2 = sum
-template <int MODE>
-__global__ void __launch_bounds__(64)
-k_acc_colsum2(const double *__restrict__ part, int nblk, double nrows, double *__restrict__ mom_batch) {
-  const int j = blockIdx.x;
-  double s = 0.0;
-  for (int b = threadIdx.x; b < nblk; b += 64) s += part[(uint64_t)j * nblk + b];
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-  if (threadIdx.x == 0) {
-    if (MODE == 0) {
-      mom_batch[4 * j + 1] = s / nrows;
-      mom_batch[4 * j + 3] = nrows;
-    } else {
-      mom_batch[4 * j + 2] = s;
-    }
-  }
 }
 
 // ---- folding one state into another ---------------------------------------------------------
@@ -169,46 +119,6 @@ k_acc_fold_mom(double *__restrict__ mom_dst, const double *__restrict__ mom_src,
 }
 
 // ---- the Newton step on a state (minus another) ------------------------------------------------
-// 64 x 64 tile (bi <= bj) of the packed triangle(s) -> H = e2 (T - T_minus) + diag(prec) in full
-// symmetric storage (lpdfvec::hess_, fit.cpp:503-512) and its diagonal: H[i][j] in 512-byte row
-// segments and, transposed through LDS, H[j][i] likewise
-__global__ void __launch_bounds__(256)
-k_acc_form(const double *__restrict__ tri, const double *__restrict__ tri_minus, uint64_t p, int nb,
-           double *__restrict__ H, double e2, const double *__restrict__ prec, double *__restrict__ diagH) {
-  __shared__ double S[64 * 65];
-  int bi = 0, rem = blockIdx.x;
-  while (rem >= nb - bi) {
-    rem -= nb - bi;
-    ++bi;
-  }
-  const int bj = bi + rem;
-  const int c = threadIdx.x & 63, r4 = threadIdx.x >> 6;
-  const uint64_t j = (uint64_t)bj * 64 + c;
-  for (int r = r4; r < 64; r += 4) {
-    const uint64_t i = (uint64_t)bi * 64 + r;
-    double v = 0.0;
-    if (i < p && j < p && j >= i) {
-      const uint64_t o = tri_off(i, p) + (j - i);
-      v = tri[o];
-      if (tri_minus) v -= tri_minus[o];
-      v *= e2;
-      if (i == j) {
-        v += prec[i];
-        if (diagH) diagH[i] = v;
-      }
-      H[i * p + j] = v;
-    }
-    S[r * 65 + c] = v;
-  }
-  __syncthreads();
-  // mirror: row jj = 64 bj + r, column ii = 64 bi + c holds S[c][r]; strictly below the diagonal only
-  const uint64_t ii = (uint64_t)bi * 64 + c;
-  for (int r = r4; r < 64; r += 4) {
-    const uint64_t jj = (uint64_t)bj * 64 + r;
-    if (jj < p && ii < p && ii < jj) H[jj * p + ii] = S[c * 65 + r];
-  }
-}
-
 // moments of the rows that remain and the right-hand sides of their standardised problem,
 // e2 B^T ((y_j - cent_j) / sd_j) = e2 ((R - mu b1) - (R' - (mu + c - c') b1')) / sd_j with the
 // primed quantities of the state taken out; meansd: q triples (cent, sd with n - 1 denominator, n).
@@ -239,68 +149,32 @@ k_acc_rhs(const double *__restrict__ rb, const double *__restrict__ mom, const d
   }
 }
 
-// ---- held-out score ------------------------------------------------------------------------------
-// per response the sum over the rows of (cent + sd mean - y)^2 (meansd null: mean is in raw units
-// already), in the summation order of vsum
-__global__ void __launch_bounds__(256)
-k_cv_score1(const double *__restrict__ mean, const double *__restrict__ Y, uint64_t n, uint64_t ld,
-            const double *__restrict__ meansd, double *__restrict__ part) {
-  __shared__ double red[256];
-  const int j = blockIdx.y;
-  const double cent = meansd ? meansd[3 * j] : 0.0, sd = meansd ? meansd[3 * j + 1] : 1.0;
-  const double *m = mean + (uint64_t)j * ld, *y = Y + (uint64_t)j * ld;
-  double acc = 0.0;
-  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
-    const double r = fma(sd, m[i], cent) - y[i];
-    acc = fma(r, r, acc);
-  }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int off = 128; off >= 1; off >>= 1) {
-    if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) part[(uint64_t)j * gridDim.x + blockIdx.x] = red[0];
-}
-
-__global__ void __launch_bounds__(64)
-k_cv_score2(const double *__restrict__ part, int nblk, double nrows, double *__restrict__ out) {
-  const int j = blockIdx.x;
-  double s = 0.0;
-  for (int b = threadIdx.x; b < nblk; b += 64) s += part[(uint64_t)j * nblk + b];
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-  if (threadIdx.x == 0) {
-    out[2 * j] = s;
-    out[2 * j + 1] = nrows;
-  }
-}
-
-int sum_blocks(uint64_t n) { return (int)std::min<uint64_t>(512, std::max<uint64_t>(1, (n + 255) / 256)); }
-
 }  // namespace
 
 // d_mom_batch[4 j] = shift, d_Ys (n x (q + 1)) = [Y - shift | 1], then (mu, M2, n) of the shifted
-// batch by two passes; d_part: 512 q doubles
+// batch by two passes of vcolsum; d_part: kSumBlocks q doubles
 int launch_acc_batch_moments(const double *d_Y, uint64_t ldy, uint64_t n, uint64_t q, bool empty,
                              const double *d_mom_state, double *d_mom_batch, double *d_Ys, double *d_part) {
   hipStream_t st = cur_stream();
-  const int nblk = sum_blocks(n);
   const unsigned qb = (unsigned)((q + 255) / 256);
   hipLaunchKernelGGL(k_acc_pick_shift, dim3(qb), dim3(256), 0, st, d_Y, ldy, (int)q, empty ? 1 : 0, d_mom_state,
                      d_mom_batch);
-  hipLaunchKernelGGL(k_acc_shift_y, dim3(nblk, (unsigned)q + 1), dim3(256), 0, st, d_Y, ldy, n, (int)q,
+  hipLaunchKernelGGL(k_acc_shift_y, dim3(sum_blocks(n), (unsigned)q + 1), dim3(256), 0, st, d_Y, ldy, n, (int)q,
                      (const double *)d_mom_batch, d_Ys);
-  hipLaunchKernelGGL(k_acc_colsum1<0>, dim3(nblk, (unsigned)q), dim3(256), 0, st, (const double *)d_Ys, n,
-                     (const double *)d_mom_batch, d_part);
-  hipLaunchKernelGGL(k_acc_colsum2<0>, dim3((unsigned)q), dim3(64), 0, st, (const double *)d_part, nblk, (double)n,
-                     d_mom_batch);
-  hipLaunchKernelGGL(k_acc_colsum1<1>, dim3(nblk, (unsigned)q), dim3(256), 0, st, (const double *)d_Ys, n,
-                     (const double *)d_mom_batch, d_part);
-  hipLaunchKernelGGL(k_acc_colsum2<1>, dim3((unsigned)q), dim3(64), 0, st, (const double *)d_part, nblk, (double)n,
-                     d_mom_batch);
   OB_HIP(hipGetLastError());
-  return 0;
+  const double *ys = d_Ys;
+  double *mom = d_mom_batch;
+  const double nrows = (double)n;
+  OB_TRY(vcolsum(n, q, [=] __device__(int j, uint64_t i, double &acc) { acc += ys[(uint64_t)j * n + i]; },
+                 [=] __device__(int j, double s) {
+                   mom[4 * j + 1] = s / nrows;
+                   mom[4 * j + 3] = nrows;
+                 },
+                 d_part));
+  return vcolsum(n, q, [=] __device__(int j, uint64_t i, double &acc) {
+    const double c = ys[(uint64_t)j * n + i] - mom[4 * j + 1];
+    acc = fma(c, c, acc);
+  }, [=] __device__(int j, double s) { mom[4 * j + 2] = s; }, d_part);
 }
 
 // dst +/- src, both in the accumulator's layout
@@ -318,16 +192,6 @@ int launch_acc_fold(uint64_t p, uint64_t q, double *d_dst, const double *d_src, 
   return 0;
 }
 
-int launch_acc_form(uint64_t p, const double *d_tri, const double *d_tri_minus, double *d_H, double e2,
-                    const double *d_prec, double *d_diagH) {
-  ProfScope ps("acc_form");
-  const int nb = (int)((p + 63) / 64);
-  hipLaunchKernelGGL(k_acc_form, dim3((unsigned)(nb * (nb + 1) / 2)), dim3(256), 0, cur_stream(), d_tri, d_tri_minus, p,
-                     nb, d_H, e2, d_prec, d_diagH);
-  OB_HIP(hipGetLastError());
-  return 0;
-}
-
 // d_state / d_minus (may be null): whole accumulator buffers
 int launch_acc_rhs(uint64_t p, uint64_t q, const double *d_state, const double *d_minus, double e2, double *d_rhs,
                    double *d_meansd) {
@@ -339,15 +203,19 @@ int launch_acc_rhs(uint64_t p, uint64_t q, const double *d_state, const double *
   return 0;
 }
 
-// d_part: 512 q doubles
+// per response the sum over the rows of (cent + sd mean - y)^2 (meansd null: mean is in raw units
+// already) and the row count, in the summation order of vsum; d_part: kSumBlocks q doubles
 int launch_cv_score(const double *d_mean, const double *d_Y, uint64_t n, uint64_t q, uint64_t ld,
                     const double *d_meansd, double *d_out, double *d_part) {
-  const int nblk = sum_blocks(n);
-  hipStream_t st = cur_stream();
-  hipLaunchKernelGGL(k_cv_score1, dim3(nblk, (unsigned)q), dim3(256), 0, st, d_mean, d_Y, n, ld, d_meansd, d_part);
-  hipLaunchKernelGGL(k_cv_score2, dim3((unsigned)q), dim3(64), 0, st, (const double *)d_part, nblk, (double)n, d_out);
-  OB_HIP(hipGetLastError());
-  return 0;
+  const double nrows = (double)n;
+  return vcolsum(n, q, [=] __device__(int j, uint64_t i, double &acc) {
+    const double cent = d_meansd ? d_meansd[3 * j] : 0.0, sd = d_meansd ? d_meansd[3 * j + 1] : 1.0;
+    const double r = fma(sd, d_mean[(uint64_t)j * ld + i], cent) - d_Y[(uint64_t)j * ld + i];
+    acc = fma(r, r, acc);
+  }, [=] __device__(int j, double s) {
+    d_out[2 * j] = s;
+    d_out[2 * j + 1] = nrows;
+  }, d_part);
 }
 
 }  // namespace obhip

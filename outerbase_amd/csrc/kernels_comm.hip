@@ -12,10 +12,6 @@ namespace obhip {
 
 namespace {
 
-__device__ __forceinline__ uint64_t tri_off(uint64_t i, uint64_t p) {
-  return i * p - i * (i - 1) / 2;  // start of row i (entries j >= i) in the packed triangle
-}
-
 // one block per row i: G[i][i..p) -> buf[tri_off(i) ...]
 __global__ void __launch_bounds__(256)
 k_pack_tri(const double *__restrict__ G, uint64_t p, double *__restrict__ buf) {
@@ -39,10 +35,14 @@ k_pack_tail(const double *__restrict__ g, const double *__restrict__ b1,
   }
 }
 
-// 64 x 64 tile (bi <= bj) of the packed triangle -> G[i][j] and, transposed through LDS,
-// G[j][i]; both written in 512-byte row segments
+// 64 x 64 tile (bi <= bj) of the packed triangle(s) -> full symmetric storage: M[i][j] in 512-byte
+// row segments and, transposed through LDS, M[j][i] likewise.  MINUS: T - T_minus (a streaming fit
+// with a held-out state).  FORM: the Hessian H = e2 T + diag(prec) (lpdfvec::hess_, fit.cpp:503-512)
+// and its diagonal, in the one pass that has to touch the p x p matrix anyway.
+template <bool FORM, bool MINUS>
 __global__ void __launch_bounds__(256)
-k_unpack_tri(const double *__restrict__ buf, uint64_t p, int nb, double *__restrict__ G) {
+k_unpack_tri(const double *__restrict__ tri, const double *__restrict__ tri_minus, uint64_t p, int nb,
+             double *__restrict__ H, double e2, const double *__restrict__ prec, double *__restrict__ diagH) {
   __shared__ double S[64 * 65];
   int bi = 0, rem = blockIdx.x;
   while (rem >= nb - bi) {
@@ -56,50 +56,23 @@ k_unpack_tri(const double *__restrict__ buf, uint64_t p, int nb, double *__restr
     const uint64_t i = (uint64_t)bi * 64 + r;
     double v = 0.0;
     if (i < p && j < p && j >= i) {
-      v = buf[tri_off(i, p) + (j - i)];
-      G[i * p + j] = v;
-    }
-    S[r * 65 + c] = v;
-  }
-  __syncthreads();
-  // mirror: row jj = 64 bj + r, column ii = 64 bi + c holds S[c][r]; strictly below the
-  // diagonal only
-  const uint64_t ii = (uint64_t)bi * 64 + c;
-  for (int r = r4; r < 64; r += 4) {
-    const uint64_t jj = (uint64_t)bj * 64 + r;
-    if (jj < p && ii < p && ii < jj) G[jj * p + ii] = S[c * 65 + r];
-  }
-}
-
-// The unpack of a row-sharded Newton fit: the summed packed triangle becomes the Hessian
-// H = e2 G + diag(prec) in full symmetric storage (lpdfvec::hess_, fit.cpp:503-512) and its
-// diagonal, in the one pass that has to touch the p x p matrix anyway.
-__global__ void __launch_bounds__(256)
-k_unpack_form(const double *__restrict__ buf, uint64_t p, int nb, double *__restrict__ H, double e2,
-              const double *__restrict__ prec, double *__restrict__ diagH) {
-  __shared__ double S[64 * 65];
-  int bi = 0, rem = blockIdx.x;
-  while (rem >= nb - bi) {
-    rem -= nb - bi;
-    ++bi;
-  }
-  const int bj = bi + rem;
-  const int c = threadIdx.x & 63, r4 = threadIdx.x >> 6;
-  const uint64_t j = (uint64_t)bj * 64 + c;
-  for (int r = r4; r < 64; r += 4) {
-    const uint64_t i = (uint64_t)bi * 64 + r;
-    double v = 0.0;
-    if (i < p && j < p && j >= i) {
-      v = e2 * buf[tri_off(i, p) + (j - i)];
-      if (i == j) {
-        v += prec[i];
-        if (diagH) diagH[i] = v;
+      const uint64_t o = tri_off(i, p) + (j - i);
+      v = tri[o];
+      if (MINUS) v -= tri_minus[o];
+      if (FORM) {
+        v *= e2;
+        if (i == j) {
+          v += prec[i];
+          if (diagH) diagH[i] = v;
+        }
       }
       H[i * p + j] = v;
     }
     S[r * 65 + c] = v;
   }
   __syncthreads();
+  // mirror: row jj = 64 bj + r, column ii = 64 bi + c holds S[c][r]; strictly below the
+  // diagonal only
   const uint64_t ii = (uint64_t)bi * 64 + c;
   for (int r = r4; r < 64; r += 4) {
     const uint64_t jj = (uint64_t)bj * 64 + r;
@@ -147,23 +120,20 @@ int launch_unpack_normal_eq(uint64_t p, bool with_tri, const double *d_buf, doub
                             double *d_meansd) {
   const uint64_t tri = p * (p + 1) / 2;
   hipStream_t st = cur_stream();
-  if (with_tri) {
-    const int nb = (int)((p + 63) / 64);
-    hipLaunchKernelGGL(k_unpack_tri, dim3((unsigned)(nb * (nb + 1) / 2)), dim3(256), 0, st, d_buf, p,
-                       nb, d_G);
-  }
+  if (with_tri) OB_TRY(launch_unpack_tri(p, d_buf, nullptr, d_G, false));
   hipLaunchKernelGGL(k_finalize_rhs, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, st, d_buf + tri,
                      p, d_g, d_meansd);
   OB_HIP(hipGetLastError());
   return 0;
 }
 
-int launch_unpack_form(uint64_t p, const double *d_tri, double *d_H, double e2, const double *d_prec,
-                       double *d_diagH) {
-  ProfScope ps("unpack_form");
+int launch_unpack_tri(uint64_t p, const double *d_tri, const double *d_tri_minus, double *d_H, bool form, double e2,
+                      const double *d_prec, double *d_diagH) {
   const int nb = (int)((p + 63) / 64);
-  hipLaunchKernelGGL(k_unpack_form, dim3((unsigned)(nb * (nb + 1) / 2)), dim3(256), 0, cur_stream(),
-                     d_tri, p, nb, d_H, e2, d_prec, d_diagH);
+  auto k = form ? (d_tri_minus ? k_unpack_tri<true, true> : k_unpack_tri<true, false>)
+                : (d_tri_minus ? k_unpack_tri<false, true> : k_unpack_tri<false, false>);
+  hipLaunchKernelGGL(k, dim3((unsigned)(nb * (nb + 1) / 2)), dim3(256), 0, cur_stream(), d_tri, d_tri_minus, p, nb,
+                     d_H, e2, d_prec, d_diagH);
   OB_HIP(hipGetLastError());
   return 0;
 }

@@ -1614,12 +1614,6 @@ using namespace obhip;
 
 namespace {
 
-int d2h(void *dst, const void *src, size_t bytes) {
-  OB_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, cur_stream()));
-  OB_HIP(hipStreamSynchronize(cur_stream()));
-  return 0;
-}
-
 int check_grad_args(const obhip_basis *b, const obhip_terms *t) {
   if (!b || !t) return fail(OBHIP_ERR_INVALID, "gradhyp: null argument");
   if (t->d != b->model->d) return fail(OBHIP_ERR_INVALID, "terms and model disagree on d");

@@ -1,4 +1,4 @@
-// Kernels of the multi-response Newton fit and predictor (fit_multi.cpp): q responses over one
+// Kernels of the multi-response Newton fit and predictor (fit_newton.cpp): q responses over one
 // design x share the Gram, the Hessian and its Cholesky factor; what depends on Y is batched
 // over the responses in column blocks of 16, the n of v_mfma_f64_16x16x4_f64.
 //

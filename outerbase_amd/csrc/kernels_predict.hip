@@ -343,10 +343,6 @@ int dispatch_predict(const obhip_model &m, obhip_terms &t, const double *d_theta
 
 }  // namespace
 
-bool star_predict_supports(const obhip_terms &t);
-int launch_star_predict(const obhip_model &m, obhip_terms &t, const double *d_theta, const double *d_x, uint64_t n,
-                        double *d_mean, const double *d_coeffvar, double e2sigma, double *d_var);
-
 int launch_predict(const obhip_model &m, obhip_terms &t, const double *d_theta, const double *d_x,
                    uint64_t n, double *d_mean, const double *d_coeffvar, double e2sigma,
                    double *d_var) {

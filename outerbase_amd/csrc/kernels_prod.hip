@@ -1137,16 +1137,6 @@ int dispatch_mm_tl(const obhip_basis &b, obhip_terms &t, const double *d_a, doub
 #undef OB_ML
 }
 
-// kernels_star.hip: the kernels on shared sub-products (stars of four terms), from 9 star-waves up
-bool star_supports(const obhip_terms &t, bool one_block, bool dual = false);
-int launch_star_hess(const obhip_basis &b, obhip_terms &t, const double *d_a, const double *d_y, double ca,
-                     double cb, double *part, double *d_yhat, double *sspart, unsigned nsplit, uint64_t ntiles,
-                     uint64_t tps, const double *stop0, const double *stop1);
-int launch_star_tmm(const obhip_basis &b, obhip_terms &t, const double *d_a, bool squared, double *part,
-                    const double *d_a2, double *part2, unsigned nsplit, uint64_t ntiles, uint64_t tps);
-int launch_star_mm(const obhip_basis &b, obhip_terms &t, const double *d_a, bool squared, double *d_out,
-                   double *mpart, unsigned nsplit, uint64_t ntiles, uint64_t tps);
-
 namespace {
 bool hm3_wanted() {
   static const bool off = getenv("OBHIP_HM3") && atoi(getenv("OBHIP_HM3")) == 0;
@@ -1516,13 +1506,6 @@ int run_hm_tl(const obhip_basis &b, obhip_terms &t, const double *d_a, const dou
   if (ro) return run_hm_tl2<W2, NU, false, true>(b, t, d_a, d_y, ca, cb, part, d_yhat, sspart, nsplit, ntiles, tps, lds);
   return run_hm_tl2<W2, NU, false, false>(b, t, d_a, d_y, ca, cb, part, d_yhat, sspart, nsplit, ntiles, tps, lds);
 }
-
-// kernels_hm.hip: the second-generation kernel (two tile buffers fed by LDS-direct loads, four
-// waves per SIMD) and the terms it takes
-bool hm2_supports(const obhip_terms &t, bool ro, int variant);
-int launch_hm2(const obhip_basis &b, obhip_terms &t, const double *d_a, const double *d_y, double ca,
-               double cb, double *part, double *d_yhat, double *sspart, unsigned nsplit, uint64_t ntiles,
-               uint64_t tps, int variant, const double *stop0, const double *stop1);
 
 namespace {
 bool hm2_wanted() {

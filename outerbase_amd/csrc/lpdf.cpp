@@ -19,18 +19,7 @@
 
 using namespace obhip;
 
-namespace obhip {
-int launch_colnorm2(const double *d_Z, uint64_t ld, uint64_t p, uint64_t n, double add,
-                    double *d_out);
-}
-
 namespace {
-
-int d2h(void *dst, const void *src, size_t bytes) {
-  OB_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, cur_stream()));
-  OB_HIP(hipStreamSynchronize(cur_stream()));
-  return 0;
-}
 
 int h2d(void *dst, const void *src, size_t bytes) {  // src may be a temporary: synchronous
   OB_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, cur_stream()));
@@ -1493,13 +1482,7 @@ int obhip_predictor_setnthreads(obhip_predictor *p, int) {
 int obhip_predictor_update(obhip_predictor *p, const double *x, uint64_t n, uint64_t ldx) {
   if (!p || !x || n == 0 || ldx < n) return fail(OBHIP_ERR_INVALID, "predictor_update: bad argument");
   const uint64_t d = p->om->d;
-  if (ldx == n) {
-    OB_TRY(p->x.upload(x, n * d));
-  } else {
-    std::vector<double> xc(n * d);
-    for (uint64_t l = 0; l < d; ++l) std::memcpy(&xc[l * n], x + l * ldx, n * sizeof(double));
-    OB_TRY(p->x.upload(xc.data(), xc.size()));
-  }
+  OB_TRY(upload_cols(p->x, x, n, d, ldx));
   p->n = n;
   p->fresh = false;
   return 0;

@@ -4,8 +4,8 @@
 // B^T 1 and per response (c, mean - c, M2, n), one device buffer laid out as kernels_acc.hip says --
 // so that rows are passed over once, ever:
 //   add / remove   the batch's Gram goes through launch_gram_to with a packed sink into scratch,
-//                  B^T [Y - c | 1] as fit_multi.cpp forms B^T Y (column 0 with the staging pass, the
-//                  others by k_aty_multi or a column loop), then one fold with the sign;
+//                  B^T [Y - c | 1] as fit_newton.cpp forms B^T Y (column 0 with the staging pass, the
+//                  others by bty_columns), then one fold with the sign;
 //   combine        the same fold of one accumulator into another;
 //   solve          H = e^{-2 sigma} (T - T_minus) + diag(prec) unpacked from the triangle(s), the
 //                  moments of the remaining rows and the right-hand sides standardised AFTER the sum,
@@ -23,21 +23,6 @@
 #include "vec_ops.h"
 
 using namespace obhip;
-
-namespace obhip {
-std::vector<double> prior_prec_of(const obhip_model &m, const obhip_terms &t, double rho);
-int check_compat_of(const obhip_model *m, const obhip_terms *t);
-// kernels_acc.hip
-int launch_acc_batch_moments(const double *d_Y, uint64_t ldy, uint64_t n, uint64_t q, bool empty,
-                             const double *d_mom_state, double *d_mom_batch, double *d_Ys, double *d_part);
-int launch_acc_fold(uint64_t p, uint64_t q, double *d_dst, const double *d_src, bool dst_empty, double sign);
-int launch_acc_form(uint64_t p, const double *d_tri, const double *d_tri_minus, double *d_H, double e2,
-                    const double *d_prec, double *d_diagH);
-int launch_acc_rhs(uint64_t p, uint64_t q, const double *d_state, const double *d_minus, double e2, double *d_rhs,
-                   double *d_meansd);
-int launch_cv_score(const double *d_mean, const double *d_Y, uint64_t n, uint64_t q, uint64_t ld,
-                    const double *d_meansd, double *d_out, double *d_part);
-}  // namespace obhip
 
 struct obhip_normal_acc {
   const obhip_model *model = nullptr;
@@ -86,7 +71,7 @@ int obhip_normal_acc_bytes(uint64_t p, uint64_t q, uint64_t *bytes) {
 
 int obhip_normal_acc_create(obhip_normal_acc **out, const obhip_model *m, const obhip_terms *t, uint64_t q) {
   if (!out || !m || !t || q == 0 || q > kMaxResponses) return fail(OBHIP_ERR_INVALID, "normal_acc_create: bad argument");
-  OB_TRY(check_compat_of(m, t));
+  OB_TRY(check_compat(m, t));
   OB_TRY(require_device());
   obhip_normal_acc *a = new (std::nothrow) obhip_normal_acc();
   if (!a) return fail(OBHIP_ERR_INVALID, "normal_acc_create: out of host memory");
@@ -138,7 +123,7 @@ int obhip_normal_acc_add_dev(obhip_normal_acc *acc, const obhip_basis *bc, const
   const uint64_t n = bc->n, p = acc->p, q = acc->q;
   if (n == 0) return 0;
   if (!d_Y_raw || ldy < n) return fail(OBHIP_ERR_INVALID, "normal_acc_add_dev: Y is null or ldy below the rows of the basis");
-  OB_TRY(check_compat_of(acc->model, acc->terms));
+  OB_TRY(check_compat(acc->model, acc->terms));
   OB_TRY(check_version(acc, "normal_acc_add_dev"));
   if (bc->md.model_version != acc->model->version)
     return fail(OBHIP_ERR_STATE, "normal_acc_add_dev: the basis was built before the model last changed");
@@ -152,7 +137,7 @@ int obhip_normal_acc_add_dev(obhip_normal_acc *acc, const obhip_basis *bc, const
   DevBuf<double> scratch, Ys, part;
   OB_TRY(scratch.alloc(state_count(p, q)));
   OB_TRY(Ys.alloc(n * (q + 1)));
-  OB_TRY(part.alloc(512 * q));
+  OB_TRY(part.alloc(kSumBlocks * q));
   const bool empty = acc->rows == 0;
   double *s_rb = scratch.p + tri, *s_mom = scratch.p + tri + nrb;
   OB_TRY(launch_acc_batch_moments(d_Y_raw, ldy, n, q, empty, acc->st.p + tri + nrb, s_mom, Ys.p, part.p));
@@ -166,11 +151,7 @@ int obhip_normal_acc_add_dev(obhip_normal_acc *acc, const obhip_basis *bc, const
   // column 0 as the single fit takes it: with the staging pass, or by its own pass over the basis
   if (!fuse.done) OB_TRY(launch_tmm(b, t, Ys.p, s_rb, false));
   // columns 1 .. q - 1 of Y - c, then the ones column: B^T 1
-  if (q >= kMultiMinCols && b.bmat.p && t.uid != 0 && b.bmat_terms == t.uid) {
-    OB_TRY(launch_aty_multi(b, t, Ys.p + n, n, q, s_rb + p, p));
-  } else {
-    for (uint64_t j = 1; j <= q; ++j) OB_TRY(launch_tmm(b, t, Ys.p + j * n, s_rb + j * p, false));
-  }
+  OB_TRY(bty_columns(b, t, Ys.p + n, n, q, s_rb + p));
   OB_TRY(launch_acc_fold(p, q, acc->st.p, scratch.p, empty, (double)sign));
   if (empty) acc->version = acc->model->version;
   if (sign > 0) {
@@ -219,7 +200,7 @@ int obhip_normal_acc_solve_dev(const obhip_normal_acc *acc, const obhip_normal_a
   if (minus && (minus->model != acc->model || !same_terms(minus->terms, acc->terms) || minus->p != acc->p || minus->q != acc->q))
     return fail(OBHIP_ERR_INVALID, "normal_acc_solve_dev: the accumulators differ in model, terms or responses");
   const obhip_model *m = acc->model;
-  OB_TRY(check_compat_of(m, acc->terms));
+  OB_TRY(check_compat(m, acc->terms));
   OB_TRY(check_version(acc, "normal_acc_solve_dev"));
   if (minus) OB_TRY(check_version(minus, "normal_acc_solve_dev"));
   if (minus && minus->rows > acc->rows)
@@ -235,25 +216,21 @@ int obhip_normal_acc_solve_dev(const obhip_normal_acc *acc, const obhip_normal_a
   if (workspace_bytes < need) return fail(OBHIP_ERR_INVALID, "normal_acc_solve_dev: workspace too small");
   OB_TRY(require_device());
   obhip_terms &t = *const_cast<obhip_terms *>(acc->terms);
-  if (!t.prec_dev.p || t.prec_model != m || t.prec_version != m->version || t.prec_rho != rho) {
-    const std::vector<double> prec = prior_prec_of(*m, t, rho);
-    OB_TRY(t.prec_dev.upload(prec.data(), p));  // (synchronises: prec is a local)
-    t.prec_model = m;
-    t.prec_version = m->version;
-    t.prec_rho = rho;
-  }
+  const double *d_prec = nullptr;
+  OB_TRY(terms_prec_dev(m, t, rho, &d_prec));
   const double e2 = std::exp(-2.0 * sigma);
   const double *d_minus = minus && minus->rows > 0 ? minus->st.p : nullptr;
   DevBuf<double> rhs;
   OB_TRY(rhs.alloc(p * q));
-  OB_TRY(launch_acc_form(p, acc->st.p, d_minus, d_H, e2, t.prec_dev.p, d_diagH));
+  {
+    ProfScope ps("acc_form");
+    OB_TRY(launch_unpack_tri(p, acc->st.p, d_minus, d_H, true, e2, d_prec, d_diagH));
+  }
   OB_TRY(launch_acc_rhs(p, q, acc->st.p, d_minus, e2, rhs.p, d_meansd));
   void *d_cholws = (double *)d_workspace + 2 * p;
   OB_TRY(launch_newton_solve(p, d_H, rhs.p, d_Theta, d_cholws, newton_workspace_bytes(p)));
-  if (q == 1) return 0;
   // the right-hand sides carry e^{-2 sigma} already
-  return launch_trsm_multi(p, d_H, newton_workspace_iinv(p, d_cholws), rhs.p + p, p, q - 1, 1.0, d_Theta + p,
-                           (char *)d_workspace + single);
+  return solve_columns(p, d_H, d_cholws, rhs.p + p, q - 1, 1.0, d_Theta + p, (char *)d_workspace + single);
 }
 
 int obhip_cv_score_dev(const double *d_mean, const double *d_Y_raw, uint64_t n, uint64_t q, uint64_t ld,
@@ -262,7 +239,7 @@ int obhip_cv_score_dev(const double *d_mean, const double *d_Y_raw, uint64_t n, 
     return fail(OBHIP_ERR_INVALID, "cv_score_dev: bad argument");
   OB_TRY(require_device());
   DevBuf<double> part;
-  OB_TRY(part.alloc(512 * q));
+  OB_TRY(part.alloc(kSumBlocks * q));
   return launch_cv_score(d_mean, d_Y_raw, n, q, ld, d_meansd, d_out, part.p);
 }
 

@@ -159,6 +159,11 @@ struct DevBuf {
   }
 };
 
+// dst (host) <- src (device), waited for
+int d2h(void *dst, const void *src, size_t bytes);
+// d <- the rows x cols column-major host matrix src with leading dimension ld, compacted to ld = rows
+int upload_cols(DevBuf<double> &d, const double *src, uint64_t rows, uint64_t cols, uint64_t ld);
+
 // ---- covariance functions (host) --------------------------------------------
 constexpr int kNumCov = 3;
 struct CovInfo {
@@ -450,6 +455,24 @@ int launch_mm_generic(const obhip_basis &b, obhip_terms &t, const double *d_a, d
 int launch_tmm_generic(const obhip_basis &b, obhip_terms &t, const double *d_a, double *d_out,
                        bool squared);
 int launch_materialize_generic(const obhip_basis &b, obhip_terms &t, double *d_B);
+// kernels_star.hip: the kernels on shared sub-products (stars of four terms), from 9 star-waves up
+bool star_supports(const obhip_terms &t, bool one_block, bool dual = false);
+int launch_star_hess(const obhip_basis &b, obhip_terms &t, const double *d_a, const double *d_y, double ca,
+                     double cb, double *part, double *d_yhat, double *sspart, unsigned nsplit, uint64_t ntiles,
+                     uint64_t tps, const double *stop0, const double *stop1);
+int launch_star_tmm(const obhip_basis &b, obhip_terms &t, const double *d_a, bool squared, double *part,
+                    const double *d_a2, double *part2, unsigned nsplit, uint64_t ntiles, uint64_t tps);
+int launch_star_mm(const obhip_basis &b, obhip_terms &t, const double *d_a, bool squared, double *d_out,
+                   double *mpart, unsigned nsplit, uint64_t ntiles, uint64_t tps);
+bool star_predict_supports(const obhip_terms &t);
+int launch_star_predict(const obhip_model &m, obhip_terms &t, const double *d_theta, const double *d_x, uint64_t n,
+                        double *d_mean, const double *d_coeffvar, double e2sigma, double *d_var);
+// kernels_hm.hip: the second-generation kernel (two tile buffers fed by LDS-direct loads, four
+// waves per SIMD) and the terms it takes
+bool hm2_supports(const obhip_terms &t, bool ro, int variant);
+int launch_hm2(const obhip_basis &b, obhip_terms &t, const double *d_a, const double *d_y, double ca,
+               double cb, double *part, double *d_yhat, double *sspart, unsigned nsplit, uint64_t ntiles,
+               uint64_t tps, int variant, const double *stop0, const double *stop1);
 // kernels_gram.hip
 // where k_gram_reduce puts the summed tiles: full symmetric p x p (raw G, or with `form` the
 // Hessian e2 G + diag(prec) and its diagonal) or the packed upper triangle of a row-sharded
@@ -527,7 +550,7 @@ int launch_newton_solve(uint64_t p, double *d_H, const double *d_rhs,
 int launch_form_hessian(uint64_t p, double *d_G, const double *d_prec,
                         double e2, double *d_diagH);
 const double *newton_workspace_iinv(uint64_t p, const void *d_ws);
-// kernels_multi.hip: the batched passes of the multi-response fit and predictor (fit_multi.cpp)
+// kernels_multi.hip: the batched passes of the multi-response fit and predictor (fit_newton.cpp)
 uint64_t multi_solve_scratch_bytes(uint64_t p);
 // Fewest columns worth a batched pass of B^T Y or the predictor: one pass costs the same for 1 to 16
 // columns (d=20, n=1e6, p=4096: 5.6 ms and 9.1 ms) where the single-column kernels take 0.77 ms and
@@ -551,7 +574,22 @@ int ensure_dx_tables(const obhip_model &m, obhip_terms &t);  // after t.prepare(
 int launch_predict_dx(const obhip_model &m, obhip_terms &t, const double *d_theta, const double *d_x, uint64_t n,
                       double *d_mean, double *d_grad, const double *d_coeffvar, double e2sigma, double *d_var,
                       double *d_gradvar);
+// kernels_acc.hip: the streaming fit's batch moments, folds and right-hand sides (normal_acc.cpp)
+int launch_acc_batch_moments(const double *d_Y, uint64_t ldy, uint64_t n, uint64_t q, bool empty,
+                             const double *d_mom_state, double *d_mom_batch, double *d_Ys, double *d_part);
+int launch_acc_fold(uint64_t p, uint64_t q, double *d_dst, const double *d_src, bool dst_empty, double sign);
+int launch_acc_rhs(uint64_t p, uint64_t q, const double *d_state, const double *d_minus, double e2, double *d_rhs,
+                   double *d_meansd);
+int launch_cv_score(const double *d_mean, const double *d_Y, uint64_t n, uint64_t q, uint64_t ld,
+                    const double *d_meansd, double *d_out, double *d_part);
 // small vector kernels (kernels_misc.hip)
+int launch_colnorm2(const double *d_Z, uint64_t ld, uint64_t p, uint64_t n, double add, double *d_out);
+int launch_dot_cols(const double *d_A, const double *d_B, uint64_t ld, uint64_t p, uint64_t n, double *d_out,
+                    double *d_part);
+int quantile_max_targets();
+int launch_count_le(const double *d_x, uint64_t n, uint64_t d, const uint64_t *d_mids, int T,
+                    unsigned long long *d_counts);
+int launch_u64_to_f64(const unsigned long long *d_in, uint64_t n, double *d_out);
 int launch_synth(uint64_t seed, uint64_t row0, uint64_t n, uint64_t d,
                  const int *d_kinds, double *d_x, double *d_y);
 int launch_sum_sumsq(const double *d_v, uint64_t n, double *d_out2,
@@ -561,6 +599,31 @@ int launch_resid(const double *d_yhat, const double *d_y, uint64_t n, double e2,
                  double *d_r, double *d_diff);
 int launch_scale(double *d_v, uint64_t n, double c);
 int launch_fill(double *d_v, uint64_t n, double c);
+// kernels_comm.hip: the one-buffer exchange of the normal equations, and the packed upper triangle
+// (row-major, row i from its diagonal on) in which a sharded fit exchanges G and a streaming fit keeps it
+__host__ __device__ inline uint64_t tri_off(uint64_t i, uint64_t p) {
+  return i * p - i * (i - 1) / 2;  // start of row i (entries j >= i)
+}
+uint64_t normal_eq_tail(uint64_t p);
+int launch_pack_normal_eq(uint64_t p, bool with_tri, const double *d_G, const double *d_g, const double *d_b1,
+                          const double *d_sum2, double nlocal, double *d_buf, uint64_t count);
+int launch_unpack_normal_eq(uint64_t p, bool with_tri, const double *d_buf, double *d_G, double *d_g,
+                            double *d_meansd);
+// d_H (full symmetric p x p) = the packed triangle d_tri minus d_tri_minus (may be null); with `form`
+// the Hessian e2 (T - T_minus) + diag(prec) and its diagonal (d_diagH may be null)
+int launch_unpack_tri(uint64_t p, const double *d_tri, const double *d_tri_minus, double *d_H, bool form,
+                      double e2 = 1.0, const double *d_prec = nullptr, double *d_diagH = nullptr);
+// api.cpp: logpr_gauss::diaghess of the terms; model and terms belong together
+std::vector<double> prior_prec(const obhip_model &m, const obhip_terms &t, double rho);
+int check_compat(const obhip_model *m, const obhip_terms *t);
+// fit_newton.cpp: the pieces of the one Newton-fit pipeline that the streaming fit uses as well.
+// *d_prec = the prior precisions of t on the device, uploaded when the model state or rho changed
+int terms_prec_dev(const obhip_model *m, obhip_terms &t, double rho, const double **d_prec);
+// d_out (p x ncols, ld = p) = B^T Y for the columns that do not ride along with the Gram
+int bty_columns(obhip_basis &b, obhip_terms &t, const double *d_Y, uint64_t ldy, uint64_t ncols, double *d_out);
+// d_Theta (p x ncols) = inv(H) e2 R on the factor launch_newton_solve has just left in d_H
+int solve_columns(uint64_t p, const double *d_H, const void *d_cholws, const double *d_R, uint64_t ncols, double e2,
+                  double *d_Theta, void *d_scratch);
 // comm.cpp: in-place sum over the ranks of c (no-op for c == nullptr or one rank)
 int comm_allreduce(obhip_comm *c, double *d_buf, uint64_t count);
 int comm_nranks(const obhip_comm *c);

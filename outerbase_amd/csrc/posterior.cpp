@@ -22,9 +22,6 @@
 using namespace obhip;
 
 namespace obhip {
-int launch_dot_cols(const double *d_A, const double *d_B, uint64_t ld, uint64_t p, uint64_t n,
-                    double *d_out, double *d_part);
-
 static uint64_t pad128(uint64_t v) { return (v + 127) / 128 * 128; }
 
 // f.L = Cholesky factor of H (lower triangle, row-major p x p), f.X = L^-T (pp x pp)
@@ -113,18 +110,10 @@ extern "C" int obhip_predict_std(const obhip_model *m, const obhip_terms *tc, co
   OB_TRY(dH.upload(H, p * p));
   PostFactor f;
   OB_TRY(post_factor_build(dH.p, p, f, true));
-  if (ldx == n) {
-    OB_TRY(dx.upload(x, n * m->d));
-  } else {
-    std::vector<double> xc(n * m->d);
-    for (uint64_t l = 0; l < m->d; ++l) std::memcpy(&xc[l * n], x + l * ldx, n * sizeof(double));
-    OB_TRY(dx.upload(xc.data(), xc.size()));
-  }
+  OB_TRY(upload_cols(dx, x, n, m->d, ldx));
   OB_TRY(dvar.alloc(n));
   OB_TRY(post_var_dev(*m, t, f, dx.p, n, std::exp(2.0 * sigma), dvar.p));
-  OB_HIP(hipMemcpyAsync(var, dvar.p, n * sizeof(double), hipMemcpyDeviceToHost, cur_stream()));
-  OB_HIP(hipStreamSynchronize(cur_stream()));
-  return 0;
+  return d2h(var, dvar.p, n * sizeof(double));
 }
 
 // Marginal adjustment of lpdfvec(loglik_std, logpr_gauss) with the full Hessian

@@ -14,7 +14,6 @@
 using namespace obhip;
 
 namespace obhip {
-int check_compat_of(const obhip_model *m, const obhip_terms *t);
 
 // rows one call takes: the view offsets and tile counts of the kernel are 64-bit, the bound keeps
 // n * d * 8 bytes far inside the address space
@@ -139,14 +138,6 @@ int ensure_dx_tables(const obhip_model &m, obhip_terms &t) {
 
 }  // namespace obhip
 
-namespace {
-int d2h(void *dst, const void *src, size_t bytes) {
-  OB_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, cur_stream()));
-  OB_HIP(hipStreamSynchronize(cur_stream()));
-  return 0;
-}
-}  // namespace
-
 extern "C" {
 
 int obhip_predict_grad_dev(const obhip_model *m, const obhip_terms *t, const double *d_theta, const double *d_x,
@@ -156,7 +147,7 @@ int obhip_predict_grad_dev(const obhip_model *m, const obhip_terms *t, const dou
     return fail(OBHIP_ERR_INVALID, "predict_grad_dev: null model, terms, theta, x or grad");
   if (d_gradvar && !d_coeffvar) return fail(OBHIP_ERR_INVALID, "predict_grad_dev: gradvar needs coeffvar");
   if (n > kDxMaxRows) return fail(OBHIP_ERR_INVALID, "predict_grad_dev: more than 2^40 rows in one call");
-  OB_TRY(check_compat_of(m, t));
+  OB_TRY(check_compat(m, t));
   if (n == 0) return 0;
   OB_TRY(require_device());
   return launch_predict_dx(*m, *const_cast<obhip_terms *>(t), d_theta, d_x, n, d_mean, d_grad, d_coeffvar,
@@ -171,18 +162,12 @@ int obhip_predict_grad(const obhip_model *m, const obhip_terms *t, const double 
   if (gradvar && !coeffvar) return fail(OBHIP_ERR_INVALID, "predict_grad: gradvar needs coeffvar");
   if (n > kDxMaxRows) return fail(OBHIP_ERR_INVALID, "predict_grad: more than 2^40 rows in one call");
   if (ldx < n || ldg < n) return fail(OBHIP_ERR_INVALID, "predict_grad: leading dimension below n");
-  OB_TRY(check_compat_of(m, t));
+  OB_TRY(check_compat(m, t));
   if (n == 0) return 0;
   OB_TRY(require_device());
   const uint64_t d = m->d;
   DevBuf<double> dx, dth, dmean, dgrad, dcv, dvar, dgv;
-  if (ldx == n) {
-    OB_TRY(dx.upload(x, n * d));
-  } else {
-    std::vector<double> xc(n * d);
-    for (uint64_t l = 0; l < d; ++l) std::memcpy(&xc[l * n], x + l * ldx, n * sizeof(double));
-    OB_TRY(dx.upload(xc.data(), xc.size()));
-  }
+  OB_TRY(upload_cols(dx, x, n, d, ldx));
   OB_TRY(dth.upload(theta, t->p));
   if (mean) OB_TRY(dmean.alloc(n));
   OB_TRY(dgrad.alloc(n * d));

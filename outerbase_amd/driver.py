@@ -256,9 +256,10 @@ class HotPath:
         # loglik_std.cpp:51: para0 = log(0.01 * var(y)); var of the standardised y is 1
         self.sigma = math.log(0.01)
 
-    def fit(self):
-        torch = self.torch
-        call("obhip_set_stream", C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    def prepare_fit(self):
+        """the basis of this rank's rows on the current stream (built once, then rebuilt in place)
+        and the standardised targets"""
+        call("obhip_set_stream", C.c_void_p(self.torch.cuda.current_stream().cuda_stream))
         if self.basis is None:
             h = C.c_void_p()
             call("obhip_basis_create_dev", C.byref(h), self.om._h, self.x.data_ptr(), self.n,
@@ -267,6 +268,9 @@ class HotPath:
         else:
             call("obhip_basis_rebuild", self.basis)
         self.standardise()
+
+    def fit(self):
+        self.prepare_fit()
         if self.backend == "newton":
             # Gram on the matrix cores -> [one sum of the packed triangle + B^T y over the ranks]
             # -> H = e^{-2 sigma} G + prior -> Cholesky, two triangular solves (replicated)
@@ -379,16 +383,7 @@ class MultiHotPath(HotPath):
         self.sigma = math.log(0.01)  # loglik_std.cpp:51 on standardised responses
 
     def fit(self):
-        torch = self.torch
-        call("obhip_set_stream", C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if self.basis is None:
-            h = C.c_void_p()
-            call("obhip_basis_create_dev", C.byref(h), self.om._h, self.x.data_ptr(), self.n,
-                 self.caps.ctypes.data)
-            self.basis = h
-        else:
-            call("obhip_basis_rebuild", self.basis)
-        self.standardise()
+        self.prepare_fit()
         call("obhip_fit_newton_multi_dev", self.comm, self.basis, self.t._h, self.om._h,
              self.Y.data_ptr(), self.q, self.n, self.sigma, self.rho, self.G.data_ptr(),
              self.Grhs.data_ptr(), self.Theta.data_ptr(), self.diagH.data_ptr(),

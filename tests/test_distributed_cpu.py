@@ -180,7 +180,7 @@ def _worker_v3(rank, world, port, out_dir):
         _lib.call("obhip_comm_destroy", comm)
         sigma = math.log(0.01)
         e2 = math.exp(-2 * sigma)
-        H = np.zeros((P, P))                                    # k_unpack_form
+        H = np.zeros((P, P))                                    # k_unpack_tri<FORM>
         H[np.triu_indices(P)] = e2 * allsum_buf[:tri]
         H = H + np.triu(H, 1).T
         H[np.diag_indices(P)] += O.prior_prec(om, terms, O.DEFAULT_RHO)
