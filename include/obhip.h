@@ -313,6 +313,18 @@ int obhip_gram_dev(const obhip_basis *b, const obhip_terms *t,
  * terms of at most 8 factors on at most 128 used basis columns).  Both give the same G up to
  * summation order; DESIGN.md has the measurements. */
 int obhip_set_gram_backend(int backend);
+/* Entries of G repeat: G[s][t] depends on the per-dimension unordered level pairs {s_k, t_k} only.
+ * The staged back end gives no task to a 128 x 128 tile pair all of whose entries occur in tile
+ * pairs nearer the diagonal, and copies them from there after the reduction.  The term set is
+ * analysed once, on the device, at its first Gram or at the first of these calls (which need a
+ * device).  tile_pairs: pairs of the upper triangle; skipped: those without a task (0 with
+ * OBHIP_GRAM_DEDUP=0 and where no analysis runs: fewer than three tiles, i.e. p <= 256, or more than
+ * 48 Mi / 16384 = 3072 tile pairs); analysis_ms: host wall time the analysis took.  Any out pointer may be NULL. */
+int obhip_gram_dedup_info(const obhip_terms *t, uint64_t *tile_pairs, uint64_t *skipped, double *analysis_ms);
+/* d_src (device, p x p row-major int64): for an entry of a skipped tile pair the linear index
+ * s' * p + t' of the entry it is copied from (s' <= t', in a tile pair that is computed), -1
+ * everywhere else. */
+int obhip_gram_dedup_table_dev(const obhip_terms *t, int64_t *d_src);
 /* bytes of device workspace obhip_newton_solve_dev needs for p terms */
 int obhip_newton_workspace_bytes(uint64_t p, uint64_t *bytes);
 /* One Newton step from coeff = 0 of lpdfvec(loglik_std, logpr_gauss)

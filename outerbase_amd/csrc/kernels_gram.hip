@@ -39,8 +39,9 @@ constexpr int kRedRows = 16;  // rows of a quadrant per workgroup
 __global__ void __launch_bounds__(256)
 k_gram_reduce(const double *__restrict__ part, int npairs, int nsplit, int nb, int p,
               double *__restrict__ G, int acc, int packed, int form, double e2,
-              const double *__restrict__ prec, double *__restrict__ diagH) {
+              const double *__restrict__ prec, double *__restrict__ diagH, const uint8_t *__restrict__ skip) {
   __shared__ double S[kRedRows * 65];  // the slice, so that the mirror goes out in row segments too
+  if (skip && skip[blockIdx.x]) return;  // no task wrote its partials: k_gram_fill copies the entries
   int I = 0, rem = blockIdx.x;
   while (rem >= nb - I) {
     rem -= nb - I;
@@ -89,13 +90,13 @@ k_gram_reduce(const double *__restrict__ part, int npairs, int nsplit, int nb, i
 }  // namespace
 
 int launch_gram_reduce(const double *part, int npairs, int nsplit, int nb, int p, const GramSink &sink,
-                       bool accumulate, bool last) {
+                       bool accumulate, bool last, const uint8_t *skip) {
   ProfScope ps("gram_reduce");
   const int form = sink.form && last ? 1 : 0;
   if (form && !sink.prec) return fail(OBHIP_ERR_INVALID, "gram sink: form without the prior precisions");
   hipLaunchKernelGGL(k_gram_reduce, dim3((unsigned)npairs, 4 * (64 / kRedRows)), dim3(256), 0, cur_stream(), part, npairs,
                      nsplit, nb, p, sink.out, accumulate ? 1 : 0, sink.packed ? 1 : 0, form, sink.e2,
-                     sink.prec, sink.diagH);
+                     sink.prec, sink.diagH, skip);
   OB_HIP(hipGetLastError());
   return 0;
 }

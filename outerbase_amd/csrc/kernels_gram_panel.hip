@@ -412,11 +412,18 @@ k_atb_dma2(const double *__restrict__ A, uint64_t ldA, const double *__restrict_
 // the units are dealt CONTINUOUSLY instead (`continuous`): the task list in unit order is cut
 // into 8 equal runs, a unit may straddle two XCDs (its panels are then fetched by both).
 // gram_xcd_blocks tells the row-split choice what either dealing gives an XCD.
+//
+// Tile pairs that hold repeats of other entries of G only (`skip`, one byte per slot of the pair
+// triangle, gram_dedup.hip; may be null) get no task: their squares are smaller units, and their
+// slots of the partial-tile workspace stay unwritten.
 constexpr int kXcd = 8, kSq = 8;
 struct GramUnit {
   int bi, bj, y, size;
 };
-void gram_units(int nb, int nsplit, bool diag4, std::vector<GramUnit> &units) {
+inline bool pair_skipped(const uint8_t *skip, int nb, int i, int j) {
+  return skip && skip[i * nb - i * (i - 1) / 2 + (j - i)];
+}
+void gram_units(int nb, int nsplit, bool diag4, const uint8_t *skip, std::vector<GramUnit> &units) {
   const int nsq = (nb + kSq - 1) / kSq;
   for (int y = 0; y < nsplit; ++y)
     for (int bi = 0; bi < nsq; ++bi)
@@ -424,14 +431,14 @@ void gram_units(int nb, int nsplit, bool diag4, std::vector<GramUnit> &units) {
         int size = 0;
         for (int i = bi * kSq; i < std::min(nb, (bi + 1) * kSq); ++i)
           for (int j = std::max(i, bj * kSq); j < std::min(nb, (bj + 1) * kSq); ++j)
-            if (!(i == j && diag4 && i / 4 * 4 + 3 < nb && i % 4 == 3)) ++size;
+            if (!(i == j && diag4 && i / 4 * 4 + 3 < nb && i % 4 == 3) && !pair_skipped(skip, nb, i, j)) ++size;
         if (size) units.push_back({bi, bj, y, size});
       }
 }
 // blocks of the busiest XCD
 uint64_t gram_xcd_blocks(int nb, int nsplit, bool diag4, bool continuous) {
   std::vector<GramUnit> units;
-  gram_units(nb, 1, diag4, units);  // (every split has the same units)
+  gram_units(nb, 1, diag4, nullptr, units);  // (every split has the same units)
   uint64_t per_split = 0;
   for (const GramUnit &u : units) per_split += (uint64_t)u.size;
   if (continuous) return (per_split * (uint64_t)nsplit + kXcd - 1) / kXcd;
@@ -448,50 +455,93 @@ uint64_t gram_xcd_blocks(int nb, int nsplit, bool diag4, bool continuous) {
   }
   return *std::max_element(load, load + kXcd);
 }
-void build_task_order(int nb, int nsplit, bool diag4, bool continuous, std::vector<uint64_t> &tab) {
+void build_task_order(int nb, int nsplit, bool diag4, bool continuous, const uint8_t *skip,
+                      std::vector<uint64_t> &tab) {
   typedef GramUnit Unit;
   std::vector<Unit> units;
-  gram_units(nb, nsplit, diag4, units);
-  // largest units first, each to the XCD with the fewest blocks so far (stable: the order
-  // of equal-sized units keeps squares of one split together)
-  if (!continuous)
-    std::stable_sort(units.begin(), units.end(), [](const Unit &a, const Unit &b) { return a.size > b.size; });
-  uint64_t total = 0;
-  for (const Unit &u : units) total += (uint64_t)u.size;
-  const uint64_t run = (total + kXcd - 1) / kXcd;  // continuous: tasks per XCD
-  uint64_t dealt = 0;
-  std::vector<std::vector<uint64_t>> seq(kXcd);
-  for (const Unit &u : units) {
-    int k = 0;
-    for (int q = 1; q < kXcd; ++q)
-      if (seq[q].size() < seq[k].size()) k = q;
-    if (continuous) {  // task by task: the unit's tasks go to XCD dealt / run
-      for (int i = u.bi * kSq; i < std::min(nb, (u.bi + 1) * kSq); ++i)
-        for (int j = std::max(i, u.bj * kSq); j < std::min(nb, (u.bj + 1) * kSq); ++j) {
-          if (i == j && diag4) {
-            const int g0 = i / 4 * 4;
-            if (g0 + 3 < nb) {
-              if (i - g0 < 3) seq[(dealt++) / run].push_back(atb_task(i, i + 1, u.y, 1 + (i - g0)));
-              continue;
-            }
-          }
-          seq[(dealt++) / run].push_back(atb_task(i, j, u.y));
-        }
-      continue;
-    }
+  gram_units(nb, nsplit, diag4, skip, units);
+  // the tasks of a unit in its order
+  auto unit_tasks = [&](const Unit &u, std::vector<uint64_t> &out) {
     for (int i = u.bi * kSq; i < std::min(nb, (u.bi + 1) * kSq); ++i)
       for (int j = std::max(i, u.bj * kSq); j < std::min(nb, (u.bj + 1) * kSq); ++j) {
         if (i == j && diag4) {
           // four consecutive diagonal tiles as three blocks (atb_wave_code); squares are 8 wide,
-          // so a group never straddles two of them
+          // so a group never straddles two of them (its three blocks may still go to different
+          // XCDs where the top-up below takes single tasks of a diagonal square: they write
+          // disjoint wave tiles)
           const int g0 = i / 4 * 4;
           if (g0 + 3 < nb) {
-            if (i - g0 < 3) seq[k].push_back(atb_task(i, i + 1, u.y, 1 + (i - g0)));
+            if (i - g0 < 3) out.push_back(atb_task(i, i + 1, u.y, 1 + (i - g0)));
             continue;
           }
         }
-        seq[k].push_back(atb_task(i, j, u.y));
+        if (pair_skipped(skip, nb, i, j)) continue;
+        out.push_back(atb_task(i, j, u.y));
       }
+  };
+  std::vector<std::vector<uint64_t>> seq(kXcd);
+  // whole runs of tasks, the largest first, each to the XCD with the fewest blocks so far (stable:
+  // the order of equal-sized runs keeps squares of one split together)
+  auto deal = [&](std::vector<std::vector<uint64_t>> &runs) {
+    std::stable_sort(runs.begin(), runs.end(),
+                     [](const std::vector<uint64_t> &a, const std::vector<uint64_t> &b) { return a.size() > b.size(); });
+    for (const auto &r : runs) {
+      int k = 0;
+      for (int q = 1; q < kXcd; ++q)
+        if (seq[q].size() < seq[k].size()) k = q;
+      seq[k].insert(seq[k].end(), r.begin(), r.end());
+    }
+  };
+  static const bool topup = !(getenv("OBHIP_GRAM_TOPUP") && atoi(getenv("OBHIP_GRAM_TOPUP")) == 0);
+  if (continuous) {  // the task list in unit order cut into 8 equal runs
+    std::vector<uint64_t> all;
+    for (const Unit &u : units) unit_tasks(u, all);
+    const uint64_t run = (all.size() + kXcd - 1) / kXcd;
+    for (size_t m = 0; m < all.size(); ++m) seq[m / run].push_back(all[m]);
+  } else if (skip && topup) {
+    // An off-diagonal square that lost pairs no longer fills the 64 slots of its XCD: the next
+    // unit's first blocks would start beside it and its remaining ones a round later, and sharers
+    // of a panel that do not start together miss the L2 together.  Such a
+    // square is topped up to 64 with tasks of the split's diagonal squares -- those of its own row
+    // or column band first, whose panels it stages anyway -- and what is left of the diagonal
+    // squares goes out in runs of 64.
+    constexpr size_t kFull = (size_t)kSq * kSq;
+    std::vector<std::vector<uint64_t>> runs;
+    const int nsq = (nb + kSq - 1) / kSq;
+    size_t u0 = 0;
+    while (u0 < units.size()) {
+      size_t u1 = u0;
+      while (u1 < units.size() && units[u1].y == units[u0].y) ++u1;
+      std::vector<std::vector<uint64_t>> diag((size_t)nsq);
+      for (size_t m = u0; m < u1; ++m)
+        if (units[m].bi == units[m].bj) unit_tasks(units[m], diag[(size_t)units[m].bi]);
+      for (size_t m = u0; m < u1; ++m) {
+        const Unit &u = units[m];
+        if (u.bi == u.bj) continue;
+        std::vector<uint64_t> r;
+        unit_tasks(u, r);
+        for (int pass = 0; pass < 2 && r.size() < kFull; ++pass)
+          for (int sq = 0; sq < nsq && r.size() < kFull; ++sq) {
+            if ((pass == 0) != (sq == u.bi || sq == u.bj)) continue;
+            std::vector<uint64_t> &pool = diag[(size_t)sq];
+            while (!pool.empty() && r.size() < kFull) {
+              r.push_back(pool.back());
+              pool.pop_back();
+            }
+          }
+        runs.push_back(std::move(r));
+      }
+      std::vector<uint64_t> rest;
+      for (auto &pool : diag) rest.insert(rest.end(), pool.begin(), pool.end());
+      for (size_t m = 0; m < rest.size(); m += kFull)
+        runs.emplace_back(rest.begin() + m, rest.begin() + std::min(rest.size(), m + kFull));
+      u0 = u1;
+    }
+    deal(runs);
+  } else {
+    std::vector<std::vector<uint64_t>> runs(units.size());
+    for (size_t m = 0; m < units.size(); ++m) unit_tasks(units[m], runs[m]);
+    deal(runs);
   }
   size_t len = 0;
   for (auto &q : seq) len = std::max(len, q.size());
@@ -580,7 +630,13 @@ int gram_of_staged(obhip_basis &b, const double *d_B, uint64_t ntiles, obhip_ter
   const int ncu = device_cus(b.device);
   const bool diag4 = !(getenv("OBHIP_GRAM_DIAG4") && atoi(getenv("OBHIP_GRAM_DIAG4")) == 0);
   // blocks per row split: four consecutive diagonal tiles take three blocks (atb_wave_code)
-  const uint64_t bps = (uint64_t)npairs - (diag4 ? (uint64_t)(nb / 4) : 0);
+  // ... and tile pairs that only repeat entries of other pairs none (gram_dedup.hip; analysed on the
+  // term set's first Gram)
+  const GramDedup *dd = nullptr;
+  OB_TRY(gram_dedup_get(t, &dd));
+  const uint8_t *skip = dd ? dd->skip.data() : nullptr;
+  const uint64_t skip_sig = dd ? dd->sig : 0;
+  const uint64_t bps = (uint64_t)npairs - (diag4 ? (uint64_t)(nb / 4) : 0) - (dd ? (uint64_t)dd->nskip : 0);
   const uint64_t slots = 2 * (uint64_t)ncu;
   uint64_t nsplit = 1;
   const uint64_t max_split = std::max<uint64_t>(
@@ -615,14 +671,29 @@ int gram_of_staged(obhip_basis &b, const double *d_B, uint64_t ntiles, obhip_ter
       cached = true;
     }
   }
+  // The split is chosen WITHOUT the skipped pairs, as if every pair had its task: the entries of the
+  // computed pairs are then the same sums in the same order whether or not others are skipped (bit
+  // for bit the run with OBHIP_GRAM_DEDUP=0).  Only the dealing to the XCDs, which changes no sum,
+  // is priced on the tasks that are left -- on the table build_task_order deals for the mask (its
+  // topped-up runs are not the units gram_xcd_blocks models), once per term set and shape.
+  const uint64_t bps_all = bps + (dd ? (uint64_t)dd->nskip : 0);
+  auto price = [&](uint64_t ns, int mode, const uint8_t *mask, uint64_t blocks) {
+    uint64_t per;
+    if (mask) {
+      std::vector<uint64_t> tab;
+      build_task_order(nb, (int)ns, diag4, mode == 1, mask, tab);
+      per = tab.size() / kXcd;  // the longest XCD sequence
+    } else {
+      per = gram_xcd_blocks(nb, (int)ns, diag4, mode == 1);
+    }
+    const uint64_t full = per / xslots, tail = per % xslots;
+    const double rounds = (double)full + (tail == 0 ? 0.0 : (2 * tail <= xslots ? 0.6 : 1.0));
+    const double cost = rounds * ((double)ntiles / (double)ns + 1.0) + 0.0022 * (double)blocks;
+    return mode == 1 ? cost * 1.03 : cost;
+  };
   for (uint64_t ns = 1; !cached && ns <= max_split; ++ns) {
-    const uint64_t blocks = ns * bps;
     for (int mode = 0; mode < 2; ++mode) {
-      const uint64_t per = gram_xcd_blocks(nb, (int)ns, diag4, mode == 1);
-      const uint64_t full = per / xslots, tail = per % xslots;
-      const double rounds = (double)full + (tail == 0 ? 0.0 : (2 * tail <= xslots ? 0.6 : 1.0));
-      double cost = rounds * ((double)ntiles / (double)ns + 1.0) + 0.0022 * (double)blocks;
-      if (mode == 1) cost *= 1.03;
+      const double cost = price(ns, mode, nullptr, ns * bps_all);
       if (cost < bestc - 1e-9) {
         bestc = cost;
         nsplit = ns;
@@ -635,15 +706,27 @@ int gram_of_staged(obhip_basis &b, const double *d_B, uint64_t ntiles, obhip_ter
     split_cache[split_key] = std::make_pair(nsplit, continuous);
   }
   if (const char *e = getenv("OBHIP_GRAM_NSPLIT")) nsplit = std::max<uint64_t>(1, std::min<uint64_t>(max_split, atoi(e)));
+  if (skip) {  // the dealing for this mask at this split: kept with the analysis
+    GramDedup &d = t.dedup;
+    const auto key = std::make_tuple(ntiles, nsplit, slots, diag4);
+    if (!d.cont_known || d.cont_key != key) {
+      d.cont = price(nsplit, 1, skip, nsplit * bps) < price(nsplit, 0, skip, nsplit * bps) - 1e-9;
+      d.cont_key = key;
+      d.cont_known = true;
+    }
+    continuous = d.cont;
+  }
   if (const char *e = getenv("OBHIP_GRAM_CONTINUOUS")) continuous = atoi(e) != 0;
   double *part = nullptr;
   OB_TRY(b.workspace((size_t)nsplit * npairs * kGT * kGT * sizeof(double) + 256, (void **)&part));
   unsigned long long *dbgout =
       dbg ? (unsigned long long *)(part + (size_t)nsplit * npairs * kGT * kGT) : nullptr;
   if (b.gram_pairs_nb != nb || b.gram_pairs_ns != (int)nsplit || b.gram_pairs_diag4 != diag4 ||
-      b.gram_pairs_cont != continuous) {
+      b.gram_pairs_cont != continuous || b.gram_pairs_skip != skip_sig) {
     std::vector<uint64_t> tab;
-    build_task_order(nb, (int)nsplit, diag4, continuous, tab);
+    build_task_order(nb, (int)nsplit, diag4, continuous, skip, tab);
+    b.gram_pairs_nb = -1;  // (not the old table's key should the upload fail)
+    b.gram_pairs_skip = skip_sig;
     b.gram_pairs_diag4 = diag4;
     b.gram_pairs_cont = continuous;
     OB_TRY(b.gram_pairs.upload(tab.data(), tab.size()));
@@ -681,7 +764,12 @@ int gram_of_staged(obhip_basis &b, const double *d_B, uint64_t ntiles, obhip_ter
             "per 16-row chunk (8192 = matrix pipe saturated by two blocks)\n",
             h[0], h[1], h[1] ? 100.0 * h[0] / h[1] : 0.0, h[2] ? (double)h[0] / h[2] : 0.0);
   }
-  return launch_gram_reduce(part, npairs, (int)nsplit, nb, (int)t.p, sink, accumulate, last);
+  OB_TRY(launch_gram_reduce(part, npairs, (int)nsplit, nb, (int)t.p, sink, accumulate, last,
+                            dd ? dd->skip_dev.p : nullptr));
+  // the skipped pairs' entries from their sources in the sink: after every reduction (of a row
+  // chunk too: the sources then hold the sums so far, the copies likewise), formed values when the
+  // reduction formed the Hessian
+  return dd ? launch_gram_fill(*dd, (int)t.p, sink) : 0;
 }
 
 }  // namespace

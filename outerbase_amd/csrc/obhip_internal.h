@@ -12,6 +12,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/obhip.h"
@@ -270,6 +271,22 @@ struct ShareTables {
 int build_share_tables(const uint16_t *hc, uint64_t p_pad, uint64_t W, ShareTables &out, bool renumber = false,
                        uint64_t ncol = 0);
 bool share_wanted();  // OBHIP_SHARE=0: the kernels take the plain tables (A/B measurements)
+
+// tile pairs of the panel Gram that hold repeats of other entries of G only (csrc/gram_dedup.hip):
+// analysed once per term set, on the device
+struct GramDedup {
+  bool tried = false;
+  int hashbits = 0;            // bits of the hash the analysis ran with (OBHIP_GRAM_DEDUP_HASHBITS)
+  int nb = 0, npairs = 0, nskip = 0;
+  double analysis_ms = 0.0;    // host wall time of the analysis, uploads and read-back included
+  uint64_t sig = 0;            // serial number of the analysis (non-zero): key of the task tables built on the mask
+  bool cont_known = false, cont = false;  // dealing chosen for the mask (continuous or whole runs) at the shape
+  std::tuple<uint64_t, uint64_t, uint64_t, bool> cont_key;  // (row tiles, row splits, block slots, diag4)
+  std::vector<uint8_t> skip;   // per tile pair (row-major slot in the upper triangle): 1 = no task
+  DevBuf<uint8_t> skip_dev;    // the same on the device
+  DevBuf<uint32_t> pairs;      // nskip skipped tile pairs, I | J << 16
+  DevBuf<uint32_t> src;        // nskip x 128 x 128: the entry's source s' << 16 | t' (s' <= t', in a kept pair)
+};
 }  // namespace obhip
 
 struct obhip_terms {
@@ -349,6 +366,7 @@ struct obhip_terms {
   const obhip_model *prec_model = nullptr;
   uint64_t prec_version = 0;
   double prec_rho = 0.0;
+  obhip::GramDedup dedup;             // redundant tile pairs of the panel Gram (levels only: no cap in its key)
   int prepare(const std::vector<int64_t> &cap, const std::vector<obhip::DimDesc> &dims);
 };
 
@@ -395,6 +413,7 @@ struct obhip_basis {
   obhip::DevBuf<uint64_t> gram_pairs;  // XCD-aware (tile pair, row split) task order of that kernel
   int gram_pairs_nb = -1, gram_pairs_ns = -1;
   bool gram_pairs_diag4 = false, gram_pairs_cont = false;
+  uint64_t gram_pairs_skip = 0;  // GramDedup::sig of the mask the order was built with (0: none)
   std::unique_ptr<obhip_gradbasis> grad;  // built on first *_gradhyp call, dropped on rebuild
   int device = 0;
   int workspace(size_t bytes, void **out) {
@@ -495,8 +514,13 @@ struct GramFuse {
 };
 int launch_gram(const obhip_basis &b, obhip_terms &t, double *d_G);
 int launch_gram_to(const obhip_basis &b, obhip_terms &t, const GramSink &sink, GramFuse *fuse = nullptr);
+// skip (device, may be null): tile pairs whose partials were never written and that are left alone
 int launch_gram_reduce(const double *part, int npairs, int nsplit, int nb, int p, const GramSink &sink,
-                       bool accumulate, bool last);
+                       bool accumulate, bool last, const uint8_t *skip = nullptr);
+// gram_dedup.hip: *out = the redundant tile pairs of t's term set, nullptr when there are none (or
+// OBHIP_GRAM_DEDUP=0); launch_gram_fill copies their entries from their sources in the sink
+int gram_dedup_get(obhip_terms &t, const GramDedup **out);
+int launch_gram_fill(const GramDedup &dd, int p, const GramSink &sink);
 void set_gram_backend(int b);
 int get_gram_backend();
 // kernels_gram_panel.hip
