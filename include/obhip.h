@@ -614,6 +614,51 @@ int obhip_normal_acc_solve_dev(const obhip_normal_acc *acc, const obhip_normal_a
 int obhip_cv_score_dev(const double *d_mean, const double *d_Y_raw, uint64_t n, uint64_t q,
                        uint64_t ld, const double *d_meansd, double *d_out);
 
+/* ---- observed input gradients as rows of the Newton fit (no reference counterpart) ----
+ * A computer code with an adjoint returns dy/dx with y: 1 + d equations per run.  With
+ * y~ = (y - cent) / sd and g~_l = g_l / sd (the gradient has no offset: cent and sd come from the
+ * value rows only), D_l[i,k] = dB[i,k] / dx_l and a weight w_l > 0 per differentiated dimension
+ * (gradients carry the units of 1 / x_l, so their noise differs by dimension) the Newton step solves
+ *   (e^{-2 sigma} (B^T B + sum_l w_l D_l^T D_l) + diag(prec)) theta
+ *       = e^{-2 sigma} (B^T y~ + sum_l w_l D_l^T g~_l).
+ * In the accumulator's state a gradient batch adds sum_l w_l D_l^T D_l to the triangle and
+ * sum_l w_l D_l^T g_l (raw g) to R, nothing to B^T 1 and the moments; the solve's right-hand side
+ * (R - (cent - c) B^T 1) / sd is then already the one above.  In the notation of
+ * obhip_predict_grad_dev,
+ *   D_l[i,k] = s_i (rho_l P_k + [t_kl > 0] E_kl r'_{l,t_kl}),
+ * every entry non-zero through rho_l, the derivative of the row scale: D_l is dense.
+ * The batch is staged in row chunks as L blocks sqrt(w_l) D_l (one kernel; fused while the terms
+ * use at most 8 factors and the tile of 2 Mu - 1 + d columns plus its reduction space fits 160 KB of
+ * LDS, from a pooled HBM tile per block beyond that and under OBHIP_FORCE_GENERIC: every term set
+ * obhip_predict_grad_dev accepts) and goes through the Gram kernels of obhip_gram_dev; the right-hand
+ * side of the first response rides along with the staging, the others take one pass over the staged
+ * chunk each.  No atomics: two calls give the same bits.  Scratch: the packed triangle, p q doubles
+ * and one staged chunk (at most a quarter of the free HBM and 16 GB; OBHIP_GRAM_CHUNK_ROWS sets the
+ * batch rows per chunk for tests).
+ * dims (host): ndims distinct dimensions, each < d, 1 <= ndims <= d.  weights (host, ndims): finite
+ * and > 0, NULL = all 1.  Refused in this order, before any device call, with OBHIP_ERR_INVALID:
+ * a null argument, ndims = 0 (or > d), a repeated dimension, a dimension >= d, a weight <= 0 or not
+ * finite, lddy < n, ldo < p.  n = 0 is a no-op; at most 2^40 rows per call. */
+/* out[(j*n + i)*ldo + k] = sqrt(w_j) dB[i,k]/dx_{dims[j]}; d_x column-major n x d (ld = n); ldo >= p;
+ * nothing else of d_out is written */
+int obhip_design_dx_dev(const obhip_model *m, const obhip_terms *t, const double *d_x, uint64_t n,
+                        const uint32_t *dims, uint64_t ndims, const double *weights,
+                        double *d_out, uint64_t ldo);
+/* d_dY_raw[(r*ndims + j)*lddy + i] = d y_r / d x_{dims[j]} at row i (raw units), r < q; sign = +1
+ * adds the n ndims gradient equations, sign = -1 takes out a batch added before (more equations than
+ * the state holds: OBHIP_ERR_STATE).  Value rows (obhip_normal_acc_info) and the fewer-than-two-rows
+ * rule of the solve count value rows only; gradient and value batches may come in any order, and the
+ * tie to the model's state holds from the first batch of either kind.  A state without value rows
+ * and gradient equations is reset.  obhip_normal_acc_combine_dev and the `minus` of the solve carry
+ * the gradient rows with them. */
+int obhip_normal_acc_add_grad_dev(obhip_normal_acc *acc, const double *d_x, uint64_t n,
+                                  const uint32_t *dims, uint64_t ndims, const double *weights,
+                                  const double *d_dY_raw, uint64_t lddy, int sign);
+/* gradient equations in the state (rows x differentiated dimensions) and their batches; either
+ * pointer may be NULL */
+int obhip_normal_acc_grad_info(const obhip_normal_acc *acc, uint64_t *grad_equations,
+                               uint64_t *grad_batches);
+
 /* ---- predictor ---------------------------------------------------------- */
 /* predictor$update(x) + $mean() (+ $var() of pred_gauss):
  * loglik_gauss.cpp:214-227, loglik_std.cpp:239-248.  The basis at xnew is

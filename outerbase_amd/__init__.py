@@ -14,7 +14,8 @@ from .obmod import (covf, covf_mat25, covf_mat25ang, covf_mat25pow, gethyp, getp
 from .fitting import BFGS_lpdf, BFGS_std, obfit, obpred, obpred_grad
 from .multi import MultiFit, fit_newton_multi
 from .driver import HotPath, MultiHotPath
-from .stream import CVResult, NewtonAccumulator, cv_folds, cv_newton_multi
+from .stream import (CVResult, NewtonAccumulator, cv_folds, cv_newton_multi, design_dx,
+                     fit_newton_grad)
 
 __all__ = [
     "ObhipError", "device_count", "covf", "covf_mat25", "covf_mat25ang", "covf_mat25pow", "gethyp",
@@ -24,4 +25,5 @@ __all__ = [
     "MultiFit", "fit_newton_multi", "HotPath", "MultiHotPath",
     "NewtonAccumulator", "cv_newton_multi", "cv_folds", "CVResult",
     "predict_grad", "obpred_grad", "term_dim_views",
+    "design_dx", "fit_newton_grad",
 ]

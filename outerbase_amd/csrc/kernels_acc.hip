@@ -192,6 +192,17 @@ int launch_acc_fold(uint64_t p, uint64_t q, double *d_dst, const double *d_src, 
   return 0;
 }
 
+// dst +/- src over [tri][R] alone: gradient rows add nothing to B^T 1 and the moments, and R needs no
+// move of the shift (their part of it does not depend on c)
+int launch_acc_fold_grad(uint64_t p, uint64_t q, double *d_dst, const double *d_src, double sign) {
+  ProfScope ps("acc_fold");
+  const uint64_t count = p * (p + 1) / 2 + p * q;
+  const unsigned blocks = (unsigned)std::min<uint64_t>(8192, (count / 2 + 255) / 256 + 1);
+  hipLaunchKernelGGL(k_acc_fold, dim3(blocks), dim3(256), 0, cur_stream(), d_dst, d_src, count, sign);
+  OB_HIP(hipGetLastError());
+  return 0;
+}
+
 // d_state / d_minus (may be null): whole accumulator buffers
 int launch_acc_rhs(uint64_t p, uint64_t q, const double *d_state, const double *d_minus, double e2, double *d_rhs,
                    double *d_meansd) {

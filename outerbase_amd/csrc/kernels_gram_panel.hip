@@ -774,6 +774,12 @@ int gram_of_staged(obhip_basis &b, const double *d_B, uint64_t ntiles, obhip_ter
 
 }  // namespace
 
+// for rows the caller staged itself (grad_obs.cpp: the derivative design matrix)
+int gram_of_staged_rows(obhip_basis &holder, const double *d_B, uint64_t ntiles, obhip_terms &t, const GramSink &sink,
+                        bool accumulate, bool last) {
+  return gram_of_staged(holder, d_B, ntiles, t, sink, accumulate, last);
+}
+
 // d_B: n_pad x p_pad doubles, row-major (= column-major p_pad x n_pad); padding rows are 0
 int launch_materialize_rows(const obhip_basis &b, obhip_terms &t, double *d_B, GramFuse *fuse) {
   OB_TRY(t.prepare(b.md.cap, b.md.dims_h));

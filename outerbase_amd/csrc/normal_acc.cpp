@@ -29,8 +29,12 @@ struct obhip_normal_acc {
   const obhip_terms *terms = nullptr;
   uint64_t p = 0, q = 0;
   uint64_t rows = 0, batches = 0;
-  uint64_t version = 0;  // of the model when the first batch came in (rows > 0)
+  uint64_t geq = 0, gbatches = 0;  // gradient equations (rows x differentiated dimensions) and their batches
+  uint64_t version = 0;  // of the model when the first batch came in (rows > 0 or geq > 0)
   DevBuf<double> st;     // [tri][R p x q][b1 p][moments 4 q]
+  // lends the Gram of staged gradient rows its device, workspace and task-table cache; it never has rows
+  // of its own, and the staged buffer is never its bmat
+  std::unique_ptr<obhip_basis> gholder;
 };
 
 namespace {
@@ -42,6 +46,7 @@ uint64_t state_count(uint64_t p, uint64_t q) { return p * (p + 1) / 2 + p * q + 
 int zero_state(obhip_normal_acc *a) {
   OB_HIP(hipMemsetAsync(a->st.p, 0, a->st.n * sizeof(double), cur_stream()));
   a->rows = a->batches = 0;
+  a->geq = a->gbatches = 0;
   return 0;
 }
 
@@ -52,10 +57,23 @@ bool same_terms(const obhip_terms *a, const obhip_terms *b) {
 
 // the model must be what it was when the state's first rows came in
 int check_version(const obhip_normal_acc *a, const char *who) {
-  if (a->rows > 0 && a->version != a->model->version)
+  if ((a->rows > 0 || a->geq > 0) && a->version != a->model->version)
     return fail(OBHIP_ERR_STATE, std::string(who) +
                                      ": the model's hyper-parameters or knots changed since the accumulator's first "
                                      "batch (G depends on them): reset it and add the rows again");
+  return 0;
+}
+
+// after rows or gradient equations left.  Nothing of either kind left: the sums are rounding residue of what
+// was there, the state starts afresh.  No value rows left beside gradient rows: B^T 1 and the moments are
+// such residue (the next value batch brings its own shift)
+int after_removal(obhip_normal_acc *a) {
+  if (a->rows == 0 && a->geq == 0) return zero_state(a);
+  if (a->rows == 0) {
+    const uint64_t head = a->p * (a->p + 1) / 2 + a->p * a->q;
+    OB_HIP(hipMemsetAsync(a->st.p + head, 0, (a->st.n - head) * sizeof(double), cur_stream()));
+    a->batches = 0;
+  }
   return 0;
 }
 
@@ -153,16 +171,65 @@ int obhip_normal_acc_add_dev(obhip_normal_acc *acc, const obhip_basis *bc, const
   // columns 1 .. q - 1 of Y - c, then the ones column: B^T 1
   OB_TRY(bty_columns(b, t, Ys.p + n, n, q, s_rb + p));
   OB_TRY(launch_acc_fold(p, q, acc->st.p, scratch.p, empty, (double)sign));
-  if (empty) acc->version = acc->model->version;
+  if (empty && acc->geq == 0) acc->version = acc->model->version;
   if (sign > 0) {
     acc->rows += n;
     acc->batches += 1;
   } else {
     acc->rows -= n;
     acc->batches -= acc->batches > 0 ? 1 : 0;
-    // nothing left: the sums are rounding residue of what was there, the state starts afresh
-    if (acc->rows == 0) OB_TRY(zero_state(acc));
+    OB_TRY(after_removal(acc));
   }
+  return 0;
+}
+
+int obhip_normal_acc_add_grad_dev(obhip_normal_acc *acc, const double *d_x, uint64_t n, const uint32_t *dims,
+                                  uint64_t ndims, const double *weights, const double *d_dY_raw, uint64_t lddy,
+                                  int sign) {
+  if (!acc || !dims || (sign != 1 && sign != -1) || (n > 0 && (!d_x || !d_dY_raw)))
+    return fail(OBHIP_ERR_INVALID, "normal_acc_add_grad_dev: null accumulator, x, dims or dY, or a sign other than +1 / -1");
+  OB_TRY(check_grad_dims("normal_acc_add_grad_dev", acc->model->d, dims, ndims, weights));
+  if (lddy < n) return fail(OBHIP_ERR_INVALID, "normal_acc_add_grad_dev: lddy below the rows of the batch");
+  if (n > (1ull << 40)) return fail(OBHIP_ERR_INVALID, "normal_acc_add_grad_dev: more than 2^40 rows in one call");
+  if (n == 0) return 0;
+  OB_TRY(check_compat(acc->model, acc->terms));
+  OB_TRY(check_version(acc, "normal_acc_add_grad_dev"));
+  const uint64_t eq = n * ndims;
+  if (sign < 0 && eq > acc->geq)
+    return fail(OBHIP_ERR_STATE, "normal_acc_add_grad_dev: removing " + std::to_string(eq) +
+                                     " gradient equations from an accumulator that holds " + std::to_string(acc->geq));
+  OB_TRY(require_device());
+  if (!acc->gholder) {
+    acc->gholder.reset(new (std::nothrow) obhip_basis());
+    if (!acc->gholder) return fail(OBHIP_ERR_INVALID, "normal_acc_add_grad_dev: out of host memory");
+    acc->gholder->model = acc->model;
+    acc->gholder->d = acc->model->d;
+    (void)hipGetDevice(&acc->gholder->device);
+  }
+  const uint64_t p = acc->p, q = acc->q, tri = p * (p + 1) / 2;
+  DevBuf<double> scratch;
+  OB_TRY(scratch.alloc(tri + p * q));
+  // sum_l w_l D_l^T D_l to the triangle, sum_l w_l D_l^T g_l (raw g: k_acc_rhs divides by sd) to R; nothing
+  // to B^T 1 and the moments -- the gradient has no offset
+  OB_TRY(grad_batch_normal_eq(*acc->gholder, *acc->model, *const_cast<obhip_terms *>(acc->terms), d_x, n, dims, weights,
+                              ndims, d_dY_raw, lddy, q, scratch.p, scratch.p + tri));
+  OB_TRY(launch_acc_fold_grad(p, q, acc->st.p, scratch.p, (double)sign));
+  if (acc->rows == 0 && acc->geq == 0) acc->version = acc->model->version;
+  if (sign > 0) {
+    acc->geq += eq;
+    acc->gbatches += 1;
+  } else {
+    acc->geq -= eq;
+    acc->gbatches -= acc->gbatches > 0 ? 1 : 0;
+    OB_TRY(after_removal(acc));
+  }
+  return 0;
+}
+
+int obhip_normal_acc_grad_info(const obhip_normal_acc *acc, uint64_t *grad_equations, uint64_t *grad_batches) {
+  if (!acc) return fail(OBHIP_ERR_INVALID, "normal_acc_grad_info: null argument");
+  if (grad_equations) *grad_equations = acc->geq;
+  if (grad_batches) *grad_batches = acc->gbatches;
   return 0;
 }
 
@@ -171,23 +238,34 @@ int obhip_normal_acc_combine_dev(obhip_normal_acc *dst, const obhip_normal_acc *
   if (dst == src) return fail(OBHIP_ERR_INVALID, "normal_acc_combine_dev: an accumulator cannot be combined with itself");
   if (dst->model != src->model || !same_terms(dst->terms, src->terms) || dst->p != src->p || dst->q != src->q)
     return fail(OBHIP_ERR_INVALID, "normal_acc_combine_dev: the accumulators differ in model, terms or responses");
-  if (src->rows == 0) return 0;
+  if (src->rows == 0 && src->geq == 0) return 0;
   OB_TRY(check_version(dst, "normal_acc_combine_dev"));
   OB_TRY(check_version(src, "normal_acc_combine_dev"));
   if (sign < 0 && src->rows > dst->rows)
     return fail(OBHIP_ERR_STATE, "normal_acc_combine_dev: removing " + std::to_string(src->rows) +
                                      " rows from an accumulator that holds " + std::to_string(dst->rows));
+  if (sign < 0 && src->geq > dst->geq)
+    return fail(OBHIP_ERR_STATE, "normal_acc_combine_dev: removing " + std::to_string(src->geq) +
+                                     " gradient equations from an accumulator that holds " + std::to_string(dst->geq));
   OB_TRY(require_device());
-  const bool empty = dst->rows == 0;
-  OB_TRY(launch_acc_fold(dst->p, dst->q, dst->st.p, src->st.p, empty, (double)sign));
-  if (empty) dst->version = src->version;
+  const bool empty = dst->rows == 0;  // of value rows: the shift is theirs alone
+  const bool fresh = empty && dst->geq == 0;
+  if (src->rows == 0)  // gradient rows only: no B^T 1, no moments, no shift
+    OB_TRY(launch_acc_fold_grad(dst->p, dst->q, dst->st.p, src->st.p, (double)sign));
+  else
+    OB_TRY(launch_acc_fold(dst->p, dst->q, dst->st.p, src->st.p, empty, (double)sign));
+  if (fresh) dst->version = src->version;
   if (sign > 0) {
     dst->rows += src->rows;
     dst->batches += src->batches;
+    dst->geq += src->geq;
+    dst->gbatches += src->gbatches;
   } else {
     dst->rows -= src->rows;
     dst->batches -= std::min(dst->batches, src->batches);
-    if (dst->rows == 0) OB_TRY(zero_state(dst));
+    dst->geq -= src->geq;
+    dst->gbatches -= std::min(dst->gbatches, src->gbatches);
+    OB_TRY(after_removal(dst));
   }
   return 0;
 }
@@ -203,7 +281,7 @@ int obhip_normal_acc_solve_dev(const obhip_normal_acc *acc, const obhip_normal_a
   OB_TRY(check_compat(m, acc->terms));
   OB_TRY(check_version(acc, "normal_acc_solve_dev"));
   if (minus) OB_TRY(check_version(minus, "normal_acc_solve_dev"));
-  if (minus && minus->rows > acc->rows)
+  if (minus && (minus->rows > acc->rows || minus->geq > acc->geq))
     return fail(OBHIP_ERR_STATE, "normal_acc_solve_dev: more rows to take out than the accumulator holds");
   const uint64_t left = acc->rows - (minus ? minus->rows : 0);
   if (left < 2)
@@ -219,7 +297,7 @@ int obhip_normal_acc_solve_dev(const obhip_normal_acc *acc, const obhip_normal_a
   const double *d_prec = nullptr;
   OB_TRY(terms_prec_dev(m, t, rho, &d_prec));
   const double e2 = std::exp(-2.0 * sigma);
-  const double *d_minus = minus && minus->rows > 0 ? minus->st.p : nullptr;
+  const double *d_minus = minus && (minus->rows > 0 || minus->geq > 0) ? minus->st.p : nullptr;
   DevBuf<double> rhs;
   OB_TRY(rhs.alloc(p * q));
   {

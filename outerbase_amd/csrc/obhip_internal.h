@@ -359,6 +359,9 @@ struct obhip_terms {
     const obhip_model *tab_model = nullptr;
     uint64_t tab_version = ~0ull;
     std::vector<int64_t> tab_cap;
+    // staging of the derivative design matrix (kernels_materialize_dx.hip): used column -> dimension
+    obhip::DevBuf<int32_t> udim;     // Mu (-1: the ones column)
+    std::vector<int64_t> udim_cap;   // column layout it was made for
   } dx;
   // prior precisions 1 / (sd e^rho)^2 of these terms on the device, for the model state and rho
   // they were last asked for (the device-side Newton fit: no upload, no host sync per fit)
@@ -598,7 +601,42 @@ int ensure_dx_tables(const obhip_model &m, obhip_terms &t);  // after t.prepare(
 int launch_predict_dx(const obhip_model &m, obhip_terms &t, const double *d_theta, const double *d_x, uint64_t n,
                       double *d_mean, double *d_grad, const double *d_coeffvar, double e2sigma, double *d_var,
                       double *d_gradvar);
+// kernels_materialize_dx.hip / grad_obs.cpp: the derivative design matrix as rows of the normal equations
+struct DxStage {
+  const double *x = nullptr;        // device, column-major with leading dimension ldx, n rows from x on
+  uint64_t ldx = 0, n = 0;
+  const uint32_t *dims = nullptr;   // device: the L differentiated dimensions
+  const double *sqw = nullptr;      // device: sqrt(w_j)
+  uint64_t L = 0;
+  double *out = nullptr;            // out[(j * blk_rows + i) * pitch + k] = sqrt(w_j) dB[i,k] / dx_{dims[j]}
+  uint64_t pitch = 0, blk_rows = 0;
+  uint64_t pcols = 0;               // columns written per row: p .. pcols as zeros
+  bool pad_rows = false;            // rows n .. next multiple of 64 written as zeros
+  const double *g = nullptr;        // with ypart: g[j * ldg + i], one response's observed gradients (raw)
+  uint64_t ldg = 0;
+  double *ypart = nullptr;          // [ceil(n / 64)][pitch] partial (staged)^T sqrt(w) g per tile
+};
+// dims distinct and < d, 1 <= ndims <= d, weights (may be null) finite and > 0 -- refused in that order
+int check_grad_dims(const char *who, uint64_t d, const uint32_t *dims, uint64_t ndims, const double *weights);
+int ensure_dx_stage(const obhip_model &m, obhip_terms &t);  // tables of the staging kernel (device)
+bool materialize_dx_supports(const obhip_terms &t);
+int launch_materialize_dx(const obhip_model &m, obhip_terms &t, const DxStage &s);
+uint64_t dx_aty_splits(uint64_t rows);
+int launch_dx_aty(const double *d_B, uint64_t pitch, uint64_t blk_rows, uint64_t L, uint64_t n, const double *d_sqw,
+                  const double *d_g, uint64_t ldg, double *d_part, uint64_t p, bool accumulate, double *d_out);
+int launch_dx_colsum(const double *d_part, uint64_t nsplit, uint64_t pitch, uint64_t p, bool accumulate, double *d_out);
+// sum_j w_j D_j^T D_j of the batch d_x (n x d, ld = n) into the packed triangle d_tri and, per response r,
+// sum_j w_j D_j^T g_rj into d_R + r * p; holder: a basis that lends gram_of_staged its device, workspace
+// and task-table cache (never its bmat)
+int grad_batch_normal_eq(obhip_basis &holder, const obhip_model &m, obhip_terms &t, const double *d_x, uint64_t n,
+                         const uint32_t *dims, const double *weights, uint64_t L, const double *d_dY, uint64_t lddy,
+                         uint64_t q, double *d_tri, double *d_R);
+// kernels_gram_panel.hip: gram_of_staged for a caller that stages its own rows (ntiles x 64 rows, pitch p_pad)
+int gram_of_staged_rows(obhip_basis &holder, const double *d_B, uint64_t ntiles, obhip_terms &t, const GramSink &sink,
+                        bool accumulate, bool last);
 // kernels_acc.hip: the streaming fit's batch moments, folds and right-hand sides (normal_acc.cpp)
+// dst +/- src over the triangle and R only (a batch of gradient rows has no B^T 1 and no moments)
+int launch_acc_fold_grad(uint64_t p, uint64_t q, double *d_dst, const double *d_src, double sign);
 int launch_acc_batch_moments(const double *d_Y, uint64_t ldy, uint64_t n, uint64_t q, bool empty,
                              const double *d_mom_state, double *d_mom_batch, double *d_Ys, double *d_part);
 int launch_acc_fold(uint64_t p, uint64_t q, double *d_dst, const double *d_src, bool dst_empty, double sign);

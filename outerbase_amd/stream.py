@@ -146,6 +146,49 @@ class NewtonAccumulator:
         """Take out rows that were added before (the same x and Y)."""
         return self._batch(x, Y, -1)
 
+    # -- observed input gradients -------------------------------------------------------------
+    @property
+    def grad_rows(self):
+        """Gradient equations in the state: rows times differentiated dimensions of every batch."""
+        self._need()
+        eq = C.c_uint64(0)
+        call("obhip_normal_acc_grad_info", self._h, C.byref(eq), None)
+        return eq.value
+
+    def _grad_batch(self, x, dY, dims, weights, sign):
+        x, dims, weights = _check_grad_x(self.om, x, dims, weights)
+        n, L = x.shape[0], len(dims)
+        dY = np.asarray(dY, dtype=np.float64)
+        if dY.ndim == 2:
+            dY = dY[:, :, None]
+        if dY.ndim != 3 or dY.shape != (n, L, self.q):
+            raise ValueError("dY must be n x %d (x %d): one column per differentiated dimension (and response)"
+                             % (L, self.q))
+        if not np.all(np.isfinite(dY)):
+            raise ValueError("dY must be finite")
+        self._need()
+        if n == 0:
+            return self
+        import torch
+        dev = _stream()
+        dx = torch.from_numpy(np.ascontiguousarray(x.T)).to(dev)
+        dg = torch.from_numpy(np.ascontiguousarray(dY.transpose(2, 1, 0))).to(dev)     # [response][dimension][row]
+        call("obhip_normal_acc_add_grad_dev", self._h, dx.data_ptr(), n, dims.ctypes.data, L,
+             None if weights is None else weights.ctypes.data, dg.data_ptr(), n, sign)
+        torch.cuda.synchronize()
+        return self
+
+    def add_grad(self, x, dY, dims=None, weights=None):
+        """Add the observed gradients dY (n x L, or n x L x q: dY[i, j] = dy / dx_dims[j] at row i, raw
+        units) at the rows x (n x d) as n L further equations of the fit, dimension dims[j] weighted by
+        weights[j] > 0 (include/obhip.h, "observed input gradients").  dims=None: all d dimensions;
+        weights=None: all 1.  The responses' mean and standard deviation stay those of the value rows."""
+        return self._grad_batch(x, dY, dims, weights, +1)
+
+    def remove_grad(self, x, dY, dims=None, weights=None):
+        """Take out gradient rows that were added before (the same x, dY, dims and weights)."""
+        return self._grad_batch(x, dY, dims, weights, -1)
+
     def merge(self, other, sign=+1):
         """self += sign * other (another accumulator of the same model, terms and q)"""
         if not isinstance(other, NewtonAccumulator):
@@ -195,6 +238,55 @@ class NewtonAccumulator:
         torch.cuda.synchronize()
         return MultiFit(self.om, self._t, theta.cpu().numpy().T.copy(), meansd.cpu().numpy(), diagH.cpu().numpy(),
                         float(sigma), float(rho))
+
+
+def _check_grad_x(om, x, dims, weights):
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] != om.d:
+        raise ValueError("x must be n x d")
+    if not np.all(np.isfinite(x)):
+        raise ValueError("x must be finite")
+    dims = np.arange(om.d, dtype=np.uint32) if dims is None else np.atleast_1d(np.asarray(dims))
+    if dims.ndim != 1 or len(dims) == 0 or not np.issubdtype(dims.dtype, np.integer):
+        raise ValueError("dims must be a non-empty list of dimensions")
+    if np.any(dims < 0) or np.any(dims >= om.d) or len(set(dims.tolist())) != len(dims):
+        raise ValueError("dims must be distinct dimensions below d = %d" % om.d)
+    dims = np.ascontiguousarray(dims, dtype=np.uint32)
+    if weights is not None:
+        weights = np.ascontiguousarray(np.atleast_1d(weights), dtype=np.float64)
+        if weights.shape != dims.shape or not np.all(np.isfinite(weights)) or np.any(weights <= 0):
+            raise ValueError("weights must be one finite positive number per differentiated dimension")
+    return x, dims, weights
+
+
+def design_dx(om, terms, x, dims=None, weights=None):
+    """The derivative design matrix at the rows x (n x d): out[j, i, k] = sqrt(weights[j]) dB[i, k] / dx_dims[j],
+    an (L, n, p) array (obhip_design_dx_dev).  dims=None: all d dimensions; weights=None: all 1."""
+    import torch
+    x, dims, weights = _check_grad_x(om, x, dims, weights)
+    t = obmod._terms_of(om, terms)
+    n, L = x.shape[0], len(dims)
+    if n == 0:
+        return np.zeros((L, 0, t.p))
+    dev = _stream()
+    dx = torch.from_numpy(np.ascontiguousarray(x.T)).to(dev)
+    out = torch.empty((L, n, t.p), dtype=torch.float64, device=dev)
+    call("obhip_design_dx_dev", om._h, t._h, dx.data_ptr(), n, dims.ctypes.data, L,
+         None if weights is None else weights.ctypes.data, out.data_ptr(), t.p)
+    torch.cuda.synchronize()
+    return out.cpu().numpy()
+
+
+def fit_newton_grad(om, terms, x, Y, dY, xg=None, dims=None, weights=None, sigma=None, rho=DEFAULT_RHO):
+    """The Newton fit of fit_newton_multi on the rows x (n x d) with responses Y (n x q) AND their observed
+    input gradients dY (ng x L, or ng x L x q) at the rows xg (None: at x itself): an accumulator filled
+    once.  dims, weights: as NewtonAccumulator.add_grad.  dY=None: the value rows alone.  -> MultiFit"""
+    x, Y = _check_xy(om, x, Y)
+    with NewtonAccumulator(om, terms, Y.shape[1]) as acc:
+        acc.add(x, Y)
+        if dY is not None:
+            acc.add_grad(x if xg is None else xg, dY, dims=dims, weights=weights)
+        return acc.fit(sigma=sigma, rho=rho)
 
 
 def cv_folds(n, folds, seed=0):
