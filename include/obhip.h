@@ -706,6 +706,40 @@ int obhip_predict_grad(const obhip_model *m, const obhip_terms *t, const double 
  * x_dim sums over beside the dense part.  *count always; terms_out (count entries) may be NULL.
  * Host only. */
 int obhip_terms_dimview(const obhip_terms *t, uint64_t dim, uint64_t *count, uint32_t *terms_out);
+/* Jacobian and vector-Jacobian product of the predictor of q responses that share the model and the
+ * terms (obhip_predict_multi_dev).  The reference has no counterpart.  In the notation of
+ * obhip_predict_grad_dev, for response j with the coefficients Theta[:, j]:
+ *   mean_ij        = s_i sum_k Theta_kj P_k(i)
+ *   dmean_ij/dx_l  = s_i (rho_l(i) sum_k Theta_kj P_k(i) + sum_{k: t_kl > 0} Theta_kj E_kl(i) r'_l,t_kl(i))
+ *   vjp_il         = sum_j W_ij dmean_ij/dx_l
+ * P_k, E_kl, r', rho_l and s do not depend on j: for q >= 2 one fused kernel evaluates the basis and
+ * its derivative once per 64-row tile, forms every product once and contracts it with a 4 x 16 slice
+ * of Theta on the matrix cores, responses in blocks of 16 and chunks of at most 64 per launch.  The
+ * VJP comes from the same kernel, which contracts each finished 64 x (responses of the chunk) block
+ * with the tile's rows of W before it leaves the chip: the n x d x q Jacobian is never written, not
+ * even as scratch.  q = 1 takes the kernel of obhip_predict_grad_dev and gives exactly its bits.
+ * Fused while the padded width of the terms is even and the tile of 2 Mu - 1 + d columns plus the
+ * staged block fits 160 KB of LDS; beyond that and under OBHIP_FORCE_GENERIC one
+ * obhip_predict_grad_dev pass per response (any term set it accepts), the VJP accumulated as
+ * out += W[:, j] o grad_j with one fma per entry, in response order, from n d doubles of pooled
+ * scratch.  No atomics and a fixed summation order on both paths: two calls give the same bits, and
+ * the bits of d_mean and d_jac do not depend on which optional outputs are passed.
+ * d_Theta: p x q column-major, ld = p.  d_x: n x d column-major, ld = n.  d_mean: n x q column-major,
+ * ld = n, may be NULL.  d_jac (required): jac[(j d + l) n + i] = dmean_ij/dx_l.  d_W: n x q
+ * column-major, ldw >= n (the padding is not read).  d_out (required): n x d column-major, ld = n.
+ * A null m, t, d_Theta, d_x, d_jac / d_W / d_out, q = 0, ldw < n, n > 2^40 and terms of another
+ * model's dimension count return OBHIP_ERR_INVALID before any device call; n = 0 is a no-op. */
+int obhip_predict_jac_multi_dev(const obhip_model *m, const obhip_terms *t, const double *d_Theta,
+                                uint64_t q, const double *d_x, uint64_t n, double *d_mean,
+                                double *d_jac);
+int obhip_predict_vjp_multi_dev(const obhip_model *m, const obhip_terms *t, const double *d_Theta,
+                                uint64_t q, const double *d_x, uint64_t n, const double *d_W,
+                                uint64_t ldw, double *d_mean, double *d_out);
+/* the Jacobian on host buffers: Theta p x q (ld = p), x n x d with ldx, mean n x q (ld = n, may be
+ * NULL), jac as d_jac */
+int obhip_predict_jac_multi(const obhip_model *m, const obhip_terms *t, const double *Theta,
+                            uint64_t q, const double *x, uint64_t n, uint64_t ldx, double *mean,
+                            double *jac);
 /* predr_std (loglik_std.cpp:218-256), the predictor of the loglik_std model with the full
  * posterior covariance of the coefficients: mean = B theta, var_i = b_i^T inv(H) b_i +
  * e^{2 sigma} (:249-256; the reference uses arma::inv; here H = L L^T by the library's own

@@ -10,9 +10,11 @@ from . import _lib
 from ._lib import ObhipError, device_count
 from .obmod import (covf, covf_mat25, covf_mat25ang, covf_mat25pow, gethyp, getpara, hypnames,
                     listcov, loglik_gauss, loglik_gda, loglik_std, logpr_gauss, lpdf, lpdfvec,
-                    outerbase, outermod, predict_grad, predictor, setcovfs, setknot, term_dim_views)
+                    outerbase, outermod, predict_grad, predict_jac, predict_vjp, predictor, setcovfs, setknot,
+                    term_dim_views)
 from .fitting import BFGS_lpdf, BFGS_std, obfit, obpred, obpred_grad
 from .multi import MultiFit, fit_newton_multi
+from .torch_emulator import TorchEmulator
 from .driver import HotPath, MultiHotPath
 from .stream import (CVResult, NewtonAccumulator, cv_folds, cv_newton_multi, design_dx,
                      fit_newton_grad)
@@ -26,4 +28,5 @@ __all__ = [
     "NewtonAccumulator", "cv_newton_multi", "cv_folds", "CVResult",
     "predict_grad", "obpred_grad", "term_dim_views",
     "design_dx", "fit_newton_grad",
+    "predict_jac", "predict_vjp", "TorchEmulator",
 ]

@@ -601,6 +601,11 @@ int ensure_dx_tables(const obhip_model &m, obhip_terms &t);  // after t.prepare(
 int launch_predict_dx(const obhip_model &m, obhip_terms &t, const double *d_theta, const double *d_x, uint64_t n,
                       double *d_mean, double *d_grad, const double *d_coeffvar, double e2sigma, double *d_var,
                       double *d_gradvar);
+// kernels_predict_jac.hip / predict_jac.cpp: Jacobian (d_W == nullptr, into d_jac) or vector-Jacobian
+// product (with d_W, into d_out) of the multi-response predictor; q = 1 goes to launch_predict_dx
+bool predict_jac_supports(const obhip_terms &t);
+int launch_predict_jac(const obhip_model &m, obhip_terms &t, const double *d_Theta, uint64_t q, const double *d_x,
+                       uint64_t n, double *d_mean, double *d_jac, const double *d_W, uint64_t ldw, double *d_out);
 // kernels_materialize_dx.hip / grad_obs.cpp: the derivative design matrix as rows of the normal equations
 struct DxStage {
   const double *x = nullptr;        // device, column-major with leading dimension ldx, n rows from x on

@@ -84,11 +84,22 @@ class MultiFit:
         call("obhip_destandardise_multi_dev", vq.data_ptr(), n, q, n, dms.data_ptr(), 1)
         return mean.cpu().numpy().T, vq.cpu().numpy().T
 
+    def _dev_inputs(self, xnew):
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        call("obhip_set_stream", C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        dx = torch.from_numpy(np.ascontiguousarray(xnew.T)).to(dev)          # column-major n x d
+        dth = torch.from_numpy(np.ascontiguousarray(self.coeff.T)).to(dev)   # column-major p x q
+        return dev, dx, dth
+
     def predict_grad(self, xnew, var=False):
         """De-standardised (mean n x q, grad n x d x q) at xnew, grad[i, l, j] = d mean_ij / d x_il;
-        with var=True also (var n x q, gradvar n x d x q).  One obhip_predict_grad_dev call per
-        response (a batched form is not built); the variance and its gradient are computed once, with
-        response 0, and scaled by y_sca^2 as predict does with the variance."""
+        with var=True also (var n x q, gradvar n x d x q).  The means and gradients of all q responses
+        come from one obhip_predict_jac_multi_dev call, which evaluates the basis and forms every term
+        product once; the variance and its gradient, the same for every response in standardised
+        units, come from one obhip_predict_grad_dev call with response 0 (its mean and gradient are
+        discarded, so var=True and var=False return the same mean and grad bits) and are scaled by
+        y_sca^2 as predict does with the variance."""
         import torch
         xnew = np.asarray(xnew, dtype=np.float64)
         if xnew.ndim != 2 or xnew.shape[1] != self.om.d:
@@ -97,22 +108,18 @@ class MultiFit:
         if n == 0:
             z, g = np.zeros((0, q)), np.zeros((0, d, q))
             return (z, g, z.copy(), g.copy()) if var else (z, g)
-        dev = torch.device("cuda", torch.cuda.current_device())
-        call("obhip_set_stream", C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        dx = torch.from_numpy(np.ascontiguousarray(xnew.T)).to(dev)          # column-major n x d
-        dth = torch.from_numpy(np.ascontiguousarray(self.coeff.T)).to(dev)   # column-major p x q
+        dev, dx, dth = self._dev_inputs(xnew)
         mean = torch.empty((q, n), dtype=f64, device=dev)
         grad = torch.empty((q, d, n), dtype=f64, device=dev)
-        dcv = dvar = dgv = None
+        call("obhip_predict_jac_multi_dev", self.om._h, self._t._h, dth.data_ptr(), q, dx.data_ptr(), n,
+             mean.data_ptr(), grad.data_ptr())
         if var:
             dcv = torch.from_numpy(1.0 / self.diagH).to(dev)
             dvar = torch.empty(n, dtype=f64, device=dev)
             dgv = torch.empty((d, n), dtype=f64, device=dev)
-        for j in range(q):
-            first = var and j == 0
-            call("obhip_predict_grad_dev", self.om._h, self._t._h, dth[j].data_ptr(), dx.data_ptr(), n,
-                 mean[j].data_ptr(), grad[j].data_ptr(), dcv.data_ptr() if first else None, self.sigma,
-                 dvar.data_ptr() if first else None, dgv.data_ptr() if first else None)
+            g0 = torch.empty((d, n), dtype=f64, device=dev)
+            call("obhip_predict_grad_dev", self.om._h, self._t._h, dth[0].data_ptr(), dx.data_ptr(), n,
+                 None, g0.data_ptr(), dcv.data_ptr(), self.sigma, dvar.data_ptr(), dgv.data_ptr())
         sca = torch.from_numpy(self.y_sca).to(dev)
         cent = torch.from_numpy(self.y_cent).to(dev)
         mean = mean * sca[:, None] + cent[:, None]
@@ -123,6 +130,32 @@ class MultiFit:
         s2 = sca * sca
         return out + ((dvar[None, :] * s2[:, None]).cpu().numpy().T,
                       (dgv[None, :, :] * s2[:, None, None]).permute(2, 1, 0).cpu().numpy())
+
+    def vjp(self, xnew, cot):
+        """sum_j cot[i, j] d mean_ij / d x_il (n x d) of the de-standardised means: the backward pass of
+        predict for the cotangent cot (n x q, raw units), scaled by y_sca per response and sent through
+        obhip_predict_vjp_multi_dev; the n x d x q Jacobian is never formed."""
+        import torch
+        xnew = np.asarray(xnew, dtype=np.float64)
+        if xnew.ndim != 2 or xnew.shape[1] != self.om.d:
+            raise ValueError("xnew must be n x d")
+        cot = np.asarray(cot, dtype=np.float64)
+        n, q, d = xnew.shape[0], self.q, self.om.d
+        if cot.shape != (n, q):
+            raise ValueError("cot must be n x q")
+        if n == 0:
+            return np.zeros((0, d))
+        dev, dx, dth = self._dev_inputs(xnew)
+        dw = torch.from_numpy(np.ascontiguousarray(cot.T)).to(dev) * torch.from_numpy(self.y_sca).to(dev)[:, None]
+        out = torch.empty((d, n), dtype=torch.float64, device=dev)
+        call("obhip_predict_vjp_multi_dev", self.om._h, self._t._h, dth.data_ptr(), q, dx.data_ptr(), n,
+             dw.data_ptr(), n, None, out.data_ptr())
+        return out.cpu().numpy().T
+
+    def torch(self):
+        """a differentiable torch module of the de-standardised predictor (torch_emulator.TorchEmulator)"""
+        from .torch_emulator import TorchEmulator
+        return TorchEmulator(self)
 
 
 def fit_newton_multi(om, terms, x, Y, sigma=None, rho=DEFAULT_RHO, comm=None):

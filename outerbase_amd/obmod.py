@@ -770,6 +770,56 @@ def predict_grad(om, terms, coeff, xnew, coeffvar=None, sigma=None):
     return (mean, grad) if cv is None else (mean, grad, var, gradvar)
 
 
+def _check_multi(om, t, Theta, xnew):
+    x = np.asarray(xnew, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] != om.d:
+        raise ValueError("xnew must be n x d")
+    Theta = np.asarray(Theta, dtype=np.float64)
+    if Theta.ndim != 2 or Theta.shape[0] != t.p or Theta.shape[1] == 0:
+        raise ValueError("Theta must be p x q with one row per term and at least one column")
+    return x, Theta
+
+
+def predict_jac(om, terms, Theta, xnew):
+    """(mean, jac) of q responses with the coefficients Theta (p x q) at the rows xnew (n x d):
+    mean = B(x) Theta (n x q) and jac[i, l, j] = d mean_ij / d x_il (n x d x q), from one fused kernel
+    that evaluates the basis and forms every product once (obhip_predict_jac_multi_dev)."""
+    t = _terms_of(om, terms)
+    x, Theta = _check_multi(om, t, Theta, xnew)
+    n, q, d = x.shape[0], Theta.shape[1], om.d
+    if n == 0:
+        return np.zeros((0, q)), np.zeros((0, d, q))
+    x, Theta = np.asfortranarray(x), np.asfortranarray(Theta)   # held until the call returns: ptr is an address
+    mean, jac = np.empty((q, n)), np.empty((q, d, n))
+    call("obhip_predict_jac_multi", om._h, t._h, ptr(Theta), q, ptr(x), n, max(n, 1), ptr(mean), ptr(jac))
+    return mean.T, jac.transpose(2, 1, 0)
+
+
+def predict_vjp(om, terms, Theta, xnew, W):
+    """(mean, out) with out[i, l] = sum_j W[i, j] d mean_ij / d x_il (n x d): the vector-Jacobian product
+    of predict_jac with the weights W (n x q), the backward pass of the predictor.  The Jacobian is
+    never formed (obhip_predict_vjp_multi_dev)."""
+    t = _terms_of(om, terms)
+    x, Theta = _check_multi(om, t, Theta, xnew)
+    W = np.asarray(W, dtype=np.float64)
+    n, q, d = x.shape[0], Theta.shape[1], om.d
+    if W.shape != (n, q):
+        raise ValueError("W must be n x q")
+    if n == 0:
+        return np.zeros((0, q)), np.zeros((0, d))
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    call("obhip_set_stream", C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    dx = torch.from_numpy(np.ascontiguousarray(x.T)).to(dev)          # column-major n x d
+    dth = torch.from_numpy(np.ascontiguousarray(Theta.T)).to(dev)     # column-major p x q
+    dw = torch.from_numpy(np.ascontiguousarray(W.T)).to(dev)          # column-major n x q
+    mean = torch.empty((q, n), dtype=torch.float64, device=dev)
+    out = torch.empty((d, n), dtype=torch.float64, device=dev)
+    call("obhip_predict_vjp_multi_dev", om._h, t._h, dth.data_ptr(), q, dx.data_ptr(), n, dw.data_ptr(), n,
+         mean.data_ptr(), out.data_ptr())
+    return mean.cpu().numpy().T, out.cpu().numpy().T
+
+
 def term_dim_views(om, terms):
     """per dimension the indices of the terms that have it at a level > 0, in term order: the lists
     the gradient kernel sums over (obhip_terms_dimview; host only)"""

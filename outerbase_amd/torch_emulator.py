@@ -1,0 +1,70 @@
+"""The multi-response predictor as a differentiable torch module.
+
+A multi-output emulator is used for calibration and optimisation over its inputs: a scalar loss of
+all q outputs is differentiated by x.  TorchEmulator wraps a MultiFit so that it can sit inside a
+torch.optim loop: forward is obhip_predict_multi_dev, backward the vector-Jacobian product
+obhip_predict_vjp_multi_dev (include/obhip.h), both on the current stream; the n x d x q Jacobian
+is never formed.  All arithmetic is in libobhip; torch holds the memory and the graph.
+"""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import call, torch
+
+if torch is None:  # host-only use of the package: the name exists, building one needs torch
+    class TorchEmulator:
+        def __init__(self, *args, **kwargs):
+            raise ImportError("TorchEmulator needs torch")
+else:
+    def _colmajor(a):
+        """the (rows, cols) tensor a as a contiguous (cols, rows) tensor: column-major storage of a"""
+        return a.detach().t().contiguous()
+
+    class _Predict(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, emu):
+            n, q = x.shape[0], emu.q
+            xc = _colmajor(x)
+            mean = torch.empty((q, n), dtype=torch.float64, device=x.device)
+            if n > 0:
+                call("obhip_set_stream", C.c_void_p(torch.cuda.current_stream().cuda_stream))
+                call("obhip_predict_multi_dev", emu._om._h, emu._t._h, emu.theta.data_ptr(), q, xc.data_ptr(), n,
+                     mean.data_ptr(), None, emu._sigma, None)
+            ctx.emu, ctx.xc = emu, xc
+            return (mean * emu.y_sca[:, None] + emu.y_cent[:, None]).t()
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad_output):
+            emu, xc = ctx.emu, ctx.xc
+            d, n = xc.shape
+            out = torch.zeros((d, n), dtype=torch.float64, device=xc.device)
+            if n > 0:
+                w = (grad_output.detach().to(torch.float64) * emu.y_sca[None, :]).t().contiguous()   # n x q column-major
+                call("obhip_set_stream", C.c_void_p(torch.cuda.current_stream().cuda_stream))
+                call("obhip_predict_vjp_multi_dev", emu._om._h, emu._t._h, emu.theta.data_ptr(), emu.q, xc.data_ptr(),
+                     n, w.data_ptr(), n, None, out.data_ptr())
+            return out.t(), None
+
+    class TorchEmulator(torch.nn.Module):
+        """forward(x): (n, d) float64 tensor on the current GPU -> (n, q) de-standardised means, differentiable
+        by x (once: no double backward).  Theta, y_cent and y_sca are device buffers uploaded once."""
+
+        def __init__(self, fit):
+            super().__init__()
+            self._om, self._t, self._sigma = fit.om, fit._t, float(fit.sigma)
+            self.q, self.d = int(fit.q), int(fit.om.d)
+            dev = torch.device("cuda", torch.cuda.current_device())
+            self.register_buffer("theta", torch.from_numpy(np.ascontiguousarray(fit.coeff.T)).to(dev))  # p x q column-major
+            self.register_buffer("y_cent", torch.from_numpy(np.ascontiguousarray(fit.y_cent)).to(dev))
+            self.register_buffer("y_sca", torch.from_numpy(np.ascontiguousarray(fit.y_sca)).to(dev))
+
+        def forward(self, x):
+            if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float64:
+                raise TypeError("TorchEmulator takes a float64 tensor on the GPU")
+            if x.dim() != 2 or x.shape[1] != self.d:
+                raise ValueError("x must be n x d")
+            if x.device != self.theta.device:
+                raise ValueError("x is on another device than the emulator")
+            return _Predict.apply(x, self)
