@@ -96,24 +96,24 @@ struct StoreGlobal {
     base[(size_t)ccol * kTileRows] = v;
   }
 };
-struct StoreLds {
-  double *lds;      // [used column][64]
+// the same into a [used column][PITCH] tile (64, or 65 where lanes read different columns at one
+// row), lane = row.  The derivative builders (device_dx.h) also write, behind the Mu value columns,
+// the derivative column of every used column >= 1 and behind those one column of rho per dimension.
+template <int PITCH>
+struct StoreTile {
+  double *tile;
   const int *cpos;  // compact column -> used column or -1
-  int lane;
-  __device__ __forceinline__ void operator()(int ccol, double v) const {
+  int lane, Mu;
+  __device__ __forceinline__ void val(int ccol, double v) const {
     const int u = cpos[ccol];
-    if (u >= 0) lds[u * kTileRows + lane] = v;
+    if (u >= 0) tile[u * PITCH + lane] = v;
   }
-};
-
-struct StoreLdsPitch {  // the same into a [used column][65] tile (term-per-lane kernels)
-  double *lds;
-  const int *cpos;
-  int lane;
-  __device__ __forceinline__ void operator()(int ccol, double v) const {
+  __device__ __forceinline__ void operator()(int ccol, double v) const { val(ccol, v); }
+  __device__ __forceinline__ void der(int ccol, double v) const {
     const int u = cpos[ccol];
-    if (u >= 0) lds[u * 65 + lane] = v;
+    if (u >= 0) tile[(Mu + u - 1) * PITCH + lane] = v;
   }
+  __device__ __forceinline__ void rho(int l, double v) const { tile[(2 * Mu - 1 + l) * PITCH + lane] = v; }
 };
 
 // R = cov(x, knots) . rotmat for one row and one dimension; levels >= 1 are
@@ -138,20 +138,23 @@ __device__ __forceinline__ double build_dim(const DimDesc &D, const double *ka, 
   return cl;
 }
 
-// mat25 / mat25pow from the interval tables (ModelDev::build, core.cpp): J = number of knots with
-// u_j <= u(x) by bisection on the sorted u, t = u(x) - u_(J-1), and per level six table entries:
-//   R[c] = e^{-t} (A0 + t (A1 + t A2)) + e^{+t} (B0 + t (t B2 - B1)).
-// O(1) per (row, level) where the knot loop spends ~17 instructions per (row, knot); two
-// exponentials per (row, dimension) as before.  No knots below (J = 0): the e^{-t} part is empty
-// and e^{-t} may overflow (t < 0), so it is dropped; likewise e^{+t} for J = m.
-template <int KIND, typename Store>
-__device__ __forceinline__ double build_dim_tab(const DimDesc &D, const double *__restrict__ tab,
-                                                double xv, const Store &store) {
-  typedef double dd2 __attribute__((ext_vector_type(2)));
-  const double ux = (KIND == OBHIP_COV_MAT25 ? xv / D.p0 : pow(xv, D.p0) / D.p1) - D.p2;
-  const double *__restrict__ us = tab + D.tab;
-  int J;
-  double uref;  // u_(J-1) (u_(0) for J = 0)
+// ---- interval search of the tables ------------------------------------------------------------
+// number of the m sorted us that are <= ux (NaN: 0), m <= 127: seven steps
+__device__ __forceinline__ int tab_bisect(const double *__restrict__ us, int m, double ux) {
+  int lo = 0, hi = m;  // u_(lo-1) <= ux < u_(hi)
+  for (int it = 0; it < 7; ++it) {
+    const int mid = (lo + hi) >> 1;
+    const bool open = lo < hi;
+    const bool le = us[min(mid, m - 1)] <= ux;
+    lo = open && le ? mid + 1 : lo;
+    hi = open && !le ? mid : hi;
+  }
+  return lo;
+}
+
+// J = number of the dimension's sorted knots us with u_j <= ux, uref = u_(J-1) (u_(0) for J = 0)
+__device__ __forceinline__ void tab_locate(const DimDesc &D, const double *__restrict__ us, double ux, int &J,
+                                           double &uref) {
   if (D.gwin > 0) {
     // (nearly) equidistant knots: the host has checked that the guess is within gwin - 1 of J for
     // every u (ModelDev::build), so J = (knots below the window) + (knots of the window <= u):
@@ -176,17 +179,26 @@ __device__ __forceinline__ double build_dim_tab(const DimDesc &D, const double *
     const int kr = max(J - 1, 0) - (J0 - 2);  // 0 .. 3
     uref = kr <= 1 ? (kr == 0 ? wv[0] : wv[1]) : (kr == 2 ? wv[2] : wv[3]);
   } else {
-    int lo = 0, hi = D.m;  // u_(lo-1) <= ux < u_(hi)
-    for (int it = 0; it < 7; ++it) {  // m <= 127
-      const int mid = (lo + hi) >> 1;
-      const bool open = lo < hi;
-      const bool le = us[min(mid, D.m - 1)] <= ux;
-      lo = open && le ? mid + 1 : lo;
-      hi = open && !le ? mid : hi;
-    }
-    J = lo;
+    J = tab_bisect(us, D.m, ux);
     uref = us[max(J - 1, 0)];
   }
+}
+
+// mat25 / mat25pow from the interval tables (ModelDev::build, core.cpp): J = number of knots with
+// u_j <= u(x) by bisection on the sorted u, t = u(x) - u_(J-1), and per level six table entries:
+//   R[c] = e^{-t} (A0 + t (A1 + t A2)) + e^{+t} (B0 + t (t B2 - B1)).
+// O(1) per (row, level) where the knot loop spends ~17 instructions per (row, knot); two
+// exponentials per (row, dimension) as before.  No knots below (J = 0): the e^{-t} part is empty
+// and e^{-t} may overflow (t < 0), so it is dropped; likewise e^{+t} for J = m.
+template <int KIND, typename Store>
+__device__ __forceinline__ double build_dim_tab(const DimDesc &D, const double *__restrict__ tab,
+                                                double xv, const Store &store) {
+  typedef double dd2 __attribute__((ext_vector_type(2)));
+  const double ux = (KIND == OBHIP_COV_MAT25 ? xv / D.p0 : pow(xv, D.p0) / D.p1) - D.p2;
+  const double *__restrict__ us = tab + D.tab;
+  int J;
+  double uref;
+  tab_locate(D, us, ux, J, uref);
   const double t = ux - uref;
   const double em = J == 0 ? 0.0 : exp(-t), ep = J == D.m ? 0.0 : exp(t);
   const dd2 *__restrict__ cf = (const dd2 *)(us + ((D.m + 1) & ~1) + (size_t)J * D.ncol * 6);

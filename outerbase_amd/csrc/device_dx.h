@@ -1,13 +1,17 @@
-// Derivative twins of build_dim / build_dim_tab / build_dim_any (device_common.h): one dimension
-// of the basis AND of its derivative by that dimension's input, for one row.  No reference
-// counterpart (the reference has no input gradients); the formulas are those of include/obhip.h
-// at obhip_predict_grad_dev.
+// What the predictors share on the device beyond device_common.h.
 //
-// With R = cov(x, knots) . rotmat and R' = (dcov/dx) . rotmat a dimension hands over
-//   r_t  = R_t / R_0                       t >= 1   store.val(compact column, .)
-//   r'_t = (R'_t - r_t R'_0) / R_0         t >= 1   store.der(compact column, .)
-//   R_0  (returned)   and   rho = R'_0 / R_0.
-// The value side repeats build_dim* operation for operation; those functions are not edited.
+// 1. The derivative twins of build_dim / build_dim_tab / build_dim_any: one dimension of the basis
+//    AND of its derivative by that dimension's input, for one row.  No reference counterpart (the
+//    reference has no input gradients); the formulas are those of include/obhip.h at
+//    obhip_predict_grad_dev.  With R = cov(x, knots) . rotmat and R' = (dcov/dx) . rotmat a
+//    dimension hands over
+//      r_t  = R_t / R_0                       t >= 1   store.val(compact column, .)
+//      r'_t = (R'_t - r_t R'_0) / R_0         t >= 1   store.der(compact column, .)
+//      R_0  (returned)   and   rho = R'_0 / R_0.
+//    The value side follows build_dim* operation for operation; the interval search is the one
+//    function both call (tab_locate).
+// 2. Phase 1 of every fused predictor (build_tile, tile_scale): the basis -- with or without its
+//    derivative -- at the 64 rows of a tile, written into the tile by the waves of the block.
 #pragma once
 #include "device_common.h"
 
@@ -114,34 +118,7 @@ __device__ __forceinline__ double build_dim_tab_dx(const DimDesc &D, const doubl
   const double *__restrict__ us = tab + D.tab;
   int J;
   double uref;
-  if (D.gwin > 0) {  // (as build_dim_tab)
-    double q = floor((ux - D.g0) * D.ginv) + 1.0;
-    q = fmin(fmax(q, 0.0), (double)D.m);
-    const int J0 = (int)q, w0 = max(J0 - 2, 0);
-    double wv[4];
-    int cnt = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int idx = J0 - 2 + k;
-      const bool in = idx >= 0 && idx < D.m;
-      wv[k] = us[min(max(idx, 0), D.m - 1)];
-      cnt += in && wv[k] <= ux ? 1 : 0;
-    }
-    J = w0 + cnt;
-    const int kr = max(J - 1, 0) - (J0 - 2);
-    uref = kr <= 1 ? (kr == 0 ? wv[0] : wv[1]) : (kr == 2 ? wv[2] : wv[3]);
-  } else {
-    int lo = 0, hi = D.m;
-    for (int it = 0; it < 7; ++it) {
-      const int mid = (lo + hi) >> 1;
-      const bool open = lo < hi;
-      const bool le = us[min(mid, D.m - 1)] <= ux;
-      lo = open && le ? mid + 1 : lo;
-      hi = open && !le ? mid : hi;
-    }
-    J = lo;
-    uref = us[max(J - 1, 0)];
-  }
+  tab_locate(D, us, ux, J, uref);
   const double t = ux - uref;
   const double em = J == 0 ? 0.0 : exp(-t), ep = J == D.m ? 0.0 : exp(t);
   const size_t eoff = (size_t)D.tab + ((D.m + 1) & ~1) + (size_t)J * D.ncol * 6;
@@ -183,6 +160,44 @@ __device__ __forceinline__ double build_dim_dx_any(const DimDesc &D, const doubl
   if (D.kind == kCovMat25PowDirect)
     return build_dim_dx<kCovMat25PowDirect>(D, ka, kb, kc, rot, xv, store, rho);
   return build_dim_dx<OBHIP_COV_MAT25ANG>(D, ka, kb, kc, rot, xv, store, rho);
+}
+
+// ---- phase 1 of the fused predictors: one 64-row tile of the basis -------------------------------
+// lane = row; wave w of WAVES takes the dimensions w, w + WAVES, ... and writes their used columns
+// through `store` (DX: also their derivative columns and the column rho_l; dtab is not read
+// otherwise), wave 0 the ones column.  Rows beyond the input (valid false) are evaluated at 0.5 instead.
+// The wave's share of the row scale (the product of its dimensions' level 0) goes to part[wave][64];
+// after a barrier tile_scale gives the row's scale.  x is column-major with leading dimension ldx.
+template <int WAVES, bool DX, int PITCH>
+__device__ __forceinline__ void build_tile(const DimDesc *__restrict__ dims, const double *__restrict__ ka,
+                                           const double *__restrict__ kb, const double *__restrict__ kc,
+                                           const double *__restrict__ rot, const double *__restrict__ tab,
+                                           const double *__restrict__ dtab, int d, const double *__restrict__ x,
+                                           uint64_t ldx, uint64_t row, bool valid, int wave,
+                                           const StoreTile<PITCH> &store, double *part) {
+  double sc = 1.0;
+  for (int l = wave; l < d; l += WAVES) {
+    const DimDesc D = dims[l];
+    const double xv = valid ? x[(uint64_t)l * ldx + row] : 0.5;
+    if constexpr (DX) {
+      double rho;
+      sc *= build_dim_dx_any(D, ka, kb, kc, rot, tab, dtab, xv, store, rho);
+      store.rho(l, rho);
+    } else {
+      sc *= build_dim_any(D, ka, kb, kc, rot, tab, xv, store);
+    }
+  }
+  if (wave == 0) store.tile[store.lane] = 1.0;  // used column 0 = all ones
+  part[wave * kTileRows + store.lane] = sc;
+}
+
+// the row scale of this lane's row: the waves' shares multiplied in wave order
+template <int WAVES>
+__device__ __forceinline__ double tile_scale(const double *part, int lane) {
+  double s = 1.0;
+#pragma unroll
+  for (int q = 0; q < WAVES; ++q) s *= part[q * kTileRows + lane];
+  return s;
 }
 
 }  // namespace obhip

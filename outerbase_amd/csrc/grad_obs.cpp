@@ -33,12 +33,7 @@ int check_grad_dims(const char *who, uint64_t d, const uint32_t *dims, uint64_t 
 }
 
 int ensure_dx_stage(const obhip_model &m, obhip_terms &t) {
-  if (t.pred_model != &m || t.pred_md.model_version != m.version) {
-    OB_TRY(t.pred_md.build(m, t.maxlev));
-    t.pred_model = &m;
-  }
-  OB_TRY(t.prepare(t.pred_md.cap, t.pred_md.dims_h));
-  OB_TRY(ensure_dx_tables(m, t));
+  OB_TRY(prepare_predict(m, t, true));
   obhip_terms::Dx &dx = t.dx;
   if (dx.udim.p && dx.udim_cap == t.cached_cap) return 0;
   std::vector<int32_t> h(t.Mu, -1);

@@ -167,16 +167,8 @@ template <int KIND>
 __device__ __forceinline__ GradRow grad_row(const DimDesc &D, const double *__restrict__ tab, double xv) {
   constexpr bool POW = KIND == OBHIP_COV_MAT25POW;
   const double ux = (POW ? pow(xv, D.p0) / D.p1 : xv / D.p0) - D.p2;
-  int lo = 0, hi = D.m;  // u_(lo-1) <= ux < u_(hi)
-  for (int it = 0; it < 7; ++it) {  // m <= 127
-    const int mid = (lo + hi) >> 1;
-    const bool open = lo < hi;
-    const bool le = tab[min(mid, D.m - 1)] <= ux;
-    lo = open && le ? mid + 1 : lo;
-    hi = open && !le ? mid : hi;
-  }
   GradRow g;
-  g.J = lo;
+  g.J = tab_bisect(tab, D.m, ux);
   g.t = ux - tab[max(g.J - 1, 0)];
   g.em = g.J == 0 ? 0.0 : exp(-g.t);
   g.ep = g.J == D.m ? 0.0 : exp(g.t);

@@ -34,25 +34,7 @@ namespace {
 constexpr int kMdThreads = 512, kMdWaves = kMdThreads / 64;
 constexpr int kMdPitch = 65;  // doubles between the columns of the LDS tile
 
-struct StoreMd {
-  double *tile;     // [column][pitch]
-  const int *cpos;  // compact column -> used column or -1
-  int lane, Mu, pitch;
-  __device__ __forceinline__ void val(int ccol, double v) const {
-    const int u = cpos[ccol];
-    if (u >= 0) tile[u * pitch + lane] = v;
-  }
-  __device__ __forceinline__ void der(int ccol, double v) const {
-    const int u = cpos[ccol];
-    if (u >= 0) tile[(Mu + u - 1) * pitch + lane] = v;
-  }
-};
-
-struct MdArgs {
-  const DimDesc *dims;
-  const double *ka, *kb, *kc, *rot, *tab, *dtab;
-  const int *cpos;
-  int d, Mu;
+struct MdArgs : PredTabs {
   const uint32_t *colsw;  // p_pad x W2rt words of two used-column indices
   int W2rt;
   const int *udim;        // used column -> its dimension (-1: the ones column)
@@ -107,28 +89,25 @@ __global__ void __launch_bounds__(kMdThreads) k_materialize_dx(const MdArgs a) {
     const bool valid = row < a.n;
     // ---- 1. basis, derivative basis and rho at the rows of the tile (lane = row) ----
     {
+      // (build_tile's loop, kept here: through the builder the HBM instantiation takes one VGPR more, 169,
+      // and with it drops below three waves per SIMD -- DESIGN §16)
       double sc = 1.0;
-      const StoreMd store{tile, a.cpos, lane, Mu, TP};
+      const StoreTile<TP> store{tile, a.cpos, lane, Mu};
       for (int l = wave; l < d; l += kMdWaves) {
         const DimDesc D = a.dims[l];
         const double xv = valid ? a.x[(uint64_t)l * a.ldx + row] : 0.5;
         double rho;
         sc *= build_dim_dx_any(D, a.ka, a.kb, a.kc, a.rot, a.tab, a.dtab, xv, store, rho);
-        tile[(2 * Mu - 1 + l) * TP + lane] = rho;
+        store.rho(l, rho);
       }
-      if (wave == 0) tile[lane] = 1.0;  // used column 0 = all ones
+      if (wave == 0) tile[lane] = 1.0;  // (the ones column)
       red[wave * kTileRows + lane] = sc;
       if (a.g)
         for (int li = wave; li < L; li += kMdWaves)
           gs[li * kTileRows + lane] = valid ? a.sqw[li] * a.g[(uint64_t)li * a.ldg + row] : 0.0;
     }
     __syncthreads();
-    if (wave == 0) {
-      double s = 1.0;
-#pragma unroll
-      for (int q = 0; q < kMdWaves; ++q) s *= red[q * kTileRows + lane];
-      srow[lane] = valid ? s : 0.0;
-    }
+    if (wave == 0) srow[lane] = valid ? tile_scale<kMdWaves>(red, lane) : 0.0;
     __syncthreads();
 
     // ---- 2. lane = two adjacent terms ----
@@ -280,16 +259,11 @@ int run_materialize_dx(const obhip_model &m, obhip_terms &t, const DxStage &s) {
   uint64_t nblk = std::min<uint64_t>(ntiles, (uint64_t)device_cus(dev) * 2);
   DevBuf<double> scratch;
   if (HBM) {
-    const uint64_t per = ncols * kTileRows * sizeof(double);
-    nblk = std::max<uint64_t>(1, std::min<uint64_t>(nblk, (1ull << 30) / per));
+    nblk = hbm_tile_blocks(nblk, ncols);
     OB_TRY(scratch.alloc(nblk * ncols * kTileRows));
   }
   MdArgs a;
-  a.dims = t.pred_md.dims.p;
-  a.ka = t.pred_md.ka.p, a.kb = t.pred_md.kb.p, a.kc = t.pred_md.kc.p;
-  a.rot = t.pred_md.rot.p, a.tab = t.pred_md.tab.p, a.dtab = t.dx.dtab.p;
-  a.cpos = t.cpos.p;
-  a.d = (int)m.d, a.Mu = (int)t.Mu;
+  static_cast<PredTabs &>(a) = pred_tabs(m, t);
   a.colsw = (const uint32_t *)t.cols.p;
   a.W2rt = (int)(t.W / 2);
   a.udim = t.dx.udim.p;
@@ -312,11 +286,11 @@ int run_materialize_dx(const obhip_model &m, obhip_terms &t, const DxStage &s) {
 
 }  // namespace
 
-// the fused kernel's domain: at most 8 factors per term and a tile that fits 160 KB of LDS
+// the fused kernel's domain: at most 8 factors per term and a tile that fits the LDS
 bool materialize_dx_supports(const obhip_terms &t) {
   const uint64_t w2 = t.W / 2;
   return w2 >= 1 && w2 <= 4 &&
-         ((2 * t.Mu - 1 + t.d) * kMdPitch + md_aux_doubles((int)t.d)) * sizeof(double) <= 160 * 1024;
+         ((2 * t.Mu - 1 + t.d) * kMdPitch + md_aux_doubles((int)t.d)) * sizeof(double) <= kLdsBudget;
 }
 
 // after ensure_dx_stage(m, t); s.n >= 1

@@ -16,7 +16,7 @@
 // MFMA operand layout (as in kernels_chol.hip): lane = (m | n) + 16 k for A[m][k] and B[k][n];
 // the four accumulator registers of a lane are D[k + 4 r][n], r = 0..3.
 #include "obhip_internal.h"
-#include "device_common.h"
+#include "device_dx.h"
 #include "vec_ops.h"
 
 namespace obhip {
@@ -320,23 +320,11 @@ k_predict_multi(const DimDesc *__restrict__ dims, const double *__restrict__ ka,
   {
     const uint64_t row = row0 + lane;
     const bool valid = row < n;
-    double sc = 1.0;
-    const StoreLds store{lds, cpos, lane};
-    for (int l = wave; l < d; l += kPmWaves) {
-      const DimDesc D = dims[l];
-      const double xv = valid ? x[(uint64_t)l * n + row] : 0.5;
-      sc *= build_dim_any(D, ka, kb, kc, rot, tab, xv, store);
-    }
-    if (wave == 0) lds[lane] = 1.0;  // used column 0 = all ones
-    reds[wave * kTileRows + lane] = sc;
+    const StoreTile<kTileRows> store{lds, cpos, lane, Mu};
+    build_tile<kPmWaves, false>(dims, ka, kb, kc, rot, tab, nullptr, d, x, n, row, valid, wave, store, reds);
   }
   __syncthreads();
-  if (wave == 0) {
-    double s = 1.0;
-#pragma unroll
-    for (int w = 0; w < kPmWaves; ++w) s *= reds[w * kTileRows + lane];
-    scl[lane] = s;
-  }
+  if (wave == 0) scl[lane] = tile_scale<kPmWaves>(reds, lane);
   const int m = lane & 15, kq = lane >> 4;
   const int rg = wave & 3, half = wave >> 2;
   const int trow = 16 * rg + m;
@@ -393,10 +381,9 @@ int run_predict_multi(const obhip_model &m, obhip_terms &t, const double *d_ThT,
   int tile = 0;
   const size_t lds = predict_multi_lds(t.Mu, NQB, &tile);
   OB_TRY(ensure_dyn_lds((const void *)k_predict_multi<NQB>, lds));
-  hipLaunchKernelGGL(k_predict_multi<NQB>, dim3((unsigned)((n + kTileRows - 1) / kTileRows)), dim3(kPmThreads),
-                     lds, cur_stream(), t.pred_md.dims.p, t.pred_md.ka.p, t.pred_md.kb.p, t.pred_md.kc.p,
-                     t.pred_md.rot.p, t.pred_md.tab.p, t.cpos.p, (int)m.d, (int)t.Mu, tile,
-                     (const uint32_t *)t.cols.p, (int)(t.W / 2), (int)t.p, d_ThT, qc, d_x, n, d_mean, ldm);
+  launch_pred<false>(k_predict_multi<NQB>, dim3((unsigned)((n + kTileRows - 1) / kTileRows)), dim3(kPmThreads), lds,
+                     pred_tabs(m, t), tile, (const uint32_t *)t.cols.p, (int)(t.W / 2), (int)t.p, d_ThT, qc, d_x, n,
+                     d_mean, ldm);
   OB_HIP(hipGetLastError());
   return 0;
 }
@@ -409,8 +396,6 @@ int run_aty(const double *B, uint64_t ldb, uint64_t n, const double *Y, uint64_t
   OB_HIP(hipGetLastError());
   return 0;
 }
-
-constexpr size_t kLdsLimit = 160 * 1024;
 
 }  // namespace
 
@@ -480,7 +465,14 @@ int launch_trsm_multi(uint64_t p64, const double *d_L, const double *d_Iinv, con
 // column lists from HBM: any number of factors per term, Mu bounded by the 160 KB of LDS.
 bool predict_multi_supports(const obhip_terms &t) {
   int tile = 0;
-  return t.W >= 2 && t.W % 2 == 0 && predict_multi_lds(t.Mu, 1, &tile) <= kLdsLimit && !getenv("OBHIP_FORCE_GENERIC");
+  return t.W >= 2 && t.W % 2 == 0 && predict_multi_lds(t.Mu, 1, &tile) <= kLdsBudget && !getenv("OBHIP_FORCE_GENERIC");
+}
+
+int launch_theta_term_major(const double *d_Theta, uint64_t p, int qc, uint64_t qw, double *d_T) {
+  return vmap(p * qw, [=] __device__(uint64_t i) {
+    const uint64_t k = i / qw, j = i % qw;
+    d_T[i] = j < (uint64_t)qc ? d_Theta[j * p + k] : 0.0;
+  });
 }
 
 // d_mean (n x q, leading dimension n): column j = B(x) Theta[:, j]; the terms are prepared
@@ -490,25 +482,18 @@ int launch_predict_multi(const obhip_model &m, obhip_terms &t, const double *d_T
   const uint64_t p = t.p;
   int tile = 0;
   int nqb_max = 4;
-  while (nqb_max > 1 && predict_multi_lds(t.Mu, nqb_max, &tile) > kLdsLimit) nqb_max /= 2;
+  while (nqb_max > 1 && predict_multi_lds(t.Mu, nqb_max, &tile) > kLdsBudget) nqb_max /= 2;
   DevBuf<double> tht;
   OB_TRY(tht.alloc(p * 16 * nqb_max));
   for (uint64_t q0 = 0; q0 < q; q0 += 16 * (uint64_t)nqb_max) {
     const int qc = (int)std::min<uint64_t>(16 * (uint64_t)nqb_max, q - q0);
     int nqb = 1;
     while (16 * nqb < qc) nqb *= 2;
-    const int qw = 16 * nqb;
-    double *T = tht.p;
-    const double *Th = d_Theta + q0 * p;
-    // term-major copy of the chunk, zero beyond its columns
-    OB_TRY(vmap(p * qw, [=] __device__(uint64_t i) {
-      const uint64_t k = i / qw, j = i % qw;
-      T[i] = j < (uint64_t)qc ? Th[j * p + k] : 0.0;
-    }));
+    OB_TRY(launch_theta_term_major(d_Theta + q0 * p, p, qc, 16 * (uint64_t)nqb, tht.p));
     double *out = d_mean + q0 * n;
-    if (nqb == 1) OB_TRY(run_predict_multi<1>(m, t, T, qc, d_x, n, out, n));
-    if (nqb == 2) OB_TRY(run_predict_multi<2>(m, t, T, qc, d_x, n, out, n));
-    if (nqb == 4) OB_TRY(run_predict_multi<4>(m, t, T, qc, d_x, n, out, n));
+    if (nqb == 1) OB_TRY(run_predict_multi<1>(m, t, tht.p, qc, d_x, n, out, n));
+    if (nqb == 2) OB_TRY(run_predict_multi<2>(m, t, tht.p, qc, d_x, n, out, n));
+    if (nqb == 4) OB_TRY(run_predict_multi<4>(m, t, tht.p, qc, d_x, n, out, n));
   }
   return 0;
 }

@@ -9,7 +9,7 @@
 // one barrier the 8 waves split the terms in groups of 64 with register-resident
 // term tables, exactly as k_mm does.
 #include "obhip_internal.h"
-#include "device_common.h"
+#include "device_dx.h"
 
 namespace obhip {
 
@@ -34,19 +34,10 @@ k_predict(const DimDesc *__restrict__ dims, const double *__restrict__ ka,
   const uint64_t row = (uint64_t)blockIdx.x * kTileRows + lane;
   const bool valid = row < n;
 
-  double sc = 1.0;
-  const StoreLds store{lds, cpos, lane};
-  for (int l = wave; l < d; l += kPrWaves) {
-    const DimDesc D = dims[l];
-    const double xv = valid ? x[(uint64_t)l * n + row] : 0.5;
-    sc *= build_dim_any(D, ka, kb, kc, rot, tab, xv, store);
-  }
-  if (wave == 0) lds[lane] = 1.0;  // used column 0 = all ones
-  red[wave * kTileRows + lane] = sc;
+  const StoreTile<kTileRows> store{lds, cpos, lane, Mu};
+  build_tile<kPrWaves, false>(dims, ka, kb, kc, rot, tab, nullptr, d, x, n, row, valid, wave, store, red);
   __syncthreads();
-  double s = 1.0;
-#pragma unroll
-  for (int q = 0; q < kPrWaves; ++q) s *= red[q * kTileRows + lane];
+  const double s = tile_scale<kPrWaves>(red, lane);
   __syncthreads();
 
   double am = 0.0, av = 0.0;
@@ -199,29 +190,17 @@ k_predict_tl(const DimDesc *__restrict__ dims, const double *__restrict__ ka,
     }
   };
 
-  const StoreLdsPitch store{lds, cpos, lane};
+  const StoreTile<kTlPitch> store{lds, cpos, lane, Mu};
   for (uint64_t tile = t0; tile < t1; ++tile) {
     __syncthreads();  // the previous tile's partials are complete, its LDS tile is free
     if (tile > t0 && wave == 0) emit(tile - 1, s_cur);
     {  // basis at the new rows, lane = row
       const uint64_t row = tile * kTileRows + lane;
       const bool valid = row < n;
-      double sc = 1.0;
-      for (int l = wave; l < d; l += kTlWaves) {
-        const DimDesc D = dims[l];
-        const double xv = valid ? x[(uint64_t)l * n + row] : 0.5;
-        sc *= build_dim_any(D, ka, kb, kc, rot, tab, xv, store);
-      }
-      if (wave == 0) lds[lane] = 1.0;  // used column 0 = all ones
-      reds[wave * kTileRows + lane] = sc;
+      build_tile<kTlWaves, false>(dims, ka, kb, kc, rot, tab, nullptr, d, x, n, row, valid, wave, store, reds);
     }
     __syncthreads();  // tile built; wave 0 has read the previous partials
-    if (wave == 0) {
-      double s = 1.0;
-#pragma unroll
-      for (int q = 0; q < kTlWaves; ++q) s *= reds[q * kTileRows + lane];
-      s_cur = s;
-    }
+    if (wave == 0) s_cur = tile_scale<kTlWaves>(reds, lane);
 #pragma unroll 1
     for (int rc = 0; rc < kTileRows; rc += 8) {
 #pragma unroll
@@ -269,11 +248,9 @@ int run_predict_tl(const obhip_model &m, obhip_terms &t, const double *d_theta, 
   uint64_t nsplit = std::min<uint64_t>(ntiles, (uint64_t)ncu * 4);
   const uint64_t tps = (ntiles + nsplit - 1) / nsplit;
   nsplit = (ntiles + tps - 1) / tps;
-  hipLaunchKernelGGL((k_predict_tl<W2, NG, VAR>), dim3((unsigned)nsplit), dim3(kTlThreads), lds,
-                     cur_stream(), t.pred_md.dims.p, t.pred_md.ka.p, t.pred_md.kb.p, t.pred_md.kc.p,
-                     t.pred_md.rot.p, t.pred_md.tab.p, t.cpos.p, (int)m.d, (int)t.Mu, (const uint32_t *)t.cols.p,
-                     t.sperm.p, (int)t.p, t.p_pad, npass, d_theta, d_coeffvar, e2sigma, d_x, n, ntiles, tps,
-                     d_mean, d_var);
+  launch_pred<false>(k_predict_tl<W2, NG, VAR>, dim3((unsigned)nsplit), dim3(kTlThreads), lds, pred_tabs(m, t),
+                     (const uint32_t *)t.cols.p, t.sperm.p, (int)t.p, t.p_pad, npass, d_theta, d_coeffvar, e2sigma,
+                     d_x, n, ntiles, tps, d_mean, d_var);
   OB_HIP(hipGetLastError());
   return 0;
 }
@@ -319,10 +296,8 @@ int run_predict(const obhip_model &m, obhip_terms &t, const double *d_theta, con
                 uint64_t n, double *d_mean, const double *d_coeffvar, double e2sigma, double *d_var) {
   const size_t lds = (t.Mu * kTileRows + 2 * kPrWaves * kTileRows) * sizeof(double);
   OB_TRY(ensure_dyn_lds((const void *)k_predict<W2, VAR>, lds));
-  hipLaunchKernelGGL((k_predict<W2, VAR>), dim3((unsigned)((n + kTileRows - 1) / kTileRows)),
-                     dim3(kPrThreads), lds, cur_stream(), t.pred_md.dims.p, t.pred_md.ka.p, t.pred_md.kb.p,
-                     t.pred_md.kc.p, t.pred_md.rot.p, t.pred_md.tab.p, t.cpos.p, (int)m.d, (int)t.Mu,
-                     (const uint32_t *)t.cols.p, (int)(t.W / 2), (int)t.p, d_theta, d_coeffvar,
+  launch_pred<false>(k_predict<W2, VAR>, dim3((unsigned)((n + kTileRows - 1) / kTileRows)), dim3(kPrThreads), lds,
+                     pred_tabs(m, t), (const uint32_t *)t.cols.p, (int)(t.W / 2), (int)t.p, d_theta, d_coeffvar,
                      e2sigma, d_x, n, d_mean, d_var);
   OB_HIP(hipGetLastError());
   return 0;
@@ -346,11 +321,7 @@ int dispatch_predict(const obhip_model &m, obhip_terms &t, const double *d_theta
 int launch_predict(const obhip_model &m, obhip_terms &t, const double *d_theta, const double *d_x,
                    uint64_t n, double *d_mean, const double *d_coeffvar, double e2sigma,
                    double *d_var) {
-  if (t.pred_model != &m || t.pred_md.model_version != m.version) {
-    OB_TRY(t.pred_md.build(m, t.maxlev));
-    t.pred_model = &m;
-  }
-  OB_TRY(t.prepare(t.pred_md.cap, t.pred_md.dims_h));
+  OB_TRY(prepare_predict(m, t, false));
   if (n == 0) return 0;
   ProfScope ps("predict");
   if (t.Mu > 296 || getenv("OBHIP_FORCE_GENERIC")) {

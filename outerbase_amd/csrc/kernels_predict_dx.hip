@@ -31,20 +31,6 @@ namespace {
 constexpr int kDxThreads = 512, kDxWaves = kDxThreads / 64;
 constexpr int kDxRedCols = 2 * 2 * kDxWaves;  // [buffer][mean | var][wave] columns of 64 partials
 
-struct StoreDx {
-  double *tile;     // [column][64]
-  const int *cpos;  // compact column -> used column or -1
-  int lane, Mu;
-  __device__ __forceinline__ void val(int ccol, double v) const {
-    const int u = cpos[ccol];
-    if (u >= 0) tile[u * kTileRows + lane] = v;
-  }
-  __device__ __forceinline__ void der(int ccol, double v) const {
-    const int u = cpos[ccol];
-    if (u >= 0) tile[(Mu + u - 1) * kTileRows + lane] = v;
-  }
-};
-
 template <int W2, bool VAR, bool HBM>
 __global__ void __launch_bounds__(kDxThreads)
 k_predict_dx(const DimDesc *__restrict__ dims, const double *__restrict__ ka, const double *__restrict__ kb,
@@ -68,23 +54,10 @@ k_predict_dx(const DimDesc *__restrict__ dims, const double *__restrict__ ka, co
     const uint64_t row = tl * kTileRows + lane;
     const bool valid = row < n;
     // ---- 1. basis, derivative basis and rho at the rows of the tile ----
-    {
-      double sc = 1.0;
-      const StoreDx store{tile, cpos, lane, Mu};
-      for (int l = wave; l < d; l += kDxWaves) {
-        const DimDesc D = dims[l];
-        const double xv = valid ? x[(uint64_t)l * n + row] : 0.5;
-        double rho;
-        sc *= build_dim_dx_any(D, ka, kb, kc, rot, tab, dtab, xv, store, rho);
-        tile[(2 * Mu - 1 + l) * kTileRows + lane] = rho;
-      }
-      if (wave == 0) tile[lane] = 1.0;  // used column 0 = all ones
-      *redp(0, 0, wave) = sc;
-    }
+    const StoreTile<kTileRows> store{tile, cpos, lane, Mu};
+    build_tile<kDxWaves, true>(dims, ka, kb, kc, rot, tab, dtab, d, x, n, row, valid, wave, store, red);
     __syncthreads();
-    double s = 1.0;
-#pragma unroll
-    for (int q = 0; q < kDxWaves; ++q) s *= *redp(0, 0, q);
+    const double s = tile_scale<kDxWaves>(red, lane);  // (the partials lie where redp(0, 0, .) does)
     __syncthreads();
 
     // ---- 2. dense pass: S = sum theta_k P_k, V = sum c_k P_k^2 ----
@@ -195,15 +168,12 @@ int run_predict_dx(const obhip_model &m, obhip_terms &t, const double *d_theta, 
   uint64_t nblk = std::min<uint64_t>(ntiles, (uint64_t)device_cus(dev) * (HBM ? 2 : 4));
   DevBuf<double> scratch;
   if (HBM) {
-    const uint64_t per = ncols * kTileRows * sizeof(double);
-    nblk = std::max<uint64_t>(1, std::min<uint64_t>(nblk, (1ull << 30) / per));
+    nblk = hbm_tile_blocks(nblk, ncols);
     OB_TRY(scratch.alloc(nblk * ncols * kTileRows));
   }
-  hipLaunchKernelGGL((k_predict_dx<W2, VAR, HBM>), dim3((unsigned)nblk), dim3(kDxThreads), lds, cur_stream(),
-                     t.pred_md.dims.p, t.pred_md.ka.p, t.pred_md.kb.p, t.pred_md.kc.p, t.pred_md.rot.p,
-                     t.pred_md.tab.p, t.dx.dtab.p, t.cpos.p, (int)m.d, (int)t.Mu, (const uint32_t *)t.cols.p,
-                     (int)(t.W / 2), (int)t.p, t.dx.vw.p, t.dx.voff_dev.p, d_theta, d_coeffvar, e2sigma, d_x, n,
-                     ntiles, scratch.p, d_mean, d_var, d_grad, d_gradvar);
+  launch_pred<true>(k_predict_dx<W2, VAR, HBM>, dim3((unsigned)nblk), dim3(kDxThreads), lds, pred_tabs(m, t),
+                    (const uint32_t *)t.cols.p, (int)(t.W / 2), (int)t.p, t.dx.vw.p, t.dx.voff_dev.p, d_theta,
+                    d_coeffvar, e2sigma, d_x, n, ntiles, scratch.p, d_mean, d_var, d_grad, d_gradvar);
   OB_HIP(hipGetLastError());
   // (scratch goes back to the pool under this stream: handed out again to work queued behind the kernel)
   return 0;
@@ -227,22 +197,17 @@ int dispatch_predict_dx(bool fused, const obhip_model &m, obhip_terms &t, const 
 
 }  // namespace
 
-// the fused kernel's domain: at most 8 factors per term and a tile that fits 160 KB of LDS
+// the fused kernel's domain: at most 8 factors per term and a tile that fits the LDS
 bool predict_dx_supports(const obhip_terms &t) {
   const uint64_t w2 = t.W / 2;
   return w2 >= 1 && w2 <= 4 &&
-         (2 * t.Mu - 1 + t.d + kDxRedCols) * kTileRows * sizeof(double) <= 160 * 1024;
+         (2 * t.Mu - 1 + t.d + kDxRedCols) * kTileRows * sizeof(double) <= kLdsBudget;
 }
 
 int launch_predict_dx(const obhip_model &m, obhip_terms &t, const double *d_theta, const double *d_x, uint64_t n,
                       double *d_mean, double *d_grad, const double *d_coeffvar, double e2sigma, double *d_var,
                       double *d_gradvar) {
-  if (t.pred_model != &m || t.pred_md.model_version != m.version) {
-    OB_TRY(t.pred_md.build(m, t.maxlev));
-    t.pred_model = &m;
-  }
-  OB_TRY(t.prepare(t.pred_md.cap, t.pred_md.dims_h));
-  OB_TRY(ensure_dx_tables(m, t));
+  OB_TRY(prepare_predict(m, t, true));
   if (n == 0) return 0;
   ProfScope ps("predict_dx");
   const bool fused = predict_dx_supports(t) && !getenv("OBHIP_FORCE_GENERIC");

@@ -33,7 +33,6 @@
 // launch_predict_dx per response, the VJP accumulated by k_vjp_accum from an n x d pooled scratch.
 #include "obhip_internal.h"
 #include "device_dx.h"
-#include "vec_ops.h"
 
 namespace obhip {
 
@@ -42,26 +41,11 @@ namespace {
 typedef double d4 __attribute__((ext_vector_type(4)));
 constexpr int kPjThreads = 512, kPjWaves = kPjThreads / 64;
 constexpr int kPjPitch = kTileRows + 1;   // doubles per tile column and per staged response
-constexpr size_t kPjLdsLimit = 160 * 1024;
 constexpr uint64_t kPjChunk = 64;         // responses of one launch at most
 
 __device__ __forceinline__ d4 mfma(double a, double b, d4 c) {
   return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
 }
-
-struct StoreJac {
-  double *tile;     // [column][65]
-  const int *cpos;  // compact column -> used column or -1
-  int lane, Mu;
-  __device__ __forceinline__ void val(int ccol, double v) const {
-    const int u = cpos[ccol];
-    if (u >= 0) tile[u * kPjPitch + lane] = v;
-  }
-  __device__ __forceinline__ void der(int ccol, double v) const {
-    const int u = cpos[ccol];
-    if (u >= 0) tile[(Mu + u - 1) * kPjPitch + lane] = v;
-  }
-};
 
 // the steps of one pass that this wave's half takes, accumulated into acc (zeroed here).
 // DENSE: entry = term, W2 column words at colsw.  Otherwise entry = view entry of W2 + 2 words (the
@@ -127,25 +111,11 @@ k_predict_jac(const DimDesc *__restrict__ dims, const double *__restrict__ ka, c
     {
       const uint64_t row = row0 + lane;
       const bool valid = row < n;
-      double sc = 1.0;
-      const StoreJac store{tile, cpos, lane, Mu};
-      for (int l = wave; l < d; l += kPjWaves) {
-        const DimDesc D = dims[l];
-        const double xv = valid ? x[(uint64_t)l * n + row] : 0.5;
-        double rho;
-        sc *= build_dim_dx_any(D, ka, kb, kc, rot, tab, dtab, xv, store, rho);
-        tile[(2 * Mu - 1 + l) * kPjPitch + lane] = rho;
-      }
-      if (wave == 0) tile[lane] = 1.0;  // used column 0 = all ones
-      reds[wave * kTileRows + lane] = sc;
+      const StoreTile<kPjPitch> store{tile, cpos, lane, Mu};
+      build_tile<kPjWaves, true>(dims, ka, kb, kc, rot, tab, dtab, d, x, n, row, valid, wave, store, reds);
     }
     __syncthreads();
-    if (wave == 0) {
-      double s = 1.0;
-#pragma unroll
-      for (int w = 0; w < kPjWaves; ++w) s *= reds[w * kTileRows + lane];
-      scl[lane] = s;
-    }
+    if (wave == 0) scl[lane] = tile_scale<kPjWaves>(reds, lane);
 
     // ---- 2. / 3. the d + 1 passes ----
     d4 S[NQB];
@@ -233,11 +203,9 @@ int run_predict_jac(const obhip_model &m, obhip_terms &t, const double *d_ThT, i
   (void)hipGetDevice(&dev);
   const uint64_t ntiles = (n + kTileRows - 1) / kTileRows;
   const uint64_t nblk = std::min<uint64_t>(ntiles, (uint64_t)device_cus(dev) * 8);
-  hipLaunchKernelGGL((k_predict_jac<NQB, VJP>), dim3((unsigned)nblk), dim3(kPjThreads), lds, cur_stream(),
-                     t.pred_md.dims.p, t.pred_md.ka.p, t.pred_md.kb.p, t.pred_md.kc.p, t.pred_md.rot.p,
-                     t.pred_md.tab.p, t.dx.dtab.p, t.cpos.p, (int)m.d, (int)t.Mu, (const uint32_t *)t.cols.p,
-                     (int)(t.W / 2), (int)t.p, t.dx.vw.p, t.dx.voff_dev.p, d_ThT, qc, d_x, n, ntiles, d_mean, d_jac,
-                     d_W, ldw, first, d_out);
+  launch_pred<true>(k_predict_jac<NQB, VJP>, dim3((unsigned)nblk), dim3(kPjThreads), lds, pred_tabs(m, t),
+                    (const uint32_t *)t.cols.p, (int)(t.W / 2), (int)t.p, t.dx.vw.p, t.dx.voff_dev.p, d_ThT, qc, d_x,
+                    n, ntiles, d_mean, d_jac, d_W, ldw, first, d_out);
   OB_HIP(hipGetLastError());
   return 0;
 }
@@ -254,9 +222,9 @@ k_vjp_accum(const double *__restrict__ w, const double *__restrict__ g, uint64_t
 }  // namespace
 
 // the fused kernel's domain: an even padded width (any number of factors: the column lists are read
-// from memory) and the tile, one staged block of 16 responses and the scale space within 160 KB
+// from memory) and the tile, one staged block of 16 responses and the scale space within the LDS
 bool predict_jac_supports(const obhip_terms &t) {
-  return t.W >= 2 && t.W % 2 == 0 && predict_jac_lds(t.Mu, t.d, 1) <= kPjLdsLimit;
+  return t.W >= 2 && t.W % 2 == 0 && predict_jac_lds(t.Mu, t.d, 1) <= kLdsBudget;
 }
 
 // d_W == nullptr: the Jacobian into d_jac ((q, d, n)); otherwise the VJP with d_W into d_out (n x d).
@@ -264,12 +232,7 @@ bool predict_jac_supports(const obhip_terms &t) {
 // take launch_predict_dx once per response.
 int launch_predict_jac(const obhip_model &m, obhip_terms &t, const double *d_Theta, uint64_t q, const double *d_x,
                        uint64_t n, double *d_mean, double *d_jac, const double *d_W, uint64_t ldw, double *d_out) {
-  if (t.pred_model != &m || t.pred_md.model_version != m.version) {
-    OB_TRY(t.pred_md.build(m, t.maxlev));
-    t.pred_model = &m;
-  }
-  OB_TRY(t.prepare(t.pred_md.cap, t.pred_md.dims_h));
-  OB_TRY(ensure_dx_tables(m, t));
+  OB_TRY(prepare_predict(m, t, true));
   if (n == 0) return 0;
   const uint64_t p = t.p, d = m.d;
   const bool vjp = d_W != nullptr;
@@ -290,7 +253,7 @@ int launch_predict_jac(const obhip_model &m, obhip_terms &t, const double *d_The
   }
   ProfScope ps(vjp ? "predict_vjp_multi" : "predict_jac_multi");
   int nqb_max = 4;
-  while (nqb_max > 1 && predict_jac_lds(t.Mu, d, nqb_max) > kPjLdsLimit) nqb_max /= 2;
+  while (nqb_max > 1 && predict_jac_lds(t.Mu, d, nqb_max) > kLdsBudget) nqb_max /= 2;
   const uint64_t chunk = std::min<uint64_t>(kPjChunk, 16 * (uint64_t)nqb_max);
   DevBuf<double> tht;
   OB_TRY(tht.alloc(p * chunk));
@@ -298,14 +261,8 @@ int launch_predict_jac(const obhip_model &m, obhip_terms &t, const double *d_The
     const int qc = (int)std::min<uint64_t>(chunk, q - q0);
     int nqb = 1;
     while (16 * nqb < qc) nqb *= 2;
-    const uint64_t qw = 16 * (uint64_t)nqb;
     double *T = tht.p;
-    const double *Th = d_Theta + q0 * p;
-    // term-major copy of the chunk, zero beyond its columns
-    OB_TRY(vmap(p * qw, [=] __device__(uint64_t i) {
-      const uint64_t k = i / qw, j = i % qw;
-      T[i] = j < (uint64_t)qc ? Th[j * p + k] : 0.0;
-    }));
+    OB_TRY(launch_theta_term_major(d_Theta + q0 * p, p, qc, 16 * (uint64_t)nqb, T));
     double *mc = d_mean ? d_mean + q0 * n : nullptr;
     double *jc = vjp ? nullptr : d_jac + q0 * d * n;
     const double *wc = vjp ? d_W + q0 * ldw : nullptr;

@@ -40,45 +40,6 @@ namespace {
 constexpr int kMaxMuLds = 304;  // 304 * 64 * 8 B = 152 KiB of the 160 KiB LDS
 constexpr int kMaxW2 = 4;       // register-resident column lists: up to 8 columns per term
 
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_readlane(lo, l);
-  hi = __builtin_amdgcn_readlane(hi, l);
-  return __hiloint2double(hi, lo);
-}
-
-// product of the staged columns of the term held by lane t, for this lane's row
-template <int W2>
-__device__ __forceinline__ double term_prod_rl(const double *__restrict__ lds,
-                                               const uint32_t (&cw)[W2], int t, int lane, double v) {
-#pragma unroll
-  for (int w = 0; w < W2; ++w) {
-    const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)cw[w], t);
-    v *= lds[(c & 0xffffu) * kTileRows + lane];
-    v *= lds[(c >> 16) * kTileRows + lane];
-  }
-  return v;
-}
-
-// generic fallback (more than 8 columns per term): column words from memory
-__device__ __forceinline__ double term_prod_mem(const double *__restrict__ lds,
-                                                const uint32_t *__restrict__ cw, int W2, int lane,
-                                                double v) {
-  for (int w = 0; w < W2; ++w) {
-    const uint32_t c = cw[w];
-    v *= lds[(c & 0xffffu) * kTileRows + lane];
-    v *= lds[(c >> 16) * kTileRows + lane];
-  }
-  return v;
-}
-
-template <int W2>
-__device__ __forceinline__ void load_cw(uint32_t (&cw)[W2], const uint32_t *__restrict__ colsw,
-                                        int k) {
-#pragma unroll
-  for (int w = 0; w < W2; ++w) cw[w] = colsw[(size_t)k * W2 + w];
-}
-
 // ---- mm / getmat -----------------------------------------------------------------------
 // MODE 0: out = B a;  MODE 1: out = B^2 a;  MODE 2: materialise B (a unused)
 // 8 waves share one staged tile: 3 blocks x 8 waves per CU instead of 3 x 4 (the tile is

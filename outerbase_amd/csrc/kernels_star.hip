@@ -618,7 +618,7 @@ k_star_predict(const DimDesc *__restrict__ dims, const double *__restrict__ ka, 
     }
   };
   auto build = [&](uint64_t tile, int bsel) {  // lane = row
-    const StoreLdsPitch store{lds + (bsel ? tile_doubles : 0), cpos, lane};
+    const StoreTile<kTlPitch> store{lds + (bsel ? tile_doubles : 0), cpos, lane, Mu};
     const uint64_t row = tile * kTileRows + lane;
     const bool valid = row < n;
     double sc = 1.0;
@@ -632,7 +632,7 @@ k_star_predict(const DimDesc *__restrict__ dims, const double *__restrict__ ka, 
       const DimDesc D = dims[l];
       sc *= build_dim_any(D, ka, kb, kc, rot, tab, xv, store);
     }
-    if (wave == 0) store.lds[lane] = 1.0;  // used column 0 = all ones
+    if (wave == 0) store.tile[lane] = 1.0;  // used column 0 = all ones
     reds[(bsel * WAVES + wave) * kStRedPitch + lane] = sc;
   };
   if (t0 < t1) {
@@ -804,9 +804,8 @@ int launch_star_predict(const obhip_model &m, obhip_terms &t, const double *d_th
 #define OB_SP2(W2_, K_, VAR_, PFX_)                                                                           \
   do {                                                                                                        \
     OB_TRY(ensure_dyn_lds((const void *)k_star_predict<W2_, K_, VAR_, PFX_>, lds));                           \
-    hipLaunchKernelGGL((k_star_predict<W2_, K_, VAR_, PFX_>), dim3((unsigned)nsplit), dim3(kStWaves * 64), lds, \
-                       cur_stream(), t.pred_md.dims.p, t.pred_md.ka.p, t.pred_md.kb.p, t.pred_md.kc.p,        \
-                       t.pred_md.rot.p, t.pred_md.tab.p, t.cpos.p, (int)m.d, (int)t.Mu,                       \
+    launch_pred<false>(k_star_predict<W2_, K_, VAR_, PFX_>, dim3((unsigned)nsplit), dim3(kStWaves * 64), lds, \
+                       pred_tabs(m, t),                                                                       \
                        (const uint32_t *)t.sh_cols.p, t.sh_term.p, t.sh_shape.p, (int)t.sh.nsw_family,        \
                        t.sh_left_term.p, (const uint32_t *)t.sh_left_cols.p, (int)t.sh.nleft, (int)t.p,       \
                        d_theta, d_coeffvar, e2sigma, d_x, n, ntiles, tps, d_mean, d_var);                     \

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 
 #include <cstdint>
@@ -435,6 +436,8 @@ struct obhip_basis {
 namespace obhip {
 
 constexpr int kTileRows = 64;
+// LDS of a workgroup on gfx950: what the fused kernels size their tiles against
+constexpr size_t kLdsBudget = 160 * 1024;
 // doubles of LDS k_build_basis has for one dimension's interval tables; ModelDev::build makes
 // tables only for dimensions whose tables fit (larger ones would be per-lane global gathers, no
 // faster than the knot loop, and cost the host O(knots^2 x levels) per hyper-parameter update)
@@ -588,8 +591,54 @@ int launch_aty_multi(obhip_basis &b, const obhip_terms &t, const double *d_Y, ui
 int launch_trsm_multi(uint64_t p, const double *d_L, const double *d_Iinv, const double *d_R, uint64_t ldr,
                       uint64_t q, double e2, double *d_Theta, void *d_scratch);
 bool predict_multi_supports(const obhip_terms &t);
+// d_T ([p][qw], term-major) = the qc <= qw columns of d_Theta (p x qc, leading dimension p), zero beyond them:
+// the B operand of the multi-response predictors
+int launch_theta_term_major(const double *d_Theta, uint64_t p, int qc, uint64_t qw, double *d_T);
 int launch_predict_multi(const obhip_model &m, obhip_terms &t, const double *d_Theta, uint64_t q,
                          const double *d_x, uint64_t n, double *d_mean);
+// ---- what the fused predictors share on the host -------------------------------------------------
+// (kernels_predict, _star, _multi, _predict_dx, _materialize_dx, _predict_jac)
+int ensure_dx_tables(const obhip_model &m, obhip_terms &t);  // predict_dx.cpp; after t.prepare(t.pred_md.cap, ...)
+// Before any of their launches: the device view of the model capped at the terms' levels (rebuilt when
+// the model or its state changed), the term tables packed against its column layout and, with_dx, the
+// per-dimension views and derivative tables of the input-gradient kernels.
+inline int prepare_predict(const obhip_model &m, obhip_terms &t, bool with_dx) {
+  if (t.pred_model != &m || t.pred_md.model_version != m.version) {
+    OB_TRY(t.pred_md.build(m, t.maxlev));
+    t.pred_model = &m;
+  }
+  OB_TRY(t.prepare(t.pred_md.cap, t.pred_md.dims_h));
+  if (with_dx) OB_TRY(ensure_dx_tables(m, t));
+  return 0;
+}
+// The tables their kernels evaluate the basis from: the kernels' leading parameters, in their order
+// (dtab: behind tab in the kernels that take it; null before ensure_dx_tables).
+struct PredTabs {
+  const DimDesc *dims;
+  const double *ka, *kb, *kc, *rot, *tab, *dtab;
+  const int *cpos;
+  int d, Mu;
+};
+inline PredTabs pred_tabs(const obhip_model &m, const obhip_terms &t) {
+  const ModelDev &md = t.pred_md;
+  return {md.dims.p, md.ka.p, md.kb.p, md.kc.p, md.rot.p, md.tab.p, t.dx.dtab.p, t.cpos.p, (int)m.d, (int)t.Mu};
+}
+// kernel<<<grid, block, lds, current stream>>>(the tables as separate arguments, rest...); DX: with dtab
+template <bool DX, typename Kernel, typename... Rest>
+void launch_pred(Kernel kernel, dim3 grid, dim3 block, size_t lds, const PredTabs &T, Rest... rest) {
+  if constexpr (DX)
+    hipLaunchKernelGGL(kernel, grid, block, lds, cur_stream(), T.dims, T.ka, T.kb, T.kc, T.rot, T.tab, T.dtab, T.cpos,
+                       T.d, T.Mu, rest...);
+  else
+    hipLaunchKernelGGL(kernel, grid, block, lds, cur_stream(), T.dims, T.ka, T.kb, T.kc, T.rot, T.tab, T.cpos, T.d,
+                       T.Mu, rest...);
+}
+// blocks of a fallback kernel that keeps its tile of ncols columns in a per-block slice of pooled HBM
+// scratch: at most `want`, at least 1, within 1 GB of scratch in all
+inline uint64_t hbm_tile_blocks(uint64_t want, uint64_t ncols) {
+  const uint64_t per = ncols * kTileRows * sizeof(double);
+  return std::max<uint64_t>(1, std::min<uint64_t>(want, (1ull << 30) / per));
+}
 // kernels_predict.hip
 int launch_predict(const obhip_model &m, obhip_terms &t, const double *d_theta,
                    const double *d_x, uint64_t n, double *d_mean,
@@ -597,7 +646,6 @@ int launch_predict(const obhip_model &m, obhip_terms &t, const double *d_theta,
 // kernels_predict_dx.hip / predict_dx.cpp: mean, variance and their gradients by the inputs
 bool predict_dx_supports(const obhip_terms &t);
 void build_dim_views_host(obhip_terms &t);               // t.dx.voff / vterm (no device needed)
-int ensure_dx_tables(const obhip_model &m, obhip_terms &t);  // after t.prepare(t.pred_md.cap, ...)
 int launch_predict_dx(const obhip_model &m, obhip_terms &t, const double *d_theta, const double *d_x, uint64_t n,
                       double *d_mean, double *d_grad, const double *d_coeffvar, double e2sigma, double *d_var,
                       double *d_gradvar);
@@ -623,7 +671,7 @@ struct DxStage {
 };
 // dims distinct and < d, 1 <= ndims <= d, weights (may be null) finite and > 0 -- refused in that order
 int check_grad_dims(const char *who, uint64_t d, const uint32_t *dims, uint64_t ndims, const double *weights);
-int ensure_dx_stage(const obhip_model &m, obhip_terms &t);  // tables of the staging kernel (device)
+int ensure_dx_stage(const obhip_model &m, obhip_terms &t);  // prepare_predict + the staging kernel's own table
 bool materialize_dx_supports(const obhip_terms &t);
 int launch_materialize_dx(const obhip_model &m, obhip_terms &t, const DxStage &s);
 uint64_t dx_aty_splits(uint64_t rows);

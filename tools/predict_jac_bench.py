@@ -65,8 +65,9 @@ def main():
     def lds_bytes(nqb):      # predict_jac_lds of csrc/kernels_predict_jac.hip
         return ((2 * used - 1 + d) * 65 + 16 * nqb * 65 + 8 * 64 + 64) * 8
 
-    fused = lds_bytes(1) <= 160 * 1024 and width >= 2 and not os.environ.get("OBHIP_FORCE_GENERIC")
-    nqb_max = max([b for b in (1, 2, 4) if lds_bytes(b) <= 160 * 1024], default=0)
+    budget = 160 * 1024      # kLdsBudget of csrc/obhip_internal.h
+    fused = lds_bytes(1) <= budget and width >= 2 and not os.environ.get("OBHIP_FORCE_GENERIC")
+    nqb_max = max([b for b in (1, 2, 4) if lds_bytes(b) <= budget], default=0)
     rng = np.random.default_rng(1)
     per_q = {}
     for q in args.q:
