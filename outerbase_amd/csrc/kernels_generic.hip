@@ -132,13 +132,11 @@ int launch_mm_generic(const obhip_basis &b, obhip_terms &t, const double *d_a, d
                       uint64_t ld) {
   if (ld == 0) ld = b.n;
   const dim3 grid((unsigned)(b.n_pad / kTileRows));
-#define OB_GMM(M_)                                                                                 \
-  hipLaunchKernelGGL(k_mm_generic<M_>, grid, dim3(kGW * 64), 0, cur_stream(), b.bm.p, b.scale.p,    \
-                     b.md.Mc, t.cols.p, t.ucol.p, (int)t.W, (int)t.p, d_a, b.n, ld, d_out)
-  if (mode == 0) OB_GMM(0);
-  else if (mode == 1) OB_GMM(1);
-  else OB_GMM(2);
-#undef OB_GMM
+  pick<0, 1, 2>(mode, [&](auto MODE) {
+    hipLaunchKernelGGL(k_mm_generic<MODE()>, grid, dim3(kGW * 64), 0, cur_stream(), b.bm.p, b.scale.p, b.md.Mc,
+                       t.cols.p, t.ucol.p, (int)t.W, (int)t.p, d_a, b.n, ld, d_out);
+    return 0;
+  });
   OB_HIP(hipGetLastError());
   return 0;
 }
@@ -147,21 +145,16 @@ int launch_tmm_generic(const obhip_basis &b, obhip_terms &t, const double *d_a, 
                        bool squared) {
   const uint64_t ntiles = b.n_pad / kTileRows;
   const uint64_t yblocks = (t.p + kGW - 1) / kGW;
-  uint64_t nsplit = std::max<uint64_t>(1, 4096 / std::max<uint64_t>(1, yblocks));
-  nsplit = std::min(nsplit, std::max<uint64_t>(1, ntiles / 4));
-  const uint64_t tps = (ntiles + nsplit - 1) / nsplit;
-  nsplit = (ntiles + tps - 1) / tps;
+  const RowSplit rs = split_rows(ntiles, 4096 / std::max<uint64_t>(1, yblocks), 4);
+  const uint64_t nsplit = rs.nsplit, tps = rs.tps;
   double *part = nullptr;
   OB_TRY(const_cast<obhip_basis &>(b).workspace(nsplit * t.p_pad * sizeof(double), (void **)&part));
   const dim3 grid((unsigned)nsplit, (unsigned)yblocks);
-  if (squared)
-    hipLaunchKernelGGL(k_tmm_generic<true>, grid, dim3(kGW * 64), 0, cur_stream(), b.bm.p, b.scale.p,
-                       b.md.Mc, t.cols.p, t.ucol.p, (int)t.W, (int)t.p, d_a, b.n, ntiles, tps, t.p_pad,
-                       part);
-  else
-    hipLaunchKernelGGL(k_tmm_generic<false>, grid, dim3(kGW * 64), 0, cur_stream(), b.bm.p, b.scale.p,
-                       b.md.Mc, t.cols.p, t.ucol.p, (int)t.W, (int)t.p, d_a, b.n, ntiles, tps, t.p_pad,
-                       part);
+  pick_bool(squared, [&](auto SQ) {
+    hipLaunchKernelGGL(k_tmm_generic<SQ()>, grid, dim3(kGW * 64), 0, cur_stream(), b.bm.p, b.scale.p, b.md.Mc,
+                       t.cols.p, t.ucol.p, (int)t.W, (int)t.p, d_a, b.n, ntiles, tps, t.p_pad, part);
+    return 0;
+  });
   hipLaunchKernelGGL(k_tmm_generic_reduce, dim3((unsigned)((t.p + 255) / 256)), dim3(256), 0,
                      cur_stream(), part, (int)nsplit, t.p_pad, (int)t.p, d_out);
   OB_HIP(hipGetLastError());

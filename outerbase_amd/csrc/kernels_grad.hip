@@ -1143,65 +1143,41 @@ __global__ void k_btu_reduce(const double *__restrict__ part, int nsplit, uint64
 }  // namespace
 
 namespace {
-template <int W2, int NHB, bool SQ, int NW>
-int run_tmm_ge0_sq(const obhip_basis &src, obhip_terms &t, const int *d_c0, int nhyp, int h0,
-                   const double *d_a, dim3 grid, uint64_t ntiles, uint64_t tps, double *part) {
-  const size_t lds = (t.Mu + 16 * NHB) * kTlPitch * sizeof(double);
-  if (lds > 64 * 1024)
-    OB_TRY(ensure_dyn_lds((const void *)k_tmm_ge0<W2, NHB, SQ, NW>, lds));
-  hipLaunchKernelGGL((k_tmm_ge0<W2, NHB, SQ, NW>), grid, dim3(NW * 64), lds, cur_stream(), src.bm.p,
-                     src.scale.p, t.ucol.p, (int)t.Mu, src.md.Mc, (const uint32_t *)t.cols.p,
-                     t.sperm.p, d_c0, nhyp, h0, d_a, src.n, ntiles, tps, t.p_pad, part);
-  OB_HIP(hipGetLastError());
-  return 0;
-}
-template <int W2, bool SQ, int N4, int NHB = 1>
-int run_tmm_ge0_db(const obhip_basis &src, obhip_terms &t, const int *d_c0, int nhyp, int h0,
-                   const double *d_a, dim3 grid, uint64_t ntiles, uint64_t tps, double *part) {
-  const size_t lds = 2 * (t.Mu + 16 * NHB + 4 * N4) * kTlPitch * sizeof(double);
-  OB_TRY(ensure_dyn_lds((const void *)k_tmm_ge0_db<W2, SQ, N4, NHB>, lds));
-  hipLaunchKernelGGL((k_tmm_ge0_db<W2, SQ, N4, NHB>), grid, dim3(1024), lds, cur_stream(), src.bm.p, src.scale.p,
-                     t.ucol.p, (int)t.Mu, src.md.Mc, (const uint32_t *)t.cols.p, t.sperm.p, d_c0, nhyp, h0,
-                     d_a, src.n, ntiles, tps, t.p_pad, part);
-  OB_HIP(hipGetLastError());
-  return 0;
-}
-template <int W2, int NHB>
+// LDS bytes of a k_tmm_ge0 / k_tmm_ge0_db tile: the used columns and the staged gradient columns of nh
+// hyper-parameters
+size_t ge0_tile_bytes(const obhip_terms &t, int nh) { return (t.Mu + nh) * kTlPitch * sizeof(double); }
+
+// nw = 8 | 16: k_tmm_ge0 with that many waves and one 16-block of hyper-parameters; nw = 32: k_tmm_ge0_db
+// (16 waves, two tile buffers) with n4 > 0: a 16-block and n4 groups of four, n4 < 0: |n4| groups of four
+// only, n4 = 0: the 16-block only
 int run_tmm_ge0(bool sq, int nw, int n4, const obhip_basis &src, obhip_terms &t, const int *d_c0, int nhyp,
                 int h0, const double *d_a, dim3 grid, uint64_t ntiles, uint64_t tps, double *part) {
-  if (nw == 32) {  // (16 waves, two tile buffers)
-    if (n4 == -1) {  // groups of four only
-      if (sq) return run_tmm_ge0_db<W2, true, 1, 0>(src, t, d_c0, nhyp, h0, d_a, grid, ntiles, tps, part);
-      return run_tmm_ge0_db<W2, false, 1, 0>(src, t, d_c0, nhyp, h0, d_a, grid, ntiles, tps, part);
-    }
-    if (n4 == -2) {
-      if (sq) return run_tmm_ge0_db<W2, true, 2, 0>(src, t, d_c0, nhyp, h0, d_a, grid, ntiles, tps, part);
-      return run_tmm_ge0_db<W2, false, 2, 0>(src, t, d_c0, nhyp, h0, d_a, grid, ntiles, tps, part);
-    }
-    if (n4 == 1) {
-      if (sq) return run_tmm_ge0_db<W2, true, 1>(src, t, d_c0, nhyp, h0, d_a, grid, ntiles, tps, part);
-      return run_tmm_ge0_db<W2, false, 1>(src, t, d_c0, nhyp, h0, d_a, grid, ntiles, tps, part);
-    }
-    if (n4 == 2) {
-      if (sq) return run_tmm_ge0_db<W2, true, 2>(src, t, d_c0, nhyp, h0, d_a, grid, ntiles, tps, part);
-      return run_tmm_ge0_db<W2, false, 2>(src, t, d_c0, nhyp, h0, d_a, grid, ntiles, tps, part);
-    }
-    if (sq) return run_tmm_ge0_db<W2, true, 0>(src, t, d_c0, nhyp, h0, d_a, grid, ntiles, tps, part);
-    return run_tmm_ge0_db<W2, false, 0>(src, t, d_c0, nhyp, h0, d_a, grid, ntiles, tps, part);
-  }
-  if (nw == 16) {
-    if (sq) return run_tmm_ge0_sq<W2, NHB, true, 16>(src, t, d_c0, nhyp, h0, d_a, grid, ntiles, tps, part);
-    return run_tmm_ge0_sq<W2, NHB, false, 16>(src, t, d_c0, nhyp, h0, d_a, grid, ntiles, tps, part);
-  }
-  if (sq) return run_tmm_ge0_sq<W2, NHB, true, 8>(src, t, d_c0, nhyp, h0, d_a, grid, ntiles, tps, part);
-  return run_tmm_ge0_sq<W2, NHB, false, 8>(src, t, d_c0, nhyp, h0, d_a, grid, ntiles, tps, part);
+  const ProdTabs T = prod_tabs(src, t);
+  return pick<1, 2, 3, 4>((int)(t.W / 2), [&](auto W2) {
+    return pick_bool(sq, [&](auto SQ) {
+      if (nw == 32)
+        return pick<1, 0>(n4 >= 0 ? 1 : 0, [&](auto NHB) {  // 16-blocks
+          return pick<1, 2, 0>(n4 < 0 ? -n4 : n4, [&](auto N4) {
+            if constexpr (!NHB() && N4() == 0) return no_kernel();
+            else
+              return launch_prod(k_tmm_ge0_db<W2(), SQ(), N4(), NHB()>, grid, dim3(1024),
+                                 2 * ge0_tile_bytes(t, 16 * NHB() + 4 * N4()), T, t.sperm.p, d_c0, nhyp, h0, d_a,
+                                 src.n, ntiles, tps, t.p_pad, part);
+          });
+        });
+      return pick<16, 8>(nw, [&](auto NW) {
+        return launch_prod(k_tmm_ge0<W2(), 1, SQ(), NW()>, grid, dim3(NW() * 64), ge0_tile_bytes(t, 16), T,
+                           t.sperm.p, d_c0, nhyp, h0, d_a, src.n, ntiles, tps, t.p_pad, part);
+      });
+    });
+  });
 }
 }  // namespace
 
 // the dense part without the design matrix (k_tmm_ge0); t prepared for b
 bool tmm_ge0_supports(const obhip_terms &t) {
   const uint64_t w2 = t.W / 2;
-  return w2 >= 1 && w2 <= 4 && (t.Mu + 32) * kTlPitch * sizeof(double) <= 156 * 1024;
+  return w2 >= 1 && w2 <= 4 && ge0_tile_bytes(t, 32) <= kLdsTile;
 }
 
 // d_out: p x nhyp column-major (device) = sum_i a_i ge[h, 0]_i B_ik (squared: the squared stores,
@@ -1225,8 +1201,8 @@ int launch_tmm_ge0(obhip_basis &b, obhip_terms &t, bool squared, const double *d
   // outside the read pipeline).  d = 20 mat25 at the headline terms, 20 hyper-parameters: dense part
   // 5.47 / 4.52 / 3.50 ms, obfit evaluation 30.8 / 29.8 / 28.5 ms (tools/r05_fours_ab.sh).
   static const int fours = getenv("OBHIP_GE0_FOURS") ? atoi(getenv("OBHIP_GE0_FOURS")) : 2;
-  const size_t tile_lds = (t.Mu + 16) * kTlPitch * sizeof(double);
-  const bool two_tiles = 2 * tile_lds <= 156 * 1024;
+  const size_t tile_lds = ge0_tile_bytes(t, 16);
+  const bool two_tiles = 2 * tile_lds <= kLdsTile;
   bool one_per_cu = tile_lds > 80 * 1024;
   int nw = one_per_cu ? 16 : 8;
   if (two_tiles) nw = 32;
@@ -1235,10 +1211,8 @@ int launch_tmm_ge0(obhip_basis &b, obhip_terms &t, bool squared, const double *d
   const uint64_t tpb = (uint64_t)(nw == 32 ? 16 : nw) * 64;
   const uint64_t pblocks = (t.p_pad + tpb - 1) / tpb;
   const int ncu = device_cus(b.device);
-  uint64_t nsplit = std::max<uint64_t>(1, (uint64_t)ncu * (one_per_cu ? 1 : 2) / pblocks);
-  nsplit = std::min(nsplit, ntiles);
-  const uint64_t tps = (ntiles + nsplit - 1) / nsplit;
-  nsplit = (ntiles + tps - 1) / tps;
+  const RowSplit rs = split_rows(ntiles, (uint64_t)ncu * (one_per_cu ? 1 : 2) / pblocks);
+  const uint64_t nsplit = rs.nsplit, tps = rs.tps;
   const dim3 grid((unsigned)nsplit, (unsigned)pblocks);
   ProfScope ps(squared ? "sqtmm_gradhyp_dense" : "tmm_gradhyp_dense");
   // 16 hyper-parameters per pass: with two 16-blocks per pass (NHB = 2) the 64 accumulator
@@ -1250,17 +1224,12 @@ int launch_tmm_ge0(obhip_basis &b, obhip_terms &t, bool squared, const double *d
     int n4 = 0;
     if (fours == 2 && nw == 32 && rem > 16 && rem <= 24) n4 = (rem - 16 + 3) / 4;
     if (fours >= 1 && nw == 32 && rem <= 8) n4 = -((rem + 3) / 4);
-    if (n4 > 0 && 2 * (t.Mu + 16 + 4 * n4) * kTlPitch * sizeof(double) > 156 * 1024) n4 = 0;
+    if (n4 > 0 && 2 * ge0_tile_bytes(t, 16 + 4 * n4) > kLdsTile) n4 = 0;
     const int nh = n4 > 0 ? rem : (n4 < 0 ? rem : std::min(16, rem));
     const int hs = n4 > 0 ? 16 + 4 * n4 : (n4 < 0 ? -4 * n4 : 16);
     double *part = nullptr;
     OB_TRY(b.workspace(nsplit * hs * t.p_pad * sizeof(double), (void **)&part));
-    switch (t.W / 2) {
-      case 1: OB_TRY((run_tmm_ge0<1, 1>(squared, nw, n4, src, t, dc0.p, nhyp, h0, d_a, grid, ntiles, tps, part))); break;
-      case 2: OB_TRY((run_tmm_ge0<2, 1>(squared, nw, n4, src, t, dc0.p, nhyp, h0, d_a, grid, ntiles, tps, part))); break;
-      case 3: OB_TRY((run_tmm_ge0<3, 1>(squared, nw, n4, src, t, dc0.p, nhyp, h0, d_a, grid, ntiles, tps, part))); break;
-      default: OB_TRY((run_tmm_ge0<4, 1>(squared, nw, n4, src, t, dc0.p, nhyp, h0, d_a, grid, ntiles, tps, part))); break;
-    }
+    OB_TRY(run_tmm_ge0(squared, nw, n4, src, t, dc0.p, nhyp, h0, d_a, grid, ntiles, tps, part));
     hipLaunchKernelGGL(k_ge0_reduce, dim3((unsigned)((t.p + 255) / 256), (unsigned)nh), dim3(256), 0,
                        cur_stream(), part, (int)nsplit, hs, t.p_pad, (int)t.p, nh,
                        d_out + (uint64_t)h0 * t.p);
@@ -1283,22 +1252,18 @@ int launch_bt_times_ge0(obhip_basis &b, obhip_terms &t, bool squared, const doub
   OB_TRY(dc0.upload(c0.data(), c0.size()));
   const uint64_t ntiles = b.n_pad / kTileRows;
   const unsigned gy = (unsigned)((t.p_pad + 2047) / 2048);
-  uint64_t nsplit = std::max<uint64_t>(1, std::min<uint64_t>(ntiles, 1024 / gy));
-  const uint64_t tps = (ntiles + nsplit - 1) / nsplit;
-  nsplit = (ntiles + tps - 1) / tps;
+  const RowSplit rs = split_rows(ntiles, 1024 / gy);
+  const uint64_t nsplit = rs.nsplit, tps = rs.tps;
   double *part = nullptr;
   OB_TRY(b.workspace(nsplit * kNHB * t.p_pad * sizeof(double), (void **)&part));
   ProfScope ps(squared ? "sqtmm_gradhyp_dense" : "tmm_gradhyp_dense");
   for (int h0 = 0; h0 < nhyp; h0 += kNHB) {
     const int nh = std::min(kNHB, nhyp - h0);
-    if (squared)
-      hipLaunchKernelGGL(k_bt_times_u<true>, dim3((unsigned)nsplit, gy), dim3(512), 0, cur_stream(),
-                         b.bmat.p, t.p_pad, src.bm.p, src.md.Mc, dc0.p, nhyp, h0, d_a, b.n, ntiles,
-                         tps, part);
-    else
-      hipLaunchKernelGGL(k_bt_times_u<false>, dim3((unsigned)nsplit, gy), dim3(512), 0, cur_stream(),
-                         b.bmat.p, t.p_pad, src.bm.p, src.md.Mc, dc0.p, nhyp, h0, d_a, b.n, ntiles,
-                         tps, part);
+    pick_bool(squared, [&](auto SQ) {
+      hipLaunchKernelGGL(k_bt_times_u<SQ()>, dim3((unsigned)nsplit, gy), dim3(512), 0, cur_stream(), b.bmat.p,
+                         t.p_pad, src.bm.p, src.md.Mc, dc0.p, nhyp, h0, d_a, b.n, ntiles, tps, part);
+      return 0;
+    });
     hipLaunchKernelGGL(k_btu_reduce, dim3((unsigned)((t.p + 255) / 256), (unsigned)nh), dim3(256), 0,
                        cur_stream(), part, (int)nsplit, t.p_pad, (int)t.p, nh,
                        d_out + (uint64_t)h0 * t.p);

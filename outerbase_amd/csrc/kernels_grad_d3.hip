@@ -213,27 +213,6 @@ k_tmm_d3(const double *__restrict__ bm, const double *__restrict__ scale,
 
 }  // namespace
 
-namespace {
-template <int W2, int NH, int NU, int MODE, bool PF, int NW>
-int run_tmm_d3(const obhip_basis &src, const obhip_terms &v, const double *d_w1, const double *d_w2, dim3 grid,
-               uint64_t ntiles, uint64_t tps, double *part) {
-  const size_t lds = v.Mu * kTlPitch * sizeof(double);
-  if (lds > 64 * 1024) OB_TRY(ensure_dyn_lds((const void *)k_tmm_d3<W2, NH, NU, MODE, PF, NW>, lds));
-  hipLaunchKernelGGL((k_tmm_d3<W2, NH, NU, MODE, PF, NW>), grid, dim3(NW * 64), lds, cur_stream(), src.bm.p,
-                     src.scale.p, v.ucol.p, (int)v.Mu, src.md.Mc, (const uint32_t *)v.cols.p, v.sperm.p, d_w1,
-                     d_w2, src.n, ntiles, tps, v.p_pad, part);
-  OB_HIP(hipGetLastError());
-  return 0;
-}
-template <int W2, int NH, int NU, bool PF, int NW>
-int run_tmm_d3_mode(int mode, const obhip_basis &src, const obhip_terms &v, const double *d_w1, const double *d_w2,
-                    dim3 grid, uint64_t ntiles, uint64_t tps, double *part) {
-  if (mode == 1) return run_tmm_d3<W2, NH, NU, 1, PF, NW>(src, v, d_w1, d_w2, grid, ntiles, tps, part);
-  if (mode == 2) return run_tmm_d3<W2, NH, NU, 2, PF, NW>(src, v, d_w1, d_w2, grid, ntiles, tps, part);
-  return run_tmm_d3<W2, NH, NU, 3, PF, NW>(src, v, d_w1, d_w2, grid, ntiles, tps, part);
-}
-}  // namespace
-
 // d_out (device, [2 nh][v.p]: u1 of the group's first hyper-parameter, of its second, u2 likewise;
 // the rows a mode does not compute are left alone) for one group of build_d3_groups
 int launch_tmm_d3(obhip_basis &b, const obhip_terms::GeD3 &g, int mode, const double *d_w1, const double *d_w2,
@@ -247,34 +226,31 @@ int launch_tmm_d3(obhip_basis &b, const obhip_terms::GeD3 &g, int mode, const do
   // against 1.91 at C3 (half the row-weight v_readlanes per view-term).  Also measured: 2 per lane
   // without prefetch 1.27, 16 waves x 1 per lane 1.42 (before the weights went into the staged columns).
   static const int variant = getenv("OBHIP_D3_VARIANT") ? atoi(getenv("OBHIP_D3_VARIANT")) : 1;
-  const int nw = 8;
+  constexpr int nw = 8;
   const int nu = variant == 1 && v.p_pad > 1024 ? 4 : 2;
   const uint64_t tpb = (uint64_t)nw * nu * 64;
   const uint64_t pblocks = (v.p_pad + tpb - 1) / tpb;
-  uint64_t nsplit = std::max<uint64_t>(1, (uint64_t)device_cus(b.device) * 2 / pblocks);
-  nsplit = std::min(nsplit, std::max<uint64_t>(1, ntiles / 4));
-  const uint64_t tps = (ntiles + nsplit - 1) / nsplit;
-  nsplit = (ntiles + tps - 1) / tps;
+  // two resident blocks per CU, one round
+  const RowSplit rs = split_rows(ntiles, (uint64_t)device_cus(b.device) * 2 / pblocks, 4);
+  const uint64_t nsplit = rs.nsplit, tps = rs.tps;
   const int nc = 2 * g.nh;
   double *part = nullptr;
   OB_TRY(b.workspace(nsplit * nc * v.p_pad * sizeof(double), (void **)&part));
   const dim3 grid((unsigned)nsplit, (unsigned)pblocks);
   {
     ProfScope ps("tmm_d3");
-#define OB_D3(W2_, NH_)                                                                                      \
-  do {                                                                                                       \
-    if (nu == 4)                                                                                             \
-      OB_TRY((run_tmm_d3_mode<W2_, NH_, 4, false, 8>(mode, src, v, d_w1, d_w2, grid, ntiles, tps, part)));   \
-    else                                                                                                     \
-      OB_TRY((run_tmm_d3_mode<W2_, NH_, 2, true, 8>(mode, src, v, d_w1, d_w2, grid, ntiles, tps, part)));    \
-  } while (0)
-    const int w2 = (int)(v.W / 2);
-    if (g.nh == 1) {
-      if (w2 == 2) OB_D3(2, 1); else if (w2 == 3) OB_D3(3, 1); else OB_D3(4, 1);
-    } else {
-      if (w2 == 2) OB_D3(2, 2); else if (w2 == 3) OB_D3(3, 2); else OB_D3(4, 2);
-    }
-#undef OB_D3
+    const size_t lds = v.Mu * kTlPitch * sizeof(double);
+    OB_TRY(pick<2, 3, 4>((int)(v.W / 2), [&](auto W2) {
+      return pick<1, 2>(g.nh, [&](auto NH) {
+        return pick<1, 2, 3>(mode, [&](auto MODE) {
+          return pick<4, 2>(nu, [&](auto NU) {
+            constexpr bool PF = NU() == 2;  // 2 per lane: the tile prefetched into registers
+            return launch_prod(k_tmm_d3<W2(), NH(), NU(), MODE(), PF, nw>, grid, dim3(nw * 64), lds,
+                               prod_tabs(src, v), v.sperm.p, d_w1, d_w2, src.n, ntiles, tps, v.p_pad, part);
+          });
+        });
+      });
+    }));
   }
   // the rows of the other mode hold whatever the workspace held: reduce only what was computed
   const int r0 = (mode & 1) ? 0 : g.nh, r1 = (mode & 2) ? nc : g.nh;

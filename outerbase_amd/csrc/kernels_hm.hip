@@ -312,23 +312,13 @@ int run_hm2(const obhip_basis &b, obhip_terms &t, const double *d_a, const doubl
             double *part, double *d_yhat, double *sspart, unsigned nsplit, uint64_t ntiles, uint64_t tps,
             size_t lds, const double *stop0, const double *stop1) {
   // (the update() form carries y, yhat and the residual sum: 8 reads in flight keep it free of spills)
-#define OB_HM2_LAUNCH(RO_)                                                                                  \
-  do {                                                                                                      \
-    constexpr int IF = RO_ && NU >= 4 ? 8 : INFL;                                                           \
-    constexpr bool SI = SIN && !(RO_ && NU >= 4);                                                           \
-    OB_TRY(ensure_dyn_lds((const void *)k_hm2<W2, NU, WAVES, IF, RO_, SI>, lds));                           \
-    hipLaunchKernelGGL((k_hm2<W2, NU, WAVES, IF, RO_, SI>), dim3(nsplit), dim3(WAVES * 64), lds, cur_stream(), \
-                       b.bm.p, b.scale.p, t.ucol.p, (int)t.Mu, b.md.Mc, (const uint32_t *)t.cols.p,         \
-                       t.sperm.p, d_a, (int)t.p, d_y, ca, cb, b.n, ntiles, tps, t.p_pad, part, d_yhat,      \
-                       sspart, stop0, stop1);                                                               \
-  } while (0)
-  if (d_y != nullptr)
-    OB_HM2_LAUNCH(true);
-  else
-    OB_HM2_LAUNCH(false);
-#undef OB_HM2_LAUNCH
-  OB_HIP(hipGetLastError());
-  return 0;
+  return pick_bool(d_y != nullptr, [&](auto RO) {
+    constexpr int IF = RO() && NU >= 4 ? 8 : INFL;
+    constexpr bool SI = SIN && !(RO() && NU >= 4);
+    return launch_prod(k_hm2<W2, NU, WAVES, IF, RO(), SI>, dim3(nsplit), dim3(WAVES * 64), lds, prod_tabs(b, t),
+                       t.sperm.p, d_a, (int)t.p, d_y, ca, cb, b.n, ntiles, tps, t.p_pad, part, d_yhat, sspart, stop0,
+                       stop1);
+  });
 }
 
 }  // namespace
@@ -354,7 +344,7 @@ size_t hm2_lds_bytes(const obhip_terms &t, bool ro, int variant) {
 // coefficients live in LDS too
 bool hm2_supports(const obhip_terms &t, bool ro, int variant) {
   const int w2 = (int)(t.W / 2);
-  return w2 >= 1 && w2 <= 3 && t.p_pad <= 4096 && hm2_lds_bytes(t, ro, variant) <= (size_t)156 * 1024;
+  return w2 >= 1 && w2 <= 3 && t.p_pad <= 4096 && hm2_lds_bytes(t, ro, variant) <= kLdsTile;
 }
 
 // variant: 0 = automatic; experiments at 4-factor terms (OBHIP_HM2_VARIANT): 2 = 12 waves x 6

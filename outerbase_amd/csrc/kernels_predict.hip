@@ -235,85 +235,57 @@ k_predict_tl(const DimDesc *__restrict__ dims, const double *__restrict__ ka,
   if (t0 < t1 && wave == 0) emit(t1 - 1, s_cur);
 }
 
-template <int W2, int NG, bool VAR>
-int run_predict_tl(const obhip_model &m, obhip_terms &t, const double *d_theta, const double *d_x,
-                   uint64_t n, double *d_mean, const double *d_coeffvar, double e2sigma,
-                   double *d_var, int npass) {
-  const size_t lds = (t.Mu * kTlPitch + 3 * kTlWaves * kTileRows) * sizeof(double);
-  OB_TRY(ensure_dyn_lds((const void *)k_predict_tl<W2, NG, VAR>, lds));
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const int ncu = device_cus(dev);
-  const uint64_t ntiles = (n + kTileRows - 1) / kTileRows;
-  uint64_t nsplit = std::min<uint64_t>(ntiles, (uint64_t)ncu * 4);
-  const uint64_t tps = (ntiles + nsplit - 1) / nsplit;
-  nsplit = (ntiles + tps - 1) / tps;
-  launch_pred<false>(k_predict_tl<W2, NG, VAR>, dim3((unsigned)nsplit), dim3(kTlThreads), lds, pred_tabs(m, t),
-                     (const uint32_t *)t.cols.p, t.sperm.p, (int)t.p, t.p_pad, npass, d_theta, d_coeffvar, e2sigma,
-                     d_x, n, ntiles, tps, d_mean, d_var);
-  OB_HIP(hipGetLastError());
-  return 0;
+size_t predict_tl_lds_bytes(const obhip_terms &t) {
+  return (t.Mu * kTlPitch + 3 * kTlWaves * kTileRows) * sizeof(double);
 }
 
-template <bool VAR>
-int dispatch_predict_tl(const obhip_model &m, obhip_terms &t, const double *d_theta,
-                        const double *d_x, uint64_t n, double *d_mean, const double *d_coeffvar,
-                        double e2sigma, double *d_var) {
-  // the variance form carries twice the accumulators and coefficients: half the terms per lane
-  const int ngmax = (t.W / 2 <= 2 ? 8 : 4) / (VAR ? 2 : 1);
-  int ng = 1;
-  while (ng < ngmax && (uint64_t)kTlWaves * ng * 64 < t.p_pad) ng *= 2;
+// k_predict_tl: the terms in passes of 8 waves x NG groups x 64
+int run_predict_tl(const obhip_model &m, obhip_terms &t, const double *d_theta, const double *d_x, uint64_t n,
+                   double *d_mean, const double *d_coeffvar, double e2sigma, double *d_var) {
+  const bool var = d_coeffvar != nullptr && d_var != nullptr;
+  const int w2 = (int)(t.W / 2);
+  const int ng = units_per_lane(t.p_pad, (uint64_t)kTlWaves * 64, predict_tl_max_units(w2, var));
   const uint64_t tpb = (uint64_t)kTlWaves * ng * 64;
   const int npass = (int)((t.p_pad + tpb - 1) / tpb);
-#define OB_PR(W2_, NG_) \
-  return run_predict_tl<W2_, NG_, VAR>(m, t, d_theta, d_x, n, d_mean, d_coeffvar, e2sigma, d_var, npass)
-  // (the larger NG only exist without the variance)
-  switch (t.W / 2) {
-    case 1:
-      if constexpr (!VAR) if (ng == 8) OB_PR(1, 8);
-      if (ng == 4) OB_PR(1, 4);
-      if (ng == 2) OB_PR(1, 2);
-      OB_PR(1, 1);
-    case 2:
-      if constexpr (!VAR) if (ng == 8) OB_PR(2, 8);
-      if (ng == 4) OB_PR(2, 4);
-      if (ng == 2) OB_PR(2, 2);
-      OB_PR(2, 1);
-    case 3:
-      if constexpr (!VAR) if (ng == 4) OB_PR(3, 4);
-      if (ng == 2) OB_PR(3, 2);
-      OB_PR(3, 1);
-    default:
-      if constexpr (!VAR) if (ng == 4) OB_PR(4, 4);
-      if (ng == 2) OB_PR(4, 2);
-      OB_PR(4, 1);
-  }
-#undef OB_PR
+  const size_t lds = predict_tl_lds_bytes(t);
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const uint64_t ntiles = (n + kTileRows - 1) / kTileRows;
+  const RowSplit rs = split_rows(ntiles, (uint64_t)device_cus(dev) * 4);
+  return pick<1, 2, 3, 4>(w2, [&](auto W2) {
+    return pick_bool(var, [&](auto VAR) {
+      return pick<8, 4, 2, 1>(ng, [&](auto NG) {
+        if constexpr (NG() > predict_tl_max_units(W2(), VAR())) return no_kernel();
+        else {
+          constexpr auto kernel = k_predict_tl<W2(), NG(), VAR()>;
+          OB_TRY(ensure_dyn_lds((const void *)kernel, lds));
+          launch_pred<false>(kernel, dim3((unsigned)rs.nsplit), dim3(kTlThreads), lds, pred_tabs(m, t),
+                             (const uint32_t *)t.cols.p, t.sperm.p, (int)t.p, t.p_pad, npass, d_theta, d_coeffvar,
+                             e2sigma, d_x, n, ntiles, rs.tps, d_mean, d_var);
+          OB_HIP(hipGetLastError());
+          return 0;
+        }
+      });
+    });
+  });
 }
 
-template <int W2, bool VAR>
-int run_predict(const obhip_model &m, obhip_terms &t, const double *d_theta, const double *d_x,
-                uint64_t n, double *d_mean, const double *d_coeffvar, double e2sigma, double *d_var) {
+// k_predict: lane = row
+int run_predict(const obhip_model &m, obhip_terms &t, const double *d_theta, const double *d_x, uint64_t n,
+                double *d_mean, const double *d_coeffvar, double e2sigma, double *d_var) {
   const size_t lds = (t.Mu * kTileRows + 2 * kPrWaves * kTileRows) * sizeof(double);
-  OB_TRY(ensure_dyn_lds((const void *)k_predict<W2, VAR>, lds));
-  launch_pred<false>(k_predict<W2, VAR>, dim3((unsigned)((n + kTileRows - 1) / kTileRows)), dim3(kPrThreads), lds,
-                     pred_tabs(m, t), (const uint32_t *)t.cols.p, (int)(t.W / 2), (int)t.p, d_theta, d_coeffvar,
-                     e2sigma, d_x, n, d_mean, d_var);
-  OB_HIP(hipGetLastError());
-  return 0;
-}
-
-template <bool VAR>
-int dispatch_predict(const obhip_model &m, obhip_terms &t, const double *d_theta, const double *d_x,
-                     uint64_t n, double *d_mean, const double *d_coeffvar, double e2sigma,
-                     double *d_var) {
-  switch (t.W / 2) {
-    case 1: return run_predict<1, VAR>(m, t, d_theta, d_x, n, d_mean, d_coeffvar, e2sigma, d_var);
-    case 2: return run_predict<2, VAR>(m, t, d_theta, d_x, n, d_mean, d_coeffvar, e2sigma, d_var);
-    case 3: return run_predict<3, VAR>(m, t, d_theta, d_x, n, d_mean, d_coeffvar, e2sigma, d_var);
-    case 4: return run_predict<4, VAR>(m, t, d_theta, d_x, n, d_mean, d_coeffvar, e2sigma, d_var);
-    default: return run_predict<0, VAR>(m, t, d_theta, d_x, n, d_mean, d_coeffvar, e2sigma, d_var);
-  }
+  const int w2 = (int)(t.W / 2);
+  return pick<1, 2, 3, 4, 0>(w2, [&](auto W2) {
+    return pick_bool(d_coeffvar != nullptr && d_var != nullptr, [&](auto VAR) {
+      constexpr auto kernel = k_predict<W2(), VAR()>;
+      OB_TRY(ensure_dyn_lds((const void *)kernel, lds));
+      launch_pred<false>(kernel, dim3((unsigned)((n + kTileRows - 1) / kTileRows)), dim3(kPrThreads), lds,
+                         pred_tabs(m, t), (const uint32_t *)t.cols.p, w2, (int)t.p, d_theta, d_coeffvar, e2sigma, d_x, n,
+                         d_mean, d_var);
+      OB_HIP(hipGetLastError());
+      return 0;
+    });
+  });
 }
 
 }  // namespace
@@ -342,15 +314,9 @@ int launch_predict(const obhip_model &m, obhip_terms &t, const double *d_theta, 
   if (!lane_row && !no_star && star_predict_supports(t))  // shared sub-products (kernels_star.hip)
     return launch_star_predict(m, t, d_theta, d_x, n, d_mean, d_coeffvar, e2sigma, d_var);
   const int w2 = (int)(t.W / 2);
-  if (!lane_row && w2 >= 1 && w2 <= 4 &&
-      (t.Mu * kTlPitch + 3 * kTlWaves * kTileRows) * sizeof(double) <= 156 * 1024) {
-    if (d_coeffvar != nullptr && d_var != nullptr)
-      return dispatch_predict_tl<true>(m, t, d_theta, d_x, n, d_mean, d_coeffvar, e2sigma, d_var);
-    return dispatch_predict_tl<false>(m, t, d_theta, d_x, n, d_mean, d_coeffvar, e2sigma, d_var);
-  }
-  if (d_coeffvar != nullptr && d_var != nullptr)
-    return dispatch_predict<true>(m, t, d_theta, d_x, n, d_mean, d_coeffvar, e2sigma, d_var);
-  return dispatch_predict<false>(m, t, d_theta, d_x, n, d_mean, d_coeffvar, e2sigma, d_var);
+  if (!lane_row && w2 >= 1 && w2 <= 4 && predict_tl_lds_bytes(t) <= kLdsTile)
+    return run_predict_tl(m, t, d_theta, d_x, n, d_mean, d_coeffvar, e2sigma, d_var);
+  return run_predict(m, t, d_theta, d_x, n, d_mean, d_coeffvar, e2sigma, d_var);
 }
 
 }  // namespace obhip

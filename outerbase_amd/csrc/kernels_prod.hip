@@ -991,66 +991,133 @@ k_tmm_reduce_q(const double *__restrict__ part, int nsplit, uint64_t p_pad, int 
   }
 }
 
-template <typename K>
-int set_lds(K kernel, size_t bytes) {
-  return ensure_dyn_lds((const void *)kernel, bytes);
-}
-
 // more used columns than one LDS tile holds: the generic kernels (kernels_generic.hip)
 bool beyond_lds(const obhip_terms &t) {
   return t.Mu > (uint64_t)kMaxMuLds || getenv("OBHIP_FORCE_GENERIC") != nullptr;  // env: tests
 }
 
-template <int W2, int MODE>
-int run_mm(const obhip_basis &b, obhip_terms &t, const double *d_a, double *d_out, uint64_t ld) {
-  const size_t lds = (t.Mu * kTileRows + kMmWaves * kTileRows) * sizeof(double);
-  OB_TRY(set_lds(k_mm<W2, MODE>, lds));
-  hipLaunchKernelGGL((k_mm<W2, MODE>), dim3((unsigned)(b.n_pad / kTileRows)), dim3(kMmThreads), lds,
-                     cur_stream(), b.bm.p, b.scale.p, t.ucol.p, (int)t.Mu, b.md.Mc,
-                     (const uint32_t *)t.cols.p, (int)(t.W / 2), (int)t.p, d_a, d_out, b.n, ld);
+// LDS bytes of the term-per-lane families: what their *_supports bound and their launches ask for
+size_t mm_tl_lds_bytes(const obhip_terms &t) { return (t.Mu * kTlPitch + kTlWaves * kTileRows) * sizeof(double); }
+size_t tmm_tl_lds_bytes(const obhip_terms &t) { return t.Mu * kTlPitch * sizeof(double); }  // and k_materialize_tl
+size_t hm_tl_lds_bytes(const obhip_terms &t) {
+  return (t.Mu * kTlPitch + 2 * kTlWaves * kHmChunk) * sizeof(double);
+}
+
+// d_out (p) = the sum of the row-split partials part[nsplit][p_pad]; with `then` q = e2 d_out + prec pv as well
+int reduce_partials(const double *part, uint64_t nsplit, const obhip_terms &t, double *d_out,
+                    const HmThen *then = nullptr) {
+  const dim3 grid((unsigned)((t.p + 63) / 64));
+  if (then)
+    hipLaunchKernelGGL(k_tmm_reduce_q, grid, dim3(kRedThreads), 0, cur_stream(), part, (int)nsplit, t.p_pad,
+                       (int)t.p, d_out, then->e2, then->prec, then->pv, then->q);
+  else
+    hipLaunchKernelGGL(k_tmm_reduce, grid, dim3(kRedThreads), 0, cur_stream(), part, (int)nsplit, t.p_pad, (int)t.p,
+                       d_out);
   OB_HIP(hipGetLastError());
   return 0;
 }
 
-template <int MODE>
-int dispatch_mm(const obhip_basis &b, obhip_terms &t, const double *d_a, double *d_out,
-                uint64_t ld = 0) {
-  switch (t.W / 2) {
-    case 1: return run_mm<1, MODE>(b, t, d_a, d_out, ld);
-    case 2: return run_mm<2, MODE>(b, t, d_a, d_out, ld);
-    case 3: return run_mm<3, MODE>(b, t, d_a, d_out, ld);
-    case 4: return run_mm<4, MODE>(b, t, d_a, d_out, ld);
-    default: return run_mm<0, MODE>(b, t, d_a, d_out, ld);
-  }
+// d_out (n) = basescale x the sum of the unscaled row sums mpart[pblocks][n_pad] (squared: basescale^2)
+int sum_mm_partials(const obhip_basis &b, const double *mpart, uint64_t pblocks, bool squared, double *d_out) {
+  return pick_bool(squared, [&](auto SQ) {
+    hipLaunchKernelGGL(k_mm_tl_sum<SQ()>, dim3((unsigned)((b.n + 255) / 256)), dim3(256), 0, cur_stream(), mpart,
+                       (int)pblocks, b.n_pad, b.scale.p, b.n, d_out);
+    OB_HIP(hipGetLastError());
+    return 0;
+  });
 }
 
-template <int W2, bool SQ, bool PF>
-int run_tmm(const obhip_basis &b, obhip_terms &t, const double *d_a, double *part, dim3 grid,
+// k_mm: lane = row.  mode 0: B a, 1: B^2 a, 2: B itself, column-major with leading dimension ld
+int run_mm(const obhip_basis &b, obhip_terms &t, int mode, const double *d_a, double *d_out, uint64_t ld = 0) {
+  const size_t lds = (t.Mu * kTileRows + kMmWaves * kTileRows) * sizeof(double);
+  const int w2 = (int)(t.W / 2);
+  return pick<1, 2, 3, 4, 0>(w2, [&](auto W2) {
+    return pick<0, 1, 2>(mode, [&](auto MODE) {
+      return launch_prod(k_mm<W2(), MODE()>, dim3((unsigned)(b.n_pad / kTileRows)), dim3(kMmThreads), lds,
+                         prod_tabs(b, t), w2, (int)t.p, d_a, d_out, b.n, ld);
+    });
+  });
+}
+
+// k_tmm: lane = row, 256 terms per block
+int run_tmm(const obhip_basis &b, obhip_terms &t, bool squared, const double *d_a, double *part, dim3 grid,
             uint64_t ntiles, uint64_t tps) {
   const size_t lds = t.Mu * kTileRows * sizeof(double) + t.Mu * sizeof(int);
-  OB_TRY(set_lds(k_tmm<W2, SQ, PF>, lds));
-  hipLaunchKernelGGL((k_tmm<W2, SQ, PF>), grid, dim3(256), lds, cur_stream(), b.bm.p, b.scale.p,
-                     t.ucol.p, (int)t.Mu, b.md.Mc, (const uint32_t *)t.cols.p, (int)(t.W / 2), d_a,
-                     b.n, ntiles, tps, t.p_pad, part);
-  OB_HIP(hipGetLastError());
-  return 0;
+  const int w2 = (int)(t.W / 2);
+  // (the form for any width, W2 = 0, has no prefetch)
+  const bool pf = w2 >= 1 && w2 <= kMaxW2 && t.Mu <= 4 * (uint64_t)kTmmPre;
+  return pick<1, 2, 3, 4, 0>(w2, [&](auto W2) {
+    return pick_bool(pf, [&](auto PF) {
+      if constexpr (W2() == 0 && PF()) return no_kernel();
+      else
+        return pick_bool(squared, [&](auto SQ) {
+          return launch_prod(k_tmm<W2(), SQ(), PF()>, grid, dim3(256), lds, prod_tabs(b, t), w2, d_a, b.n, ntiles,
+                             tps, t.p_pad, part);
+        });
+    });
+  });
 }
 
-template <bool SQ>
-int dispatch_tmm(const obhip_basis &b, obhip_terms &t, const double *d_a, double *part, dim3 grid,
-                 uint64_t ntiles, uint64_t tps) {
-  const bool pf = t.Mu <= 4 * (uint64_t)kTmmPre;
-  switch (t.W / 2) {
-    case 1: return pf ? run_tmm<1, SQ, true>(b, t, d_a, part, grid, ntiles, tps)
-                      : run_tmm<1, SQ, false>(b, t, d_a, part, grid, ntiles, tps);
-    case 2: return pf ? run_tmm<2, SQ, true>(b, t, d_a, part, grid, ntiles, tps)
-                      : run_tmm<2, SQ, false>(b, t, d_a, part, grid, ntiles, tps);
-    case 3: return pf ? run_tmm<3, SQ, true>(b, t, d_a, part, grid, ntiles, tps)
-                      : run_tmm<3, SQ, false>(b, t, d_a, part, grid, ntiles, tps);
-    case 4: return pf ? run_tmm<4, SQ, true>(b, t, d_a, part, grid, ntiles, tps)
-                      : run_tmm<4, SQ, false>(b, t, d_a, part, grid, ntiles, tps);
-    default: return run_tmm<0, SQ, false>(b, t, d_a, part, grid, ntiles, tps);
-  }
+// k_mm_tl: a block of 8 waves x ng groups x 64 terms
+int run_mm_tl(const obhip_basis &b, obhip_terms &t, bool squared, int ng, const double *d_a, double *d_out,
+              double *part, dim3 grid, uint64_t ntiles, uint64_t tps) {
+  const bool pf = t.Mu <= (uint64_t)kTlWaves * kTlPre;
+  return pick<1, 2, 3, 4>((int)(t.W / 2), [&](auto W2) {
+    return pick<8, 4, 2, 1>(ng, [&](auto NG) {
+      if constexpr (NG() > tl_max_units(W2())) return no_kernel();
+      else
+        return pick_bool(squared, [&](auto SQ) {
+          return pick_bool(pf, [&](auto PF) {
+            return launch_prod(k_mm_tl<W2(), SQ(), NG(), PF()>, grid, dim3(kTlThreads), mm_tl_lds_bytes(t),
+                               prod_tabs(b, t), t.sperm.p, d_a, (int)t.p, b.n, b.n_pad, ntiles, tps, t.p_pad, d_out,
+                               part);
+          });
+        });
+    });
+  });
+}
+
+// k_tmm_tl: terms per block 8 waves x npair x 2 groups of 64.  part2 non-null: the DUAL form (part2 = partial
+// (B^2)^T a2 from the same products; it exists for W2 <= 3 and has no squared form of its own)
+int run_tmm_tl(const obhip_basis &b, obhip_terms &t, bool squared, bool pf, int npair, const double *d_a,
+               double *part, const double *d_a2, double *part2, const RowSplit &rs, uint64_t ntiles) {
+  const uint64_t tpb = (uint64_t)kTlWaves * npair * kTlGP * 64;
+  const dim3 grid((unsigned)rs.nsplit, (unsigned)((t.p_pad + tpb - 1) / tpb));
+  return pick<1, 2, 3, 4>((int)(t.W / 2), [&](auto W2) {
+    return pick<4, 2, 1>(npair, [&](auto NP) {
+      return pick_bool(part2 != nullptr, [&](auto DUAL) {
+        return pick_bool(squared, [&](auto SQ) {
+          if constexpr (NP() > tl_max_pairs(W2()) || (DUAL() && (SQ() || W2() > 3))) return no_kernel();
+          else
+            return pick_bool(pf, [&](auto PF) {
+              return launch_prod(k_tmm_tl<W2(), SQ(), NP(), PF(), DUAL()>, grid, dim3(kTlThreads),
+                                 tmm_tl_lds_bytes(t), prod_tabs(b, t), t.sperm.p, d_a, b.n, ntiles, rs.tps, t.p_pad,
+                                 part, d_a2, part2);
+            });
+        });
+      });
+    });
+  });
+}
+
+// the units of k_tmm_tl for t and the row split of its launch: the fewest blocks along p that the
+// register budget allows; two resident blocks per CU, one round
+RowSplit tmm_tl_plan(const obhip_basis &b, const obhip_terms &t, uint64_t ntiles, int &npair) {
+  npair = units_per_lane(t.p_pad, (uint64_t)kTlWaves * kTlGP * 64, tl_max_pairs((int)(t.W / 2)));
+  const uint64_t tpb = (uint64_t)kTlWaves * npair * kTlGP * 64;
+  const uint64_t pblocks = (t.p_pad + tpb - 1) / tpb;
+  return split_rows(ntiles, (uint64_t)device_cus(b.device) * 2 / pblocks, 4);
+}
+
+bool hm3_wanted() {
+  static const bool off = getenv("OBHIP_HM3") && atoi(getenv("OBHIP_HM3")) == 0;
+  return !off;
+}
+// one workgroup per CU (two tiles of the used columns in LDS), a range of tiles each; the terms in
+// workgroups of 16 star-waves
+RowSplit star_grid(const obhip_basis &b, const obhip_terms &t, uint64_t ntiles, uint64_t &pblocks) {
+  pblocks = (t.sh.nsw_family + 15) / 16;
+  return split_rows(ntiles, (uint64_t)device_cus(b.device) / pblocks, 4);
 }
 
 }  // namespace
@@ -1061,193 +1128,55 @@ int launch_getmat(const obhip_basis &b, obhip_terms &t, double *d_out, uint64_t 
   if (ld == 0) ld = b.n;
   ProfScope ps("getmat");
   if (beyond_lds(t)) return launch_mm_generic(b, t, nullptr, d_out, 2, ld);
-  return dispatch_mm<2>(b, t, nullptr, d_out, ld);
+  return run_mm(b, t, 2, nullptr, d_out, ld);
 }
-
-
-template <int W2, bool SQ, int NG>
-int run_mm_tl(const obhip_basis &b, obhip_terms &t, const double *d_a, double *d_out, double *part,
-              dim3 grid, uint64_t ntiles, uint64_t tps) {
-  const size_t lds = (t.Mu * kTlPitch + kTlWaves * kTileRows) * sizeof(double);
-  const bool pf = t.Mu <= (uint64_t)kTlWaves * kTlPre;
-  if (pf) {
-    OB_TRY(set_lds(k_mm_tl<W2, SQ, NG, true>, lds));
-    hipLaunchKernelGGL((k_mm_tl<W2, SQ, NG, true>), grid, dim3(kTlThreads), lds, cur_stream(), b.bm.p,
-                       b.scale.p, t.ucol.p, (int)t.Mu, b.md.Mc, (const uint32_t *)t.cols.p, t.sperm.p,
-                       d_a, (int)t.p, b.n, b.n_pad, ntiles, tps, t.p_pad, d_out, part);
-  } else {
-    OB_TRY(set_lds(k_mm_tl<W2, SQ, NG, false>, lds));
-    hipLaunchKernelGGL((k_mm_tl<W2, SQ, NG, false>), grid, dim3(kTlThreads), lds, cur_stream(), b.bm.p,
-                       b.scale.p, t.ucol.p, (int)t.Mu, b.md.Mc, (const uint32_t *)t.cols.p, t.sperm.p,
-                       d_a, (int)t.p, b.n, b.n_pad, ntiles, tps, t.p_pad, d_out, part);
-  }
-  OB_HIP(hipGetLastError());
-  return 0;
-}
-
-template <bool SQ>
-int dispatch_mm_tl(const obhip_basis &b, obhip_terms &t, const double *d_a, double *d_out,
-                   double *part, dim3 grid, int ng, uint64_t ntiles, uint64_t tps) {
-#define OB_ML(W2_, NG_) return run_mm_tl<W2_, SQ, NG_>(b, t, d_a, d_out, part, grid, ntiles, tps)
-  switch (t.W / 2) {
-    case 1: if (ng == 8) OB_ML(1, 8); if (ng == 4) OB_ML(1, 4); if (ng == 2) OB_ML(1, 2); OB_ML(1, 1);
-    case 2: if (ng == 8) OB_ML(2, 8); if (ng == 4) OB_ML(2, 4); if (ng == 2) OB_ML(2, 2); OB_ML(2, 1);
-    case 3: if (ng == 4) OB_ML(3, 4); if (ng == 2) OB_ML(3, 2); OB_ML(3, 1);
-    default: if (ng == 4) OB_ML(4, 4); if (ng == 2) OB_ML(4, 2); OB_ML(4, 1);
-  }
-#undef OB_ML
-}
-
-namespace {
-bool hm3_wanted() {
-  static const bool off = getenv("OBHIP_HM3") && atoi(getenv("OBHIP_HM3")) == 0;
-  return !off;
-}
-// one workgroup per CU (two tiles of the used columns in LDS), a range of tiles each; the terms in
-// workgroups of 16 star-waves
-void star_grid(const obhip_basis &b, const obhip_terms &t, uint64_t &nsplit, uint64_t &pblocks, uint64_t &ntiles,
-               uint64_t &tps) {
-  ntiles = b.n_pad / kTileRows;
-  pblocks = (t.sh.nsw_family + 15) / 16;
-  nsplit = std::max<uint64_t>(1, (uint64_t)device_cus(b.device) / pblocks);
-  nsplit = std::min(nsplit, std::max<uint64_t>(1, ntiles / 4));
-  tps = (ntiles + nsplit - 1) / nsplit;
-  nsplit = (ntiles + tps - 1) / tps;
-}
-}  // namespace
 
 int mm_tl_supports(const obhip_terms &t) {
   const int w2 = (int)(t.W / 2);
-  return w2 >= 1 && w2 <= kMaxW2 &&
-         (t.Mu * kTlPitch + kTlWaves * kTileRows) * sizeof(double) <= 156 * 1024;
+  return w2 >= 1 && w2 <= kMaxW2 && mm_tl_lds_bytes(t) <= kLdsTile;
 }
 
 int launch_mm(const obhip_basis &b, obhip_terms &t, const double *d_a, double *d_out, bool squared) {
   OB_TRY(t.prepare(b.md.cap, b.md.dims_h));
-  if (beyond_lds(t)) {
-    ProfScope ps(squared ? "sqmm" : "mm");
-    return launch_mm_generic(b, t, d_a, d_out, squared ? 1 : 0, 0);
-  }
   static const bool force_rows = getenv("OBHIP_MM_LANE_ROW") != nullptr;
-  if (!force_rows && hm3_wanted() && star_supports(t, false)) {  // shared sub-products (kernels_star.hip)
-    uint64_t nsplit, pblocks, ntiles, tps;
-    star_grid(b, t, nsplit, pblocks, ntiles, tps);
-    double *mpart = nullptr;
-    if (pblocks > 1)
-      OB_TRY(const_cast<obhip_basis &>(b).workspace(pblocks * b.n_pad * sizeof(double), (void **)&mpart));
-    ProfScope ps(squared ? "sqmm" : "mm");
-    OB_TRY(launch_star_mm(b, t, d_a, squared, d_out, mpart, (unsigned)nsplit, ntiles, tps));
-    if (pblocks > 1) {
-      const dim3 g2((unsigned)((b.n + 255) / 256));
-      if (squared)
-        hipLaunchKernelGGL(k_mm_tl_sum<true>, g2, dim3(256), 0, cur_stream(), mpart, (int)pblocks, b.n_pad,
-                           b.scale.p, b.n, d_out);
-      else
-        hipLaunchKernelGGL(k_mm_tl_sum<false>, g2, dim3(256), 0, cur_stream(), mpart, (int)pblocks, b.n_pad,
-                           b.scale.p, b.n, d_out);
-      OB_HIP(hipGetLastError());
-    }
-    return 0;
-  }
-  if (!mm_tl_supports(t) || force_rows) {
-    ProfScope ps(squared ? "sqmm" : "mm");
-    return squared ? dispatch_mm<1>(b, t, d_a, d_out) : dispatch_mm<0>(b, t, d_a, d_out);
-  }
-  // term-per-lane kernel: a block of 8 waves x NG groups x 64 terms, as few blocks along p
-  // as the register budget allows
-  const int ngmax = t.W / 2 <= 2 ? 8 : 4;
-  int ng = 1;
-  while (ng < ngmax && (uint64_t)kTlWaves * ng * 64 < t.p_pad) ng *= 2;
-  const uint64_t tpb = (uint64_t)kTlWaves * ng * 64;
-  const uint64_t pblocks = (t.p_pad + tpb - 1) / tpb;
+  enum { kGeneric, kStar, kRows, kTl } path = kTl;
+  if (beyond_lds(t)) path = kGeneric;
+  else if (!force_rows && hm3_wanted() && star_supports(t, false)) path = kStar;  // shared sub-products (kernels_star.hip)
+  else if (!mm_tl_supports(t) || force_rows) path = kRows;
   const uint64_t ntiles = b.n_pad / kTileRows;
-  uint64_t nsplit = std::max<uint64_t>(1, (uint64_t)device_cus(b.device) * 4 / pblocks);
-  nsplit = std::min(nsplit, ntiles);
-  const uint64_t tps = (ntiles + nsplit - 1) / nsplit;
-  nsplit = (ntiles + tps - 1) / tps;
+  RowSplit rs{};
+  uint64_t pblocks = 1;  // blocks along the terms: more than one leave partial row sums in `part`
+  int ng = 1;
+  if (path == kStar) {
+    rs = star_grid(b, t, ntiles, pblocks);
+  } else if (path == kTl) {
+    // term-per-lane kernel: a block of 8 waves x NG groups x 64 terms, as few blocks along p
+    // as the register budget allows
+    ng = units_per_lane(t.p_pad, (uint64_t)kTlWaves * 64, tl_max_units((int)(t.W / 2)));
+    const uint64_t tpb = (uint64_t)kTlWaves * ng * 64;
+    pblocks = (t.p_pad + tpb - 1) / tpb;
+    rs = split_rows(ntiles, (uint64_t)device_cus(b.device) * 4 / pblocks);
+  }
   double *part = nullptr;
   if (pblocks > 1)
     OB_TRY(const_cast<obhip_basis &>(b).workspace(pblocks * b.n_pad * sizeof(double), (void **)&part));
-  const dim3 grid((unsigned)nsplit, (unsigned)pblocks);
   ProfScope ps(squared ? "sqmm" : "mm");
-  if (squared)
-    OB_TRY(dispatch_mm_tl<true>(b, t, d_a, d_out, part, grid, ng, ntiles, tps));
-  else
-    OB_TRY(dispatch_mm_tl<false>(b, t, d_a, d_out, part, grid, ng, ntiles, tps));
-  if (pblocks > 1) {
-    const dim3 g2((unsigned)((b.n + 255) / 256));
-    if (squared)
-      hipLaunchKernelGGL(k_mm_tl_sum<true>, g2, dim3(256), 0, cur_stream(), part, (int)pblocks,
-                         b.n_pad, b.scale.p, b.n, d_out);
-    else
-      hipLaunchKernelGGL(k_mm_tl_sum<false>, g2, dim3(256), 0, cur_stream(), part, (int)pblocks,
-                         b.n_pad, b.scale.p, b.n, d_out);
-    OB_HIP(hipGetLastError());
+  switch (path) {
+    case kGeneric: return launch_mm_generic(b, t, d_a, d_out, squared ? 1 : 0, 0);
+    case kRows: return run_mm(b, t, squared ? 1 : 0, d_a, d_out);
+    case kStar: OB_TRY(launch_star_mm(b, t, d_a, squared, d_out, part, (unsigned)rs.nsplit, ntiles, rs.tps)); break;
+    case kTl:
+      OB_TRY(run_mm_tl(b, t, squared, ng, d_a, d_out, part, dim3((unsigned)rs.nsplit, (unsigned)pblocks), ntiles,
+                       rs.tps));
+      break;
   }
+  if (pblocks > 1) OB_TRY(sum_mm_partials(b, part, pblocks, squared, d_out));
   return 0;
-}
-
-template <int W2, bool SQ, int NPAIR>
-int run_tmm_tl(const obhip_basis &b, obhip_terms &t, const double *d_a, double *part, dim3 grid,
-               uint64_t ntiles, uint64_t tps) {
-  const size_t lds = t.Mu * kTlPitch * sizeof(double);
-  static const bool nopf = getenv("OBHIP_TL_NOPREFETCH") != nullptr;
-  const bool pf = !nopf && t.Mu <= (uint64_t)kTlWaves * kTlPre;
-  if (pf) {
-    OB_TRY(set_lds(k_tmm_tl<W2, SQ, NPAIR, true>, lds));
-    hipLaunchKernelGGL((k_tmm_tl<W2, SQ, NPAIR, true>), grid, dim3(kTlThreads), lds, cur_stream(),
-                       b.bm.p, b.scale.p, t.ucol.p, (int)t.Mu, b.md.Mc, (const uint32_t *)t.cols.p,
-                       t.sperm.p, d_a, b.n, ntiles, tps, t.p_pad, part);
-  } else {
-    OB_TRY(set_lds(k_tmm_tl<W2, SQ, NPAIR, false>, lds));
-    hipLaunchKernelGGL((k_tmm_tl<W2, SQ, NPAIR, false>), grid, dim3(kTlThreads), lds, cur_stream(),
-                       b.bm.p, b.scale.p, t.ucol.p, (int)t.Mu, b.md.Mc, (const uint32_t *)t.cols.p,
-                       t.sperm.p, d_a, b.n, ntiles, tps, t.p_pad, part);
-  }
-  OB_HIP(hipGetLastError());
-  return 0;
-}
-
-// terms per block of k_tmm_tl: 8 waves x NPAIR x 2 groups of 64
-template <bool SQ>
-int dispatch_tmm_tl(const obhip_basis &b, obhip_terms &t, const double *d_a, double *part,
-                    unsigned nsplit, int npair, uint64_t ntiles, uint64_t tps) {
-  const uint64_t tpb = (uint64_t)kTlWaves * npair * kTlGP * 64;
-  const dim3 grid(nsplit, (unsigned)((t.p_pad + tpb - 1) / tpb));
-#define OB_TL(W2_, NP_) return run_tmm_tl<W2_, SQ, NP_>(b, t, d_a, part, grid, ntiles, tps)
-  switch (t.W / 2) {
-    case 1: if (npair == 4) OB_TL(1, 4); if (npair == 2) OB_TL(1, 2); OB_TL(1, 1);
-    case 2: if (npair == 4) OB_TL(2, 4); if (npair == 2) OB_TL(2, 2); OB_TL(2, 1);
-    case 3: if (npair == 2) OB_TL(3, 2); OB_TL(3, 1);
-    default: if (npair == 2) OB_TL(4, 2); OB_TL(4, 1);
-  }
-#undef OB_TL
 }
 
 int tmm_tl_supports(const obhip_terms &t) {
   const int w2 = (int)(t.W / 2);
-  return w2 >= 1 && w2 <= kMaxW2 && t.Mu * kTlPitch * sizeof(double) <= 156 * 1024;
-}
-
-template <int W2, int NPAIR, bool PF, bool WY>
-int run_materialize_tl2(const obhip_basis &b, obhip_terms &t, double *d_B, dim3 grid, uint64_t ntiles,
-                        uint64_t tps, const double *d_y, double *ypart) {
-  const size_t lds = t.Mu * kTlPitch * sizeof(double);
-  OB_TRY(set_lds(k_materialize_tl<W2, NPAIR, PF, WY>, lds));
-  hipLaunchKernelGGL((k_materialize_tl<W2, NPAIR, PF, WY>), grid, dim3(kTlThreads), lds, cur_stream(),
-                     b.bm.p, b.scale.p, t.ucol.p, (int)t.Mu, b.md.Mc, (const uint32_t *)t.cols.p, b.n,
-                     ntiles, tps, t.p_pad, d_B, d_y, ypart);
-  OB_HIP(hipGetLastError());
-  return 0;
-}
-template <int W2, int NPAIR>
-int run_materialize_tl(const obhip_basis &b, obhip_terms &t, double *d_B, dim3 grid, uint64_t ntiles,
-                       uint64_t tps, const double *d_y, double *ypart) {
-  const bool pf = t.Mu <= (uint64_t)kTlWaves * kTlPre;
-  if (pf && d_y) return run_materialize_tl2<W2, NPAIR, true, true>(b, t, d_B, grid, ntiles, tps, d_y, ypart);
-  if (pf) return run_materialize_tl2<W2, NPAIR, true, false>(b, t, d_B, grid, ntiles, tps, d_y, ypart);
-  if (d_y) return run_materialize_tl2<W2, NPAIR, false, true>(b, t, d_B, grid, ntiles, tps, d_y, ypart);
-  return run_materialize_tl2<W2, NPAIR, false, false>(b, t, d_B, grid, ntiles, tps, d_y, ypart);
+  return w2 >= 1 && w2 <= kMaxW2 && tmm_tl_lds_bytes(t) <= kLdsTile;
 }
 
 bool materialize_tl_supports(const obhip_terms &t) { return tmm_tl_supports(t) != 0; }
@@ -1256,40 +1185,29 @@ bool materialize_tl_supports(const obhip_terms &t) { return tmm_tl_supports(t) !
 // d_g (p) = B^T y, from the products the copy forms anyway.
 int launch_materialize_tl(const obhip_basis &b, obhip_terms &t, double *d_B, const double *d_y,
                           double *d_g) {
-  const int npmax = t.W / 2 <= 2 ? 4 : 2;
-  int npair = 1;
-  while (npair < npmax && (uint64_t)kTlWaves * npair * 128 < t.p_pad) npair *= 2;
+  const int w2 = (int)(t.W / 2);
+  const int npair = units_per_lane(t.p_pad, (uint64_t)kTlWaves * 128, tl_max_pairs(w2));
   const uint64_t tpb = (uint64_t)kTlWaves * npair * 128;
   const uint64_t pblocks = (t.p_pad + tpb - 1) / tpb;
   const uint64_t ntiles = b.n_pad / kTileRows;
-  uint64_t nsplit = std::max<uint64_t>(1, (uint64_t)device_cus(b.device) * 4 / pblocks);
-  nsplit = std::min(nsplit, ntiles);
-  const uint64_t tps = (ntiles + nsplit - 1) / nsplit;
-  nsplit = (ntiles + tps - 1) / tps;
-  const dim3 grid((unsigned)nsplit, (unsigned)pblocks);
+  const RowSplit rs = split_rows(ntiles, (uint64_t)device_cus(b.device) * 4 / pblocks);
+  const dim3 grid((unsigned)rs.nsplit, (unsigned)pblocks);
   double *ypart = nullptr;
-  if (d_y) OB_TRY(const_cast<obhip_basis &>(b).workspace(nsplit * t.p_pad * sizeof(double), (void **)&ypart));
-  int rc = 0;
-#define OB_MT(W2_, NP_) rc = run_materialize_tl<W2_, NP_>(b, t, d_B, grid, ntiles, tps, d_y, ypart); break
-  switch ((int)(t.W / 2) * 8 + npair) {
-    case 1 * 8 + 4: OB_MT(1, 4);
-    case 1 * 8 + 2: OB_MT(1, 2);
-    case 1 * 8 + 1: OB_MT(1, 1);
-    case 2 * 8 + 4: OB_MT(2, 4);
-    case 2 * 8 + 2: OB_MT(2, 2);
-    case 2 * 8 + 1: OB_MT(2, 1);
-    case 3 * 8 + 2: OB_MT(3, 2);
-    case 3 * 8 + 1: OB_MT(3, 1);
-    case 4 * 8 + 2: OB_MT(4, 2);
-    default: rc = run_materialize_tl<4, 1>(b, t, d_B, grid, ntiles, tps, d_y, ypart); break;
-  }
-#undef OB_MT
-  OB_TRY(rc);
-  if (d_y) {
-    hipLaunchKernelGGL(k_tmm_reduce, dim3((unsigned)((t.p + 63) / 64)), dim3(kRedThreads), 0, cur_stream(),
-                       ypart, (int)nsplit, t.p_pad, (int)t.p, d_g);
-    OB_HIP(hipGetLastError());
-  }
+  if (d_y) OB_TRY(const_cast<obhip_basis &>(b).workspace(rs.nsplit * t.p_pad * sizeof(double), (void **)&ypart));
+  const bool pf = t.Mu <= (uint64_t)kTlWaves * kTlPre;
+  OB_TRY(pick<1, 2, 3, 4>(w2, [&](auto W2) {
+    return pick<4, 2, 1>(npair, [&](auto NP) {
+      if constexpr (NP() > tl_max_pairs(W2())) return no_kernel();
+      else
+        return pick_bool(pf, [&](auto PF) {
+          return pick_bool(d_y != nullptr, [&](auto WY) {
+            return launch_prod(k_materialize_tl<W2(), NP(), PF(), WY()>, grid, dim3(kTlThreads), tmm_tl_lds_bytes(t),
+                               prod_tabs(b, t), b.n, ntiles, rs.tps, t.p_pad, d_B, d_y, ypart);
+          });
+        });
+    });
+  }));
+  if (d_y) OB_TRY(reduce_partials(ypart, rs.nsplit, t, d_g));
   return 0;
 }
 
@@ -1299,176 +1217,93 @@ int launch_tmm_dual(const obhip_basis &b, obhip_terms &t, const double *d_a, dou
                     double *d_out2) {
   OB_TRY(t.prepare(b.md.cap, b.md.dims_h));
   static const bool off = getenv("OBHIP_TMM_DUAL") && atoi(getenv("OBHIP_TMM_DUAL")) == 0;
-  const int w2 = (int)(t.W / 2);
-  if (!off && !beyond_lds(t) && hm3_wanted() && star_supports(t, false, true)) {  // shared sub-products
-    uint64_t nsplit, pblocks, ntiles, tps;
-    star_grid(b, t, nsplit, pblocks, ntiles, tps);
-    double *part = nullptr;
-    OB_TRY(const_cast<obhip_basis &>(b).workspace(2 * nsplit * t.p_pad * sizeof(double), (void **)&part));
-    double *part2 = part + nsplit * t.p_pad;
-    {
-      ProfScope ps("tmm_dual");
-      OB_TRY(launch_star_tmm(b, t, d_a, false, part, d_a2, part2, (unsigned)nsplit, ntiles, tps));
-    }
-    hipLaunchKernelGGL(k_tmm_reduce, dim3((unsigned)((t.p + 63) / 64)), dim3(kRedThreads), 0, cur_stream(), part,
-                       (int)nsplit, t.p_pad, (int)t.p, d_out);
-    hipLaunchKernelGGL(k_tmm_reduce, dim3((unsigned)((t.p + 63) / 64)), dim3(kRedThreads), 0, cur_stream(), part2,
-                       (int)nsplit, t.p_pad, (int)t.p, d_out2);
-    OB_HIP(hipGetLastError());
-    return 0;
-  }
-  if (off || beyond_lds(t) || !tmm_tl_supports(t) || w2 > 3) return kNotFused;
-  const bool pf = t.Mu <= (uint64_t)kTlWaves * kTlPre;  // (else the tile is loaded between the barriers)
-  const uint64_t ntiles = b.n_pad / kTileRows, p_pad = t.p_pad;
-  // six-slot terms (obfit's eight-dimensional sets): 4 terms per lane at 123 VGPRs, 8 would spill
-  const int npmax = w2 <= 2 ? 4 : 2;
+  const bool star = !off && !beyond_lds(t) && hm3_wanted() && star_supports(t, false, true);  // shared sub-products
+  if (!star && (off || beyond_lds(t) || !tmm_tl_supports(t) || t.W / 2 > 3)) return kNotFused;
+  const uint64_t ntiles = b.n_pad / kTileRows;
+  uint64_t pblocks = 0;
   int npair = 1;
-  while (npair < npmax && (uint64_t)kTlWaves * npair * kTlGP * 64 < p_pad) npair *= 2;
-  const uint64_t tpb = (uint64_t)kTlWaves * npair * kTlGP * 64;
-  const uint64_t pblocks = (p_pad + tpb - 1) / tpb;
-  uint64_t nsplit = std::max<uint64_t>(1, (uint64_t)device_cus(b.device) * 2 / pblocks);
-  nsplit = std::min(nsplit, std::max<uint64_t>(1, ntiles / 4));
-  const uint64_t tps = (ntiles + nsplit - 1) / nsplit;
-  nsplit = (ntiles + tps - 1) / tps;
+  const RowSplit rs = star ? star_grid(b, t, ntiles, pblocks) : tmm_tl_plan(b, t, ntiles, npair);
   double *part = nullptr;
-  OB_TRY(const_cast<obhip_basis &>(b).workspace(2 * nsplit * p_pad * sizeof(double), (void **)&part));
-  double *part2 = part + nsplit * p_pad;
-  const dim3 grid((unsigned)nsplit, (unsigned)pblocks);
-  const size_t lds = t.Mu * kTlPitch * sizeof(double);
+  OB_TRY(const_cast<obhip_basis &>(b).workspace(2 * rs.nsplit * t.p_pad * sizeof(double), (void **)&part));
+  double *part2 = part + rs.nsplit * t.p_pad;
   {
     ProfScope ps("tmm_dual");
-#define OB_TD2(W2_, NP_, PF_)                                                                               \
-  do {                                                                                                       \
-    OB_TRY(set_lds(k_tmm_tl<W2_, false, NP_, PF_, true>, lds));                                              \
-    hipLaunchKernelGGL((k_tmm_tl<W2_, false, NP_, PF_, true>), grid, dim3(kTlThreads), lds, cur_stream(),    \
-                       b.bm.p, b.scale.p, t.ucol.p, (int)t.Mu, b.md.Mc, (const uint32_t *)t.cols.p,          \
-                       t.sperm.p, d_a, b.n, ntiles, tps, p_pad, part, d_a2, part2);                          \
-  } while (0)
-#define OB_TD(W2_, NP_)                                                                                      \
-  do {                                                                                                       \
-    if (pf)                                                                                                  \
-      OB_TD2(W2_, NP_, true);                                                                                \
-    else                                                                                                     \
-      OB_TD2(W2_, NP_, false);                                                                               \
-  } while (0)
-    if (w2 == 1) {
-      if (npair == 4) OB_TD(1, 4); else if (npair == 2) OB_TD(1, 2); else OB_TD(1, 1);
-    } else if (w2 == 2) {
-      if (npair == 4) OB_TD(2, 4); else if (npair == 2) OB_TD(2, 2); else OB_TD(2, 1);
+    if (star) {
+      OB_TRY(launch_star_tmm(b, t, d_a, false, part, d_a2, part2, (unsigned)rs.nsplit, ntiles, rs.tps));
     } else {
-      if (npair == 2) OB_TD(3, 2); else OB_TD(3, 1);
+      const bool pf = t.Mu <= (uint64_t)kTlWaves * kTlPre;  // (else the tile is loaded between the barriers)
+      OB_TRY(run_tmm_tl(b, t, false, pf, npair, d_a, part, d_a2, part2, rs, ntiles));
     }
-#undef OB_TD2
-#undef OB_TD
-    OB_HIP(hipGetLastError());
   }
-  hipLaunchKernelGGL(k_tmm_reduce, dim3((unsigned)((t.p + 63) / 64)), dim3(kRedThreads), 0, cur_stream(), part,
-                     (int)nsplit, p_pad, (int)t.p, d_out);
-  hipLaunchKernelGGL(k_tmm_reduce, dim3((unsigned)((t.p + 63) / 64)), dim3(kRedThreads), 0, cur_stream(), part2,
-                     (int)nsplit, p_pad, (int)t.p, d_out2);
-  OB_HIP(hipGetLastError());
-  return 0;
+  OB_TRY(reduce_partials(part, rs.nsplit, t, d_out));
+  return reduce_partials(part2, rs.nsplit, t, d_out2);
 }
 
 int launch_tmm(const obhip_basis &b, obhip_terms &t, const double *d_a, double *d_out, bool squared) {
   OB_TRY(t.prepare(b.md.cap, b.md.dims_h));
-  if (beyond_lds(t)) {
-    ProfScope ps(squared ? "sqtmm" : "tmm");
-    return launch_tmm_generic(b, t, d_a, d_out, squared);
-  }
-  const uint64_t ntiles = b.n_pad / kTileRows;
-  const uint64_t p_pad = t.p_pad;  // multiple of 256 (obhip_terms::prepare)
-  double *part = nullptr;
   static const bool force_rows = getenv("OBHIP_TMM_LANE_ROW") != nullptr;
-  if (!force_rows && hm3_wanted() && star_supports(t, false)) {  // shared sub-products (kernels_star.hip)
-    uint64_t nsplit, pblocks, nt, tps;
-    star_grid(b, t, nsplit, pblocks, nt, tps);
-    OB_TRY(const_cast<obhip_basis &>(b).workspace(nsplit * p_pad * sizeof(double), (void **)&part));
-    {
-      ProfScope ps(squared ? "sqtmm" : "tmm");
-      OB_TRY(launch_star_tmm(b, t, d_a, squared, part, nullptr, nullptr, (unsigned)nsplit, nt, tps));
-    }
-    hipLaunchKernelGGL(k_tmm_reduce, dim3((unsigned)((t.p + 63) / 64)), dim3(kRedThreads), 0,
-                       cur_stream(), part, (int)nsplit, p_pad, (int)t.p, d_out);
-    OB_HIP(hipGetLastError());
-    return 0;
+  enum { kGeneric, kStar, kTl, kRows } path = kRows;
+  if (beyond_lds(t)) path = kGeneric;
+  else if (!force_rows && hm3_wanted() && star_supports(t, false)) path = kStar;  // shared sub-products (kernels_star.hip)
+  else if (tmm_tl_supports(t) && !force_rows) path = kTl;
+  const uint64_t ntiles = b.n_pad / kTileRows;
+  RowSplit rs{};
+  uint64_t pblocks = 0;
+  int npair = 1;
+  if (path == kStar) {
+    rs = star_grid(b, t, ntiles, pblocks);
+  } else if (path == kTl) {
+    rs = tmm_tl_plan(b, t, ntiles, npair);
+  } else if (path == kRows) {
+    pblocks = (t.p + 255) / 256;
+    // enough blocks to fill 256 CUs a few times over, each with >= 4 tiles
+    rs = split_rows(ntiles, (256 * 6 + pblocks - 1) / pblocks, 4);
   }
-  if (tmm_tl_supports(t) && !force_rows) {
-    // term-per-lane kernel: the fewest blocks along p that the register budget allows
-    const int npmax = t.W / 2 <= 2 ? 4 : 2;
-    int npair = 1;
-    while (npair < npmax && (uint64_t)kTlWaves * npair * kTlGP * 64 < p_pad) npair *= 2;
-    const uint64_t tpb = (uint64_t)kTlWaves * npair * kTlGP * 64;
-    const uint64_t pblocks = (p_pad + tpb - 1) / tpb;
-    // two resident blocks per CU, one round
-    uint64_t nsplit = std::max<uint64_t>(1, (uint64_t)device_cus(b.device) * 2 / pblocks);
-    nsplit = std::min(nsplit, std::max<uint64_t>(1, ntiles / 4));
-    const uint64_t tps = (ntiles + nsplit - 1) / nsplit;
-    nsplit = (ntiles + tps - 1) / tps;
-    OB_TRY(const_cast<obhip_basis &>(b).workspace(nsplit * p_pad * sizeof(double), (void **)&part));
-    {
-      ProfScope ps(squared ? "sqtmm" : "tmm");
-      if (squared)
-        OB_TRY(dispatch_tmm_tl<true>(b, t, d_a, part, (unsigned)nsplit, npair, ntiles, tps));
-      else
-        OB_TRY(dispatch_tmm_tl<false>(b, t, d_a, part, (unsigned)nsplit, npair, ntiles, tps));
-    }
-    hipLaunchKernelGGL(k_tmm_reduce, dim3((unsigned)((t.p + 63) / 64)), dim3(kRedThreads), 0,
-                       cur_stream(), part, (int)nsplit, p_pad, (int)t.p, d_out);
-    OB_HIP(hipGetLastError());
-    return 0;
-  }
-  const uint64_t pblocks = (t.p + 255) / 256;
-  // enough blocks to fill 256 CUs a few times over, each with >= 4 tiles
-  uint64_t nsplit = std::max<uint64_t>(1, (256 * 6 + pblocks - 1) / pblocks);
-  nsplit = std::min(nsplit, std::max<uint64_t>(1, ntiles / 4));
-  const uint64_t tps = (ntiles + nsplit - 1) / nsplit;
-  nsplit = (ntiles + tps - 1) / tps;
-  OB_TRY(const_cast<obhip_basis &>(b).workspace(nsplit * p_pad * sizeof(double), (void **)&part));
-  const dim3 grid((unsigned)nsplit, (unsigned)pblocks);
+  double *part = nullptr;  // [nsplit][p_pad]; p_pad is a multiple of 256 (obhip_terms::prepare)
+  if (path != kGeneric)
+    OB_TRY(const_cast<obhip_basis &>(b).workspace(rs.nsplit * t.p_pad * sizeof(double), (void **)&part));
   {
     ProfScope ps(squared ? "sqtmm" : "tmm");
-    if (squared)
-      OB_TRY(dispatch_tmm<true>(b, t, d_a, part, grid, ntiles, tps));
-    else
-      OB_TRY(dispatch_tmm<false>(b, t, d_a, part, grid, ntiles, tps));
+    switch (path) {
+      case kGeneric: return launch_tmm_generic(b, t, d_a, d_out, squared);
+      case kStar:
+        OB_TRY(launch_star_tmm(b, t, d_a, squared, part, nullptr, nullptr, (unsigned)rs.nsplit, ntiles, rs.tps));
+        break;
+      case kTl: {
+        static const bool nopf = getenv("OBHIP_TL_NOPREFETCH") != nullptr;
+        const bool pf = !nopf && t.Mu <= (uint64_t)kTlWaves * kTlPre;
+        OB_TRY(run_tmm_tl(b, t, squared, pf, npair, d_a, part, nullptr, nullptr, rs, ntiles));
+        break;
+      }
+      case kRows:
+        OB_TRY(run_tmm(b, t, squared, d_a, part, dim3((unsigned)rs.nsplit, (unsigned)pblocks), ntiles, rs.tps));
+        break;
+    }
   }
-  hipLaunchKernelGGL(k_tmm_reduce, dim3((unsigned)((t.p + 63) / 64)), dim3(kRedThreads), 0,
-                     cur_stream(), part, (int)nsplit, p_pad, (int)t.p, d_out);
-  OB_HIP(hipGetLastError());
-  return 0;
-}
-
-// d_out (p) = B^T (c_a B a + c_b y) in one pass over the basis (k_hm_tl); d_yhat (n, may be
-// null) = B a; d_ss (1, may be null) = sum (B a - y)^2.  Returns 1 when the terms do not fit the
-// fused kernel (more terms than one block holds, wide terms, too many used columns): the caller
-// then takes the two-kernel path.
-template <int W2, int NU, bool PF, bool RO>
-int run_hm_tl2(const obhip_basis &b, obhip_terms &t, const double *d_a, const double *d_y, double ca,
-               double cb, double *part, double *d_yhat, double *sspart, unsigned nsplit, uint64_t ntiles,
-               uint64_t tps, size_t lds) {
-  OB_TRY(set_lds(k_hm_tl<W2, NU, PF, RO>, lds));
-  hipLaunchKernelGGL((k_hm_tl<W2, NU, PF, RO>), dim3(nsplit), dim3(kTlThreads), lds, cur_stream(), b.bm.p,
-                     b.scale.p, t.ucol.p, (int)t.Mu, b.md.Mc, (const uint32_t *)t.cols.p, t.sperm.p, d_a,
-                     (int)t.p, d_y, ca, cb, b.n, ntiles, tps, t.p_pad, part, d_yhat, sspart);
-  OB_HIP(hipGetLastError());
-  return 0;
-}
-template <int W2, int NU>
-int run_hm_tl(const obhip_basis &b, obhip_terms &t, const double *d_a, const double *d_y, double ca,
-              double cb, double *part, double *d_yhat, double *sspart, unsigned nsplit, uint64_t ntiles,
-              uint64_t tps) {
-  const size_t lds = (t.Mu * kTlPitch + 2 * kTlWaves * kHmChunk) * sizeof(double);
-  static const bool nopf = getenv("OBHIP_HM_NOPREFETCH") != nullptr;
-  const bool pf = !nopf && t.Mu <= (uint64_t)kTlWaves * kTlPre;
-  const bool ro = d_y != nullptr;
-  if (pf && ro) return run_hm_tl2<W2, NU, true, true>(b, t, d_a, d_y, ca, cb, part, d_yhat, sspart, nsplit, ntiles, tps, lds);
-  if (pf) return run_hm_tl2<W2, NU, true, false>(b, t, d_a, d_y, ca, cb, part, d_yhat, sspart, nsplit, ntiles, tps, lds);
-  if (ro) return run_hm_tl2<W2, NU, false, true>(b, t, d_a, d_y, ca, cb, part, d_yhat, sspart, nsplit, ntiles, tps, lds);
-  return run_hm_tl2<W2, NU, false, false>(b, t, d_a, d_y, ca, cb, part, d_yhat, sspart, nsplit, ntiles, tps, lds);
+  return reduce_partials(part, rs.nsplit, t, d_out);
 }
 
 namespace {
+// k_hm_tl: one block of 8 waves x nu groups x 64 terms; kNotFused where no instantiation takes (W2, nu)
+int run_hm_tl(const obhip_basis &b, obhip_terms &t, int nu, const double *d_a, const double *d_y, double ca,
+              double cb, double *part, double *d_yhat, double *sspart, const RowSplit &rs, uint64_t ntiles) {
+  static const bool nopf = getenv("OBHIP_HM_NOPREFETCH") != nullptr;
+  const bool pf = !nopf && t.Mu <= (uint64_t)kTlWaves * kTlPre;
+  return pick_or<1, 2, 3, 4>((int)(t.W / 2), kNotFused, [&](auto W2) {
+    return pick_or<1, 2, 4, 8>(nu, kNotFused, [&](auto NU) {
+      if constexpr (NU() > tl_max_units(W2())) return (int)kNotFused;
+      else
+        return pick_bool(pf, [&](auto PF) {
+          return pick_bool(d_y != nullptr, [&](auto RO) {
+            return launch_prod(k_hm_tl<W2(), NU(), PF(), RO()>, dim3((unsigned)rs.nsplit), dim3(kTlThreads),
+                               hm_tl_lds_bytes(t), prod_tabs(b, t), t.sperm.p, d_a, (int)t.p, d_y, ca, cb, b.n,
+                               ntiles, rs.tps, t.p_pad, part, d_yhat, sspart);
+          });
+        });
+    });
+  });
+}
+
 bool hm2_wanted() {
   static const bool off = getenv("OBHIP_HESSMULT_FUSED") && atoi(getenv("OBHIP_HESSMULT_FUSED")) == 0;
   static const bool v1 = getenv("OBHIP_HM_V1") && atoi(getenv("OBHIP_HM_V1")) != 0;
@@ -1488,6 +1323,10 @@ bool hessmult_fused_skippable(const obhip_basis &b, obhip_terms &t) {
   return (hm3_wanted() && hm2_variant() == 0 && star_supports(t, true)) || hm2_supports(t, false, hm2_variant());
 }
 
+// d_out (p) = B^T (c_a B a + c_b y) in one pass over the basis (k_hm_tl); d_yhat (n, may be
+// null) = B a; d_ss (1, may be null) = sum (B a - y)^2.  Returns kNotFused when the terms do not fit the
+// fused kernel (more terms than one block holds, wide terms, too many used columns): the caller
+// then takes the two-kernel path.
 int launch_hessmult_fused(const obhip_basis &b, obhip_terms &t, const double *d_a, const double *d_y,
                           double ca, double cb, double *d_out, double *d_yhat, double *d_ss,
                           const double *d_stop0, const double *d_stop1, const HmThen *then) {
@@ -1500,60 +1339,31 @@ int launch_hessmult_fused(const obhip_basis &b, obhip_terms &t, const double *d_
   const bool use3 = hm2_wanted() && hm3_wanted() && variant == 0 && !beyond_lds(t) && star_supports(t, true);
   const bool use2 = use3 || (hm2_wanted() && !beyond_lds(t) && hm2_supports(t, d_y != nullptr, variant));
   if (d_stop0 && !use2) return fail(OBHIP_ERR_STATE, "hessmult: stop flags need the k_hm2 / k_hm3 path");
-  // (8 terms of 6 factors per lane spill and run at half the speed of the two-kernel form: measured)
-  const int numax = w2 <= 2 ? 8 : 4;
-  if (!use2 &&
-      (off || beyond_lds(t) || w2 < 1 || w2 > kMaxW2 || t.p_pad > (uint64_t)kTlWaves * numax * 64 ||
-       (t.Mu * kTlPitch + 2 * kTlWaves * kHmChunk) * sizeof(double) > 156 * 1024))
+  const int numax = tl_max_units(w2);
+  if (!use2 && (off || beyond_lds(t) || w2 < 1 || w2 > kMaxW2 || t.p_pad > (uint64_t)kTlWaves * numax * 64 ||
+                hm_tl_lds_bytes(t) > kLdsTile))
     return kNotFused;
-  int nu = 1;
-  while ((uint64_t)kTlWaves * nu * 64 < t.p_pad) nu *= 2;
+  const int nu = units_per_lane(t.p_pad, (uint64_t)kTlWaves * 64, numax);  // (k_hm_tl's; all terms in one block)
   const uint64_t ntiles = b.n_pad / kTileRows;
   // one resident block per CU (the products of a chunk live in registers), one round
-  uint64_t nsplit = std::max<uint64_t>(1, (uint64_t)device_cus(b.device));
-  nsplit = std::min(nsplit, std::max<uint64_t>(1, ntiles / 4));
-  const uint64_t tps = (ntiles + nsplit - 1) / nsplit;
-  nsplit = (ntiles + tps - 1) / tps;
+  const RowSplit rs = split_rows(ntiles, (uint64_t)device_cus(b.device), 4);
+  const uint64_t nsplit = rs.nsplit, tps = rs.tps;
   double *part = nullptr;
   OB_TRY(const_cast<obhip_basis &>(b).workspace((nsplit * t.p_pad + nsplit) * sizeof(double), (void **)&part));
   if ((d_yhat || d_ss) && !d_y) return fail(OBHIP_ERR_INVALID, "hessmult: yhat / residual sum need y");
   double *sspart = d_ss ? part + nsplit * t.p_pad : nullptr;
-  if (use3) {
+  {
     ProfScope ps("hessmult");
-    OB_TRY(launch_star_hess(b, t, d_a, d_y, ca, cb, part, d_yhat, sspart, (unsigned)nsplit, ntiles, tps,
-                            d_stop0, d_stop1));
-  } else if (use2) {
-    ProfScope ps("hessmult");
-    OB_TRY(launch_hm2(b, t, d_a, d_y, ca, cb, part, d_yhat, sspart, (unsigned)nsplit, ntiles, tps, variant,
-                      d_stop0, d_stop1));
-  } else {
-    ProfScope ps("hessmult");
-#define OB_HM(W2_, NU_) OB_TRY((run_hm_tl<W2_, NU_>(b, t, d_a, d_y, ca, cb, part, d_yhat, sspart, (unsigned)nsplit, ntiles, tps))); break
-    switch (w2 * 16 + nu) {
-      case 1 * 16 + 1: OB_HM(1, 1);
-      case 1 * 16 + 2: OB_HM(1, 2);
-      case 1 * 16 + 4: OB_HM(1, 4);
-      case 1 * 16 + 8: OB_HM(1, 8);
-      case 2 * 16 + 1: OB_HM(2, 1);
-      case 2 * 16 + 2: OB_HM(2, 2);
-      case 2 * 16 + 4: OB_HM(2, 4);
-      case 2 * 16 + 8: OB_HM(2, 8);
-      case 3 * 16 + 1: OB_HM(3, 1);
-      case 3 * 16 + 2: OB_HM(3, 2);
-      case 3 * 16 + 4: OB_HM(3, 4);
-      case 4 * 16 + 1: OB_HM(4, 1);
-      case 4 * 16 + 2: OB_HM(4, 2);
-      case 4 * 16 + 4: OB_HM(4, 4);
-      default: return kNotFused;
-    }
-#undef OB_HM
+    if (use3)
+      OB_TRY(launch_star_hess(b, t, d_a, d_y, ca, cb, part, d_yhat, sspart, (unsigned)nsplit, ntiles, tps,
+                              d_stop0, d_stop1));
+    else if (use2)
+      OB_TRY(launch_hm2(b, t, d_a, d_y, ca, cb, part, d_yhat, sspart, (unsigned)nsplit, ntiles, tps, variant,
+                        d_stop0, d_stop1));
+    else
+      OB_TRY(run_hm_tl(b, t, nu, d_a, d_y, ca, cb, part, d_yhat, sspart, rs, ntiles));
   }
-  if (then)
-    hipLaunchKernelGGL(k_tmm_reduce_q, dim3((unsigned)((t.p + 63) / 64)), dim3(kRedThreads), 0, cur_stream(),
-                       part, (int)nsplit, t.p_pad, (int)t.p, d_out, then->e2, then->prec, then->pv, then->q);
-  else
-    hipLaunchKernelGGL(k_tmm_reduce, dim3((unsigned)((t.p + 63) / 64)), dim3(kRedThreads), 0, cur_stream(),
-                       part, (int)nsplit, t.p_pad, (int)t.p, d_out);
+  OB_TRY(reduce_partials(part, nsplit, t, d_out, then));
   if (d_ss) hipLaunchKernelGGL(k_hm_ss, dim3(1), dim3(64), 0, cur_stream(), sspart, (int)nsplit, d_ss);
   OB_HIP(hipGetLastError());
   return 0;

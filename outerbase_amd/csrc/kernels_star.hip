@@ -724,7 +724,7 @@ bool star_supports(const obhip_terms &t, bool one_block, bool dual) {
   const int w2 = (int)(t.W / 2);
   return share_wanted() && t.sh.ok && w2 >= 1 && w2 <= 3 && t.sh.nsw_family >= 9 &&
          (!one_block || t.sh.nsw_family <= 16) && t.sh.nleft <= (uint64_t)(dual ? kStLeftMaxDual : kStLeftMax) &&
-         star_lds_bytes(t) <= (size_t)156 * 1024 &&
+         star_lds_bytes(t) <= kLdsTile &&
          (size_t)2 * t.Mu * kTlPitch >= (size_t)2 * kStWaves * kStNL * 16;
 }
 
@@ -739,12 +739,12 @@ int run_star(const StArgs &A, dim3 grid, size_t lds) {
 template <int OP, bool SQ, bool DUAL>
 int dispatch_star(const obhip_terms &t, const StArgs &A, dim3 grid) {
   const size_t lds = star_lds_bytes(t);
-  switch ((int)(t.W / 2)) {
-    case 1: return run_star<1, 12, OP, SQ, DUAL>(A, grid, lds);
-    // (DUAL: two accumulators per term and per left-over term -- fewer reads in flight instead of spills)
-    case 2: return run_star<2, DUAL ? 8 : 12, OP, SQ, DUAL>(A, grid, lds);
-    default: return run_star<3, DUAL ? 6 : 10, OP, SQ, DUAL>(A, grid, lds);  // (terms of 7 and 8 factors: not taken)
-  }
+  // reads in flight by W2 (DUAL: two accumulators per term and per left-over term -- fewer reads in
+  // flight instead of spills); terms of 7 and 8 factors are not taken
+  return pick<1, 2, 3>((int)(t.W / 2), [&](auto W2) {
+    constexpr int K = W2() == 1 ? 12 : W2() == 2 ? (DUAL ? 8 : 12) : (DUAL ? 6 : 10);
+    return run_star<W2(), K, OP, SQ, DUAL>(A, grid, lds);
+  });
 }
 StArgs star_args(const obhip_basis &b, const obhip_terms &t, uint64_t ntiles, uint64_t tps) {
   StArgs A{};
@@ -778,7 +778,7 @@ size_t star_predict_lds_bytes(const obhip_terms &t) {
 bool star_predict_supports(const obhip_terms &t) {
   const int w2 = (int)(t.W / 2);
   return share_wanted() && t.sh.ok && w2 >= 1 && w2 <= 3 && t.sh.nsw_family >= 9 && t.sh.nsw_family <= 16 &&
-         t.sh.nleft <= (uint64_t)kStLeftMax && star_predict_lds_bytes(t) <= (size_t)156 * 1024;
+         t.sh.nleft <= (uint64_t)kStLeftMax && star_predict_lds_bytes(t) <= kLdsTile;
 }
 int launch_star_predict(const obhip_model &m, obhip_terms &t, const double *d_theta, const double *d_x, uint64_t n,
                         double *d_mean, const double *d_coeffvar, double e2sigma, double *d_var) {
@@ -786,42 +786,28 @@ int launch_star_predict(const obhip_model &m, obhip_terms &t, const double *d_th
   int dev = 0;
   (void)hipGetDevice(&dev);
   const uint64_t ntiles = (n + kTileRows - 1) / kTileRows;
-  uint64_t nsplit = std::min<uint64_t>(ntiles, (uint64_t)device_cus(dev));
-  const uint64_t tps = (ntiles + nsplit - 1) / nsplit;
-  nsplit = (ntiles + tps - 1) / tps;
+  const RowSplit rs = split_rows(ntiles, (uint64_t)device_cus(dev));  // one workgroup per CU
   const bool wv = d_coeffvar != nullptr && d_var != nullptr;
   // (with the variance the kernel spills more for the two registers than the early request gains:
   // 1.83 -> 1.88 ms; without, 1.35 -> 1.24 ms on the same box)
   static const bool pfx_on = !(getenv("OBHIP_PREDICT_PFX") && atoi(getenv("OBHIP_PREDICT_PFX")) == 0);
   const bool pfx = pfx_on && !wv;
-#define OB_SP(W2_, K_, VAR_)                                                                                  \
-  do {                                                                                                        \
-    if (pfx)                                                                                                  \
-      OB_SP2(W2_, K_, VAR_, true);                                                                            \
-    else                                                                                                      \
-      OB_SP2(W2_, K_, VAR_, false);                                                                           \
-  } while (0)
-#define OB_SP2(W2_, K_, VAR_, PFX_)                                                                           \
-  do {                                                                                                        \
-    OB_TRY(ensure_dyn_lds((const void *)k_star_predict<W2_, K_, VAR_, PFX_>, lds));                           \
-    launch_pred<false>(k_star_predict<W2_, K_, VAR_, PFX_>, dim3((unsigned)nsplit), dim3(kStWaves * 64), lds, \
-                       pred_tabs(m, t),                                                                       \
-                       (const uint32_t *)t.sh_cols.p, t.sh_term.p, t.sh_shape.p, (int)t.sh.nsw_family,        \
-                       t.sh_left_term.p, (const uint32_t *)t.sh_left_cols.p, (int)t.sh.nleft, (int)t.p,       \
-                       d_theta, d_coeffvar, e2sigma, d_x, n, ntiles, tps, d_mean, d_var);                     \
-  } while (0)
-  switch ((int)(t.W / 2) * 2 + (wv ? 1 : 0)) {
-    case 2: OB_SP(1, 12, false); break;
-    case 3: OB_SP(1, 12, true); break;
-    case 4: OB_SP(2, 12, false); break;
-    case 5: OB_SP(2, 10, true); break;  // (ring depth 8 and / or early inputs here: 1.79-1.86 ms either way)
-    case 6: OB_SP(3, 10, false); break;
-    default: OB_SP(3, 8, true); break;
-  }
-#undef OB_SP
-#undef OB_SP2
-  OB_HIP(hipGetLastError());
-  return 0;
+  return pick<1, 2, 3>((int)(t.W / 2), [&](auto W2) {
+    return pick_bool(wv, [&](auto VAR) {
+      // reads in flight (W2 = 2 with the variance: ring depth 8 and / or early inputs, 1.79-1.86 ms either way)
+      constexpr int K = W2() == 1 ? 12 : W2() == 2 ? (VAR() ? 10 : 12) : (VAR() ? 8 : 10);
+      return pick_bool(pfx, [&](auto PFX) {
+        constexpr auto kernel = k_star_predict<W2(), K, VAR(), PFX()>;
+        OB_TRY(ensure_dyn_lds((const void *)kernel, lds));
+        launch_pred<false>(kernel, dim3((unsigned)rs.nsplit), dim3(kStWaves * 64), lds, pred_tabs(m, t),
+                           (const uint32_t *)t.sh_cols.p, t.sh_term.p, t.sh_shape.p, (int)t.sh.nsw_family,
+                           t.sh_left_term.p, (const uint32_t *)t.sh_left_cols.p, (int)t.sh.nleft, (int)t.p, d_theta,
+                           d_coeffvar, e2sigma, d_x, n, ntiles, rs.tps, d_mean, d_var);
+        OB_HIP(hipGetLastError());
+        return 0;
+      });
+    });
+  });
 }
 
 // B^T (c_a B a + c_b y): d_y null = the Hessian product

@@ -14,9 +14,11 @@
 #include <memory>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/obhip.h"
+#include "launch_plan.h"
 
 namespace obhip {
 
@@ -28,10 +30,10 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line);
     hipError_t _e = (expr);                                         \
     if (_e != hipSuccess) return obhip::hip_fail(_e, #expr, __FILE__, __LINE__); \
   } while (0)
-#define OB_TRY(expr)        \
-  do {                      \
-    int _rc = (expr);       \
-    if (_rc != 0) return _rc; \
+#define OB_TRY(...)              \
+  do {                           \
+    int _rc = (__VA_ARGS__);     \
+    if (_rc != 0) return _rc;    \
   } while (0)
 
 int require_device();
@@ -438,6 +440,10 @@ namespace obhip {
 constexpr int kTileRows = 64;
 // LDS of a workgroup on gfx950: what the fused kernels size their tiles against
 constexpr size_t kLdsBudget = 160 * 1024;
+// the largest tile the term-per-lane and star kernels were measured to run with: what their
+// *_supports functions admit.  Not the budget above: the 4 KB between them are left to the
+// compiler's own LDS and to the allocation granule
+constexpr size_t kLdsTile = 156 * 1024;
 // doubles of LDS k_build_basis has for one dimension's interval tables; ModelDev::build makes
 // tables only for dimensions whose tables fit (larger ones would be per-lane global gathers, no
 // faster than the knot loop, and cost the host O(knots^2 x levels) per hyper-parameter update)
@@ -596,6 +602,52 @@ bool predict_multi_supports(const obhip_terms &t);
 int launch_theta_term_major(const double *d_Theta, uint64_t p, int qc, uint64_t qw, double *d_T);
 int launch_predict_multi(const obhip_model &m, obhip_terms &t, const double *d_Theta, uint64_t q,
                          const double *d_x, uint64_t n, double *d_mean);
+// ---- runtime value -> template argument -----------------------------------------------------------
+// pick_or<1, 2, 4, 8>(ng, miss, [&](auto NG) { ... NG() ... }): the lambda is called with the
+// std::integral_constant of the listed value that v equals and its result returned; `miss` when v
+// equals none.  Inside the lambda `if constexpr` on NG() keeps a combination that must not exist
+// from being instantiated (no_kernel() is what such an arm returns).
+template <int... Vs, typename F>
+int pick_or(int v, int miss, F &&f) {
+  int rc = miss;
+  (void)((v == Vs ? (rc = f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+  return rc;
+}
+// the same, the LAST listed value standing in for every v that equals none (a switch's `default:`)
+template <int... Vs, typename F>
+int pick(int v, F &&f) {
+  constexpr int vs[] = {Vs...};
+  return pick_or<Vs...>(((v == Vs) || ...) ? v : vs[sizeof...(Vs) - 1], 0, f);
+}
+template <typename F>
+int pick_bool(bool v, F &&f) {
+  return v ? f(std::true_type{}) : f(std::false_type{});
+}
+inline int no_kernel() { return fail(OBHIP_ERR_STATE, "dispatch: no kernel for this combination"); }
+
+// ---- what the product kernels share on the host ---------------------------------------------------
+// (kernels_prod, _hm, _grad, _grad_d3: the kernels that stage a tile of the used columns of b in LDS)
+// Their leading parameters, in their order.
+struct ProdTabs {
+  const double *bm, *scale;
+  const uint32_t *ucol;
+  int Mu;
+  uint64_t Mc;
+  const uint32_t *cols;
+};
+inline ProdTabs prod_tabs(const obhip_basis &b, const obhip_terms &t) {
+  return {b.bm.p, b.scale.p, t.ucol.p, (int)t.Mu, b.md.Mc, (const uint32_t *)t.cols.p};
+}
+// kernel<<<grid, block, lds, current stream>>>(the tables as separate arguments, rest...), its dynamic
+// LDS granted first (ensure_dyn_lds: nothing to do up to 64 KB) and the launch checked
+template <typename Kernel, typename... Rest>
+int launch_prod(Kernel kernel, dim3 grid, dim3 block, size_t lds, const ProdTabs &T, Rest... rest) {
+  OB_TRY(ensure_dyn_lds((const void *)kernel, lds));
+  hipLaunchKernelGGL(kernel, grid, block, lds, cur_stream(), T.bm, T.scale, T.ucol, T.Mu, T.Mc, T.cols, rest...);
+  OB_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---- what the fused predictors share on the host -------------------------------------------------
 // (kernels_predict, _star, _multi, _predict_dx, _materialize_dx, _predict_jac)
 int ensure_dx_tables(const obhip_model &m, obhip_terms &t);  // predict_dx.cpp; after t.prepare(t.pred_md.cap, ...)
