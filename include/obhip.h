@@ -542,6 +542,100 @@ int obhip_predict_multi(const obhip_model *m, const obhip_terms *t, const double
                         uint64_t q, const double *x, uint64_t n, uint64_t ldx, double *mean,
                         const double *coeffvar, double sigma, double *var);
 
+/* ---- weighted, binomial and Poisson responses: iteratively reweighted least squares ----------
+ * (no reference counterpart: every fit of the reference, and every entry above, has a Gaussian
+ * response with one noise level for all rows.)  For rows i with prior weights a_i > 0 (NULL: 1)
+ * and offsets o_i (NULL: 0), eta = o + B theta and P = diag(prior precisions of the terms at
+ * rho), the entries below maximise
+ *     F(theta) = sum_i a_i l(y_i, eta_i) - theta^T P theta / 2
+ *   family     link      l(y, eta)                       mu                  IRLS weight w      y
+ *   GAUSSIAN   identity  -e^{-2 sigma} (y - eta)^2 / 2   eta                 a e^{-2 sigma}     finite
+ *   BINOMIAL   logit     y eta - softplus(eta)           1 / (1 + e^{-eta})  a mu (1 - mu)      in [0, 1]
+ *   POISSON    log       y eta - e^eta                   e^eta               a mu               >= 0
+ * (binomial y: proportions, a = trials; sigma is read by the Gaussian family only; y standardised
+ * by the caller as for obhip_fit_newton_multi_dev).  With e = exp(-|eta|) the binomial forms are
+ * free of overflow: mu = eta >= 0 ? 1 / (1 + e) : e / (1 + e), mu (1 - mu) = e / (1 + e)^2,
+ * softplus(eta) = max(eta, 0) + log1p(e).
+ * Newton's method from theta = 0 (eta = o), or from the caller's theta with info->warm_start:
+ *   1. row pass: mu, w, the weighted row factor scale_w = scale sqrt(w) of the basis, the working
+ *      column u = a (y - mu) (Gaussian: e^{-2 sigma}) / sqrt(w), so that B_w^T u = B^T (a (y - mu)),
+ *      and sum a l;
+ *   2. H = B_w^T B_w + P, g = B_w^T u - P theta by the Gram pipeline of the fits above on the
+ *      caller's basis with its row factors exchanged for scale_w for the length of that Gram (no
+ *      copy of the basis; restored on every exit path, after which an unweighted use stages the
+ *      design matrix again), Cholesky, delta = inv(H) g, dec = g^T delta;
+ *   3. one B delta on the unweighted basis; a trial step alpha is then one row pass on
+ *      eta + alpha B delta and a p-sized dot product;
+ *   4. dec <= tol (1 + |F|): the full step is taken and the fit has converged (the last step is
+ *      the one that brings theta to rounding level);
+ *   5. otherwise alpha is halved from 1 until F(theta + alpha delta) is finite and not below
+ *      F(theta) - slack, slack = (n + p + 16) 2^-53 (A(theta) + A(theta + alpha delta)), A = the
+ *      sum of the magnitudes F is summed of: the rounding bound of the two sums, so that no step is
+ *      refused on rounding noise alone.  30 halvings without a step: OBHIP_ERR_NUMERIC.
+ * One response, all rows on one device: row sharding (obhip_comm), several responses and the
+ * streaming accumulator are not offered, the weights change with every iteration and differ per
+ * response. */
+#define OBHIP_GLM_GAUSSIAN 0
+#define OBHIP_GLM_BINOMIAL 1
+#define OBHIP_GLM_POISSON 2
+typedef struct obhip_glm_info {
+  int warm_start;      /* in: non-zero = start from the theta the caller passed */
+  int converged;       /* out: step 4 was reached within maxit iterations */
+  uint64_t iterations; /* out: Newton steps taken, the last one included */
+  uint64_t halvings;   /* out: halvings of alpha over all line searches */
+  double dec;          /* out: g^T delta of the last step */
+  double F;            /* out: the penalised log-likelihood at the returned theta */
+  double deviance;     /* out: 2 sum a (l(y, saturated) - l(y, eta)) at the returned theta */
+} obhip_glm_info;
+/* bytes of device workspace of obhip_fit_glm_dev for p terms and n rows (host arithmetic) */
+int obhip_glm_workspace_bytes(uint64_t p, uint64_t n, uint64_t *bytes);
+/* The row pass on its own.  All vectors have n entries except d_scale, d_scale_w and d_u, which
+ * have n rounded up to a multiple of 64 like the row factors of a basis.
+ *   eta_i = (d_eta ? d_eta[i] : d_o ? d_o[i] : 0) + (d_deta ? alpha d_deta[i] : 0)
+ * (d_eta holds o + B theta of an earlier pass, so d_o is read only where a pass starts from it);
+ * d_a NULL: weights 1.  Written: d_eta_out (may be d_eta), d_mu (may be NULL), d_scale_w =
+ * d_scale sqrt(w), d_u; rows >= n of d_scale_w and d_u are written as zeros whatever the inputs
+ * hold there, and a row with w = 0 (binomial beyond |eta| = 745) or a non-finite w has u = 0.
+ * With d_eta_out, d_mu, d_scale_w and d_u all NULL the pass is a trial: nothing but the sums is
+ * written.  d_sums (3): sum a l over the rows whose l is finite, the sum of the magnitudes
+ * a (|y eta| + |b(eta)|) (l = y eta - b(eta); Gaussian: a |l|), and the number of rows whose l is
+ * not finite -- read that in place of a NaN-poisoned sum.  Fixed two-stage summation order, no
+ * atomics: the same bits on every call. */
+int obhip_glm_rows_dev(int family, uint64_t n, const double *d_eta, const double *d_deta,
+                       double alpha, const double *d_y, const double *d_a, const double *d_o,
+                       double sigma, const double *d_scale, double *d_eta_out, double *d_mu,
+                       double *d_scale_w, double *d_u, double *d_sums);
+/* The fit.  d_y, d_a, d_o: n rows of the basis (d_a, d_o may be NULL); d_H: p x p, on return its
+ * lower triangle holds the Cholesky factor of the last Hessian and d_diagH (p, may be NULL) that
+ * Hessian's diagonal; d_theta (p): out, in/out with info->warm_start; d_eta (n, may be NULL):
+ * o + B theta at the returned theta; d_ws: obhip_glm_workspace_bytes(p, n).  maxit >= 1
+ * iterations without convergence are no error (info->converged = 0).  OBHIP_ERR_NUMERIC: a
+ * Hessian that is not positive definite, a start at which F is not finite, a line search that
+ * finds no step; OBHIP_ERR_INVALID for argument errors, before the first launch. */
+int obhip_fit_glm_dev(const obhip_basis *b, const obhip_terms *t, const obhip_model *m, int family,
+                      const double *d_y, const double *d_a, const double *d_o, double sigma,
+                      double rho, double tol, uint64_t maxit, double *d_H, double *d_theta,
+                      double *d_diagH, double *d_eta, obhip_glm_info *info, void *d_ws,
+                      uint64_t ws_bytes);
+/* obhip_predict_dev's path without a noise term, then the response scale: d_eta (n) = o +
+ * B(x) theta, d_vareta = B^2 coeffvar (needs d_coeffvar), d_mu = the inverse link of eta, d_varmu
+ * = (d mu / d eta)^2 vareta (delta method).  Any output may be NULL; n = 0 is a no-op. */
+int obhip_predict_glm_dev(const obhip_model *m, const obhip_terms *t, int family,
+                          const double *d_theta, const double *d_x, uint64_t n, const double *d_o,
+                          const double *d_coeffvar, double *d_eta, double *d_vareta, double *d_mu,
+                          double *d_varmu);
+/* host-buffer forms like obhip_fit_newton_multi / obhip_predict_multi.  They check, before any
+ * device call, that y is in its family's domain and the weights are finite and > 0
+ * (OBHIP_ERR_INVALID).  theta (p): out, in/out with info->warm_start; diagH, eta may be NULL. */
+int obhip_fit_glm(const obhip_basis *b, const obhip_terms *t, const obhip_model *m, int family,
+                  const double *y, const double *a, const double *o, double sigma, double rho,
+                  double tol, uint64_t maxit, double *theta, double *diagH, double *eta,
+                  obhip_glm_info *info);
+int obhip_predict_glm(const obhip_model *m, const obhip_terms *t, int family, const double *theta,
+                      const double *x, uint64_t n, uint64_t ldx, const double *o,
+                      const double *coeffvar, double *eta, double *vareta, double *mu,
+                      double *varmu);
+
 /* ---- streaming Newton fit: rows come and go, one pass over each (no reference counterpart) ----
  * obfit (R/fitting.R:40-120) and every fit entry above take all rows at once and form the whole
  * Gram again per call.  An obhip_normal_acc keeps, in HBM, the sufficient statistics of the Newton

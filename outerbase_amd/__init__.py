@@ -14,6 +14,7 @@ from .obmod import (covf, covf_mat25, covf_mat25ang, covf_mat25pow, gethyp, getp
                     term_dim_views)
 from .fitting import BFGS_lpdf, BFGS_std, obfit, obpred, obpred_grad
 from .multi import MultiFit, fit_newton_multi
+from .glm import GlmFit, fit_glm
 from .torch_emulator import TorchEmulator
 from .driver import HotPath, MultiHotPath
 from .stream import (CVResult, NewtonAccumulator, cv_folds, cv_newton_multi, design_dx,
@@ -29,4 +30,5 @@ __all__ = [
     "predict_grad", "obpred_grad", "term_dim_views",
     "design_dx", "fit_newton_grad",
     "predict_jac", "predict_vjp", "TorchEmulator",
+    "GlmFit", "fit_glm",
 ]

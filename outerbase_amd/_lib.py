@@ -35,6 +35,7 @@ _BASE = {
 }
 _HANDLES = ("obhip_model", "obhip_basis", "obhip_terms", "obhip_comm", "obhip_lpdf",
             "obhip_predictor", "obhip_normal_acc")
+_STRUCTS = ("obhip_glm_info",)  # small host structs, passed by address
 
 
 def _ctype(decl):
@@ -45,6 +46,8 @@ def _ctype(decl):
         return C.c_void_p  # pass ctypes.cast(HOST_ALLREDUCE_FN(f), c_void_p) or None
     if base in _HANDLES:
         return C.c_void_p if stars == 1 else C.POINTER(C.c_void_p)
+    if base in _STRUCTS:
+        return C.c_void_p  # pass ctypes.byref(GlmInfo()) (glm.py)
     if base == "char" and stars == 1:
         return C.c_char_p
     if base == "void":

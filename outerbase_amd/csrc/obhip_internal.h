@@ -602,6 +602,25 @@ bool predict_multi_supports(const obhip_terms &t);
 int launch_theta_term_major(const double *d_Theta, uint64_t p, int qc, uint64_t qw, double *d_T);
 int launch_predict_multi(const obhip_model &m, obhip_terms &t, const double *d_Theta, uint64_t q,
                          const double *d_x, uint64_t n, double *d_mean);
+// kernels_glm.hip: the row pass between two Newton steps of the GLM fit (glm.cpp) and the response scale
+// of its predictor.  eta_i = (eta ? eta[i] : o ? o[i] : 0) + (deta ? alpha deta[i] : 0); scale, scale_w and
+// u have n rounded up to a multiple of 64 entries; scale_w == nullptr: a trial pass, only the sums
+constexpr int kGlmSums = 3;  // sum a l over the finite rows, the sum of its magnitudes, the rows left out
+struct GlmRows {
+  int family = 0;
+  uint64_t n = 0;
+  const double *eta = nullptr, *deta = nullptr;
+  double alpha = 0.0;
+  const double *y = nullptr, *a = nullptr, *o = nullptr;
+  double e2 = 1.0;  // e^{-2 sigma}, Gaussian family only
+  const double *scale = nullptr;
+  double *eta_out = nullptr, *mu = nullptr, *scale_w = nullptr, *u = nullptr;
+};
+// d_sums: kGlmSums doubles; d_part: kSumBlocks (vec_ops.h) * kGlmSums doubles of scratch
+int launch_glm_rows(const GlmRows &r, double *d_sums, double *d_part);
+// d_eta (n, in/out) += o; d_mu = inverse link; d_varmu = (d mu / d eta)^2 d_vareta; o, mu, varmu may be null
+int launch_glm_response(int family, uint64_t n, const double *d_o, double *d_eta, const double *d_vareta,
+                        double *d_mu, double *d_varmu);
 // ---- runtime value -> template argument -----------------------------------------------------------
 // pick_or<1, 2, 4, 8>(ng, miss, [&](auto NG) { ... NG() ... }): the lambda is called with the
 // std::integral_constant of the listed value that v equals and its result returned; `miss` when v
