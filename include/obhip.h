@@ -636,6 +636,56 @@ int obhip_predict_glm(const obhip_model *m, const obhip_terms *t, int family, co
                       const double *coeffvar, double *eta, double *vareta, double *mu,
                       double *varmu);
 
+/* ---- variance-based sensitivity of the fitted mean (no reference counterpart) ------------------
+ * The fitted mean is f(x) = sum_k theta_k prod_l psi_{l, t_kl}(x_l), psi_l = getbase(l) (the raw
+ * cov . rotmat).  Under independent inputs with a discrete measure per dimension -- nodes z_il with
+ * weights w_il >= 0 normalised by their sum: the empirical marginals of a sample (no weights) or a
+ * quadrature rule of a density -- every variance-based index is a closed-form sum over the moment
+ * tables of the 1-D bases; no sampling is involved.  With L_l = 1 + obhip_terms_maxlevels[l]:
+ *   mean table  m_l[t]    = sum_i w^_i psi_{l,t}(z_il)                       packed, sum L_l doubles,
+ *                                                                            dimension l at sum_{i<l} L_i
+ *   cov table   C_l[t,t'] = sum_i w^_i (psi_t - m_t)(psi_t' - m_t')          packed, sum L_l^2 doubles,
+ *                                                                            row-major per dimension
+ * (two passes: means, then centred products) and A_l = C_l + m_l m_l^T.  Per response column theta:
+ *   mu   = sum_k theta_k prod_l m_l[t_kl]
+ *   V1_l = g_l^T C_l g_l,  g_l[t] = sum_{k: t_kl = t} theta_k prod_{i != l} m_i[t_ki]   (Var E[f | x_l])
+ *   VT_l = sum_{k,k'} theta_k theta_k' C_l[t,t'] prod_{i != l} A_i[t_ki, t_k'i]        (V - Var E[f | x_~l])
+ *   V    = sum_{k,k'} theta_k theta_k' sum_l (prod_{i<l} A_i) C_l (prod_{i>l} m_i m_i)  (= prod A - prod m m)
+ * and E[f | x_l = z] = sum_t g_l[t] psi_{l,t}(z).  All sums are taken in a fixed order without
+ * atomics: the same bits on every call.  Levels beyond 255 in a dimension and tables beyond the LDS
+ * of a workgroup are refused (OBHIP_ERR_INVALID).  Argument errors return OBHIP_ERR_INVALID before
+ * any device call. */
+/* *n_mean = sum L_l, *n_cov = sum L_l^2 (either may be NULL) */
+int obhip_sobol_layout(const obhip_terms *t, uint64_t *n_mean, uint64_t *n_cov);
+/* The tables of the measure.  d_nodes: n x d column-major with ldx >= n; d_weights: n x d
+ * column-major with ldw >= n, or NULL (all 1); rows n .. ld are never read.  n = 0 is
+ * OBHIP_ERR_INVALID (there is no measure).  A weight that is negative or not finite, or a column
+ * of weights whose sum is not > 0: OBHIP_ERR_NUMERIC (found on the device; the call waits for it). */
+int obhip_dim_moments_dev(const obhip_model *m, const obhip_terms *t, const double *d_nodes,
+                          uint64_t n, uint64_t ldx, const double *d_weights, uint64_t ldw,
+                          double *d_mean, double *d_cov);
+int obhip_sobol_workspace_bytes(uint64_t p, uint64_t d, uint64_t q, uint64_t *bytes);
+/* d_Theta: p x q column-major, ld = p.  d_mean_tab / d_cov_tab: tables in the layout above -- those
+ * of obhip_dim_moments_dev or any others; every C_l must be symmetric (only the pairs k <= k' of
+ * term tiles are visited).  d_out: q x (2 + 2 d) row-major, per response [mu, V, V1_0 .. V1_{d-1},
+ * VT_0 .. VT_{d-1}].  d_g (may be NULL; d_out has the same bits either way): the g_l packed like a
+ * mean table, response j at j * sum L_l.  d_ws: obhip_sobol_workspace_bytes(p, d, q). */
+int obhip_sobol_dev(const obhip_terms *t, const double *d_Theta, uint64_t q,
+                    const double *d_mean_tab, const double *d_cov_tab, double *d_out, double *d_g,
+                    void *d_ws, uint64_t ws_bytes);
+/* d_out (G x q column-major, ld = G) = psi_dim at the G points d_grid times the g_dim of every
+ * response: E[f | x_dim = z], from which the caller subtracts mu.  d_g as obhip_sobol_dev writes it.
+ * G = 0 is a no-op. */
+int obhip_main_effect_dev(const obhip_model *m, const obhip_terms *t, uint64_t dim,
+                          const double *d_g, uint64_t q, const double *d_grid, uint64_t G,
+                          double *d_out);
+/* host-buffer forms: nodes n x d with ldx, weights n x d with ldw or NULL, mean / cov the packed
+ * tables; Theta p x q (ld = p), out q x (2 + 2 d), g (may be NULL) q x sum L_l */
+int obhip_dim_moments(const obhip_model *m, const obhip_terms *t, const double *nodes, uint64_t n,
+                      uint64_t ldx, const double *weights, uint64_t ldw, double *mean, double *cov);
+int obhip_sobol(const obhip_terms *t, const double *Theta, uint64_t q, const double *mean_tab,
+                const double *cov_tab, double *out, double *g);
+
 /* ---- streaming Newton fit: rows come and go, one pass over each (no reference counterpart) ----
  * obfit (R/fitting.R:40-120) and every fit entry above take all rows at once and form the whole
  * Gram again per call.  An obhip_normal_acc keeps, in HBM, the sufficient statistics of the Newton

@@ -15,6 +15,7 @@ from .obmod import (covf, covf_mat25, covf_mat25ang, covf_mat25pow, gethyp, getp
 from .fitting import BFGS_lpdf, BFGS_std, obfit, obpred, obpred_grad
 from .multi import MultiFit, fit_newton_multi
 from .glm import GlmFit, fit_glm
+from .sensitivity import InputMoments, SobolResult, input_moments, main_effects, sobol, uniform_nodes
 from .torch_emulator import TorchEmulator
 from .driver import HotPath, MultiHotPath
 from .stream import (CVResult, NewtonAccumulator, cv_folds, cv_newton_multi, design_dx,
@@ -31,4 +32,5 @@ __all__ = [
     "design_dx", "fit_newton_grad",
     "predict_jac", "predict_vjp", "TorchEmulator",
     "GlmFit", "fit_glm",
+    "InputMoments", "SobolResult", "input_moments", "uniform_nodes", "sobol", "main_effects",
 ]

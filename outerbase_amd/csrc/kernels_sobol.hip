@@ -1,0 +1,527 @@
+// Variance-based sensitivity of the fitted mean (sobol.cpp; include/obhip.h, "variance-based
+// sensitivity").  No reference counterpart.
+//
+// k_dim_moments<PASS>: lane = node row, block = (row slice, dimension, tile of 8 levels or pair of
+//   such tiles).  A row's raw psi_{l,t} come from the library's own builder (build_dim_any: interval
+//   tables staged in LDS where the model has them, the knot loop otherwise), level 0 returned and
+//   the normalised levels multiplied by it again, into a [level][thread] LDS tile -- never into HBM.
+//   PASS 1 sums w psi_t, w and the bad weights; PASS 2 sums w (psi_t - m_t)(psi_t' - m_t') with the
+//   means of pass 1.  Rows >= n are never read.  Sums: per thread over its rows, butterfly per wave,
+//   the waves in order, then k_moments_fin* over the blocks (lane-strided, butterfly): a fixed order.
+// k_sobol_excl / k_sobol_first: prod_{i != l} m_i[t_ki] by suffix and prefix products (no
+//   division), then one block per (dimension, response): g_l by one wave per level, V1_l = g^T C g.
+// k_sobol_pairs<DC>: the p^2 part over the upper triangle of pairs of 128-term tiles.  Lane = term
+//   k, its row offsets into the tables in registers; the partner k' is wave-uniform (levels and
+//   coefficients by scalar loads); A_l = C_l + m_l m_l^T, C_l and m_l m_l^T of every dimension in LDS.
+//   Per pair: suffix products of A, then one forward sweep gives the DC factors
+//   C_l prod_{i != l} A_i and, by D_l = C_l prod_{i<l} A_i + (m m)_l D_{l-1}, the telescoped
+//   prod A - prod m m; they are formed once per pair and used for the kSobolRC responses of the chunk.
+//   k_sobol_reduce sums the per-block partials in a fixed order.
+#include "obhip_internal.h"
+#include "device_common.h"
+
+namespace obhip {
+
+namespace {
+
+constexpr int kMomLT = 8;            // levels per accumulator tile
+constexpr int kMomP1 = kMomLT + 2;   // sums of pass 1: 8 levels, the weights, the bad weights
+constexpr int kMomP2 = kMomLT * kMomLT;
+constexpr int kMomBlocks = 512;      // row slices at most
+
+struct StoreCol {
+  double *col;  // tile + thread
+  int ccol0, nt;
+  __device__ __forceinline__ void operator()(int ccol, double v) const { col[(size_t)(ccol - ccol0 + 1) * nt] = v; }
+};
+
+// raw psi_{l,t}(xv), t < D.ncol, into col[t * nt]
+__device__ __forceinline__ void eval_raw(const DimDesc &D, const double *ka, const double *kb, const double *kc,
+                                         const double *rot, const double *tab, double xv, double *col, int nt) {
+  const StoreCol st{col, D.ccol0, nt};
+  const double c0 = build_dim_any(D, ka, kb, kc, rot, tab, xv, st);
+  col[0] = c0;
+  for (int t = 1; t < D.ncol; ++t) col[(size_t)t * nt] *= c0;
+}
+
+// the dimension's interval tables into LDS (all threads of the block call it); -> the table base
+__device__ __forceinline__ const double *stage_tab(DimDesc &D, const double *__restrict__ tab, double *ltab) {
+  if (D.tab < 0) return tab;
+  const int sz = ((D.m + 1) & ~1) + (D.m + 1) * D.ncol * 6;
+  if (sz > kIntervalTabMax) return tab;
+  for (int e = threadIdx.x; e < sz; e += blockDim.x) ltab[e] = tab[D.tab + e];
+  __syncthreads();
+  D.tab = 0;
+  return ltab;
+}
+
+__device__ __forceinline__ int mean_offset(const DimDesc *__restrict__ dims, int l) {
+  int o = 0;
+  for (int i = 0; i < l; ++i) o += dims[i].ncol;
+  return o;
+}
+__device__ __forceinline__ int cov_offset(const DimDesc *__restrict__ dims, int l) {
+  int o = 0;
+  for (int i = 0; i < l; ++i) o += dims[i].ncol * dims[i].ncol;
+  return o;
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// part[k] = sum over the block of acc[k]: butterfly per wave, the waves in order
+template <int K>
+__device__ __forceinline__ void block_sums(const double (&acc)[K], double *red, double *__restrict__ part) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const double v = wave_sum(acc[k]);
+    if (lane == 0) red[wave * K + k] = v;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < K) {
+    double s = 0.0;
+    for (int w = 0; w < nw; ++w) s += red[w * K + threadIdx.x];
+    part[threadIdx.x] = s;
+  }
+}
+
+// dynamic LDS: [interval tables kIntervalTabMax][reduction 4 * 64][tile lmax * threads]
+template <int PASS>
+__global__ void __launch_bounds__(256)
+k_dim_moments(const DimDesc *__restrict__ dims, const double *__restrict__ ka, const double *__restrict__ kb,
+              const double *__restrict__ kc, const double *__restrict__ rot, const double *__restrict__ tab,
+              const double *__restrict__ x, uint64_t n, uint64_t ldx, const double *__restrict__ w, uint64_t ldw,
+              int nlt, const double *__restrict__ mean, double *__restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  double *ltab = smem, *red = smem + kIntervalTabMax, *tile = red + 4 * kMomP2;
+  const int l = blockIdx.y, nt = blockDim.x;
+  DimDesc D = dims[l];
+  const int L = D.ncol;
+  int ta = blockIdx.z, tb = 0;
+  if (PASS == 2) {
+    int z = blockIdx.z;
+    ta = 0;
+    while (z >= ta + 1) {
+      z -= ta + 1;
+      ++ta;
+    }
+    tb = z;
+  }
+  if (ta * kMomLT >= L) return;  // (block-uniform, before the first barrier)
+  const double *tb_ = stage_tab(D, tab, ltab);
+  double *col = tile + threadIdx.x;
+  constexpr int K = PASS == 1 ? kMomP1 : kMomP2;
+  double acc[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) acc[k] = 0.0;
+  double ma[kMomLT], mb[kMomLT];
+  if (PASS == 2) {
+    const int om = mean_offset(dims, l);
+#pragma unroll
+    for (int a = 0; a < kMomLT; ++a) {
+      ma[a] = ta * kMomLT + a < L ? mean[om + ta * kMomLT + a] : 0.0;
+      mb[a] = tb * kMomLT + a < L ? mean[om + tb * kMomLT + a] : 0.0;
+    }
+  }
+  for (uint64_t i = (uint64_t)blockIdx.x * nt + threadIdx.x; i < n; i += (uint64_t)gridDim.x * nt) {
+    const double xv = x[(uint64_t)l * ldx + i];
+    double wv = w ? w[(uint64_t)l * ldw + i] : 1.0;
+    eval_raw(D, ka, kb, kc, rot, tb_, xv, col, nt);
+    if (PASS == 1) {
+      if (!(wv >= 0.0) || wv > 1.7976931348623157e308) {
+        acc[kMomLT + 1] += 1.0;
+        wv = 0.0;
+      }
+      acc[kMomLT] += wv;
+#pragma unroll
+      for (int a = 0; a < kMomLT; ++a) {
+        const int t = ta * kMomLT + a;
+        if (t < L) acc[a] = fma(wv, col[(size_t)t * nt], acc[a]);
+      }
+    } else {
+      double da[kMomLT], db[kMomLT];
+#pragma unroll
+      for (int a = 0; a < kMomLT; ++a) {
+        const int t = ta * kMomLT + a, u = tb * kMomLT + a;
+        da[a] = t < L ? col[(size_t)t * nt] - ma[a] : 0.0;
+        db[a] = u < L ? col[(size_t)u * nt] - mb[a] : 0.0;
+      }
+      // w (D_t D_t'): the product of the two deviations first, so that (t, t') and (t', t) get the same bits
+#pragma unroll
+      for (int a = 0; a < kMomLT; ++a)
+#pragma unroll
+        for (int b = 0; b < kMomLT; ++b) acc[a * kMomLT + b] = fma(wv, da[a] * db[b], acc[a * kMomLT + b]);
+    }
+  }
+  __syncthreads();
+  block_sums<K>(acc, red, part + (((uint64_t)l * gridDim.z + blockIdx.z) * gridDim.x + blockIdx.x) * K);
+}
+
+// sum over the nblk row slices of entry k of K, every lane of the wave gets it
+template <int K>
+__device__ __forceinline__ double slices_sum(const double *__restrict__ base, int nblk, int k) {
+  double s = 0.0;
+  for (int b = threadIdx.x; b < nblk; b += 64) s += base[(uint64_t)b * K + k];
+  return wave_sum(s);
+}
+
+// block (dimension, level tile), one wave: the means, the weight sum of the dimension, the flag
+__global__ void __launch_bounds__(64)
+k_moments_fin1(const DimDesc *__restrict__ dims, const double *__restrict__ part, int nblk, int nlt,
+               double *__restrict__ mean, double *__restrict__ wsum, int *__restrict__ flag) {
+  const int l = blockIdx.x, tile = blockIdx.y, L = dims[l].ncol;
+  if (tile * kMomLT >= L) return;
+  const double *base = part + ((uint64_t)l * nlt + tile) * nblk * kMomP1;
+  const double W = slices_sum<kMomP1>(base, nblk, kMomLT), bad = slices_sum<kMomP1>(base, nblk, kMomLT + 1);
+  const int om = mean_offset(dims, l);
+  if (tile == 0 && threadIdx.x == 0) {
+    wsum[l] = W;
+    if (bad > 0.0 || !(W > 0.0) || W > 1.7976931348623157e308) flag[0] = 1;
+  }
+  for (int a = 0; a < kMomLT; ++a) {
+    const double s = slices_sum<kMomP1>(base, nblk, a);
+    const int t = tile * kMomLT + a;
+    if (t < L && threadIdx.x == 0) mean[om + t] = s / W;
+  }
+}
+
+// block (dimension, pair of level tiles), one wave: the covariances, mirrored
+__global__ void __launch_bounds__(64)
+k_moments_fin2(const DimDesc *__restrict__ dims, const double *__restrict__ part, int nblk, int nt2,
+               const double *__restrict__ wsum, double *__restrict__ cov) {
+  const int l = blockIdx.x, L = dims[l].ncol;
+  int z = blockIdx.y, ta = 0;
+  while (z >= ta + 1) {
+    z -= ta + 1;
+    ++ta;
+  }
+  const int tb = z;
+  if (ta * kMomLT >= L) return;
+  const double *base = part + ((uint64_t)l * nt2 + blockIdx.y) * nblk * kMomP2;
+  const double W = wsum[l];
+  const int oc = cov_offset(dims, l);
+  for (int k = 0; k < kMomP2; ++k) {
+    const int ia = ta * kMomLT + k / kMomLT, ib = tb * kMomLT + k % kMomLT;
+    if (ia >= L || ib > ia) continue;  // (wave-uniform)
+    const double s = slices_sum<kMomP2>(base, nblk, k);
+    if (threadIdx.x == 0) {
+      const double c = s / W;
+      cov[oc + ia * L + ib] = c;
+      cov[oc + ib * L + ia] = c;
+    }
+  }
+}
+
+// dynamic LDS as k_dim_moments; thread = grid point
+__global__ void __launch_bounds__(256)
+k_main_effect(const DimDesc *__restrict__ dims, const double *__restrict__ ka, const double *__restrict__ kb,
+              const double *__restrict__ kc, const double *__restrict__ rot, const double *__restrict__ tab, int l,
+              const double *__restrict__ g, int sum_l, int q, const double *__restrict__ grid, uint64_t G,
+              double *__restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  double *ltab = smem, *tile = smem + kIntervalTabMax + 4 * kMomP2;
+  DimDesc D = dims[l];
+  const int L = D.ncol, nt = blockDim.x, om = mean_offset(dims, l);
+  const double *tb_ = stage_tab(D, tab, ltab);
+  const uint64_t i = (uint64_t)blockIdx.x * nt + threadIdx.x;
+  if (i >= G) return;
+  double *col = tile + threadIdx.x;
+  eval_raw(D, ka, kb, kc, rot, tb_, grid[i], col, nt);
+  for (int j = 0; j < q; ++j) {
+    const double *gj = g + (uint64_t)j * sum_l + om;
+    double s = 0.0;
+    for (int t = 0; t < L; ++t) s = fma(gj[t], col[(size_t)t * nt], s);
+    out[(uint64_t)j * G + i] = s;
+  }
+}
+
+// thread = term: excl[k][l] = prod_{i != l} m_i[t_ki] (suffix products written first, then multiplied
+// by the running prefix), u[k] = the whole product
+__global__ void __launch_bounds__(256)
+k_sobol_excl(const uint8_t *__restrict__ lev, const int *__restrict__ meta, int p, int d,
+             const double *__restrict__ mtab, double *__restrict__ excl, double *__restrict__ u) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= p) return;
+  const uint8_t *lv = lev + (uint64_t)k * d;
+  double *e = excl + (uint64_t)k * d;
+  double s = 1.0;
+  for (int l = d - 1; l >= 0; --l) {
+    e[l] = s;
+    s *= mtab[meta[d + l] + lv[l]];
+  }
+  double pre = 1.0;
+  for (int l = 0; l < d; ++l) {
+    e[l] *= pre;
+    pre *= mtab[meta[d + l] + lv[l]];
+  }
+  u[k] = pre;
+}
+
+// block (dimension l or, at l = d, the mean; response j).  dynamic LDS: [g: lmax][tree: 256]
+__global__ void __launch_bounds__(256)
+k_sobol_first(const uint8_t *__restrict__ lev, const int *__restrict__ meta, int p, int d, int sum_l,
+              const double *__restrict__ Theta, const double *__restrict__ ctab, const double *__restrict__ excl,
+              const double *__restrict__ u, int lmax, double *__restrict__ out, double *__restrict__ g_out) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  double *gs = smem, *red = smem + lmax;
+  const int l = blockIdx.x, j = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const double *th = Theta + (uint64_t)j * p;
+  double *o = out + (uint64_t)j * (2 + 2 * d);
+  if (l == d) {
+    double s = 0.0;
+    for (int k = threadIdx.x; k < p; k += 256) s = fma(th[k], u[k], s);
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int off = 128; off >= 1; off >>= 1) {
+      if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) o[0] = red[0];
+    return;
+  }
+  const int L = meta[l], om = meta[d + l], oc = meta[2 * d + l];
+  for (int t = wave; t < L; t += 4) {
+    double s = 0.0;
+    for (int k = lane; k < p; k += 64)
+      if (lev[(uint64_t)k * d + l] == t) s = fma(th[k], excl[(uint64_t)k * d + l], s);
+    s = wave_sum(s);
+    if (lane == 0) {
+      gs[t] = s;
+      if (g_out) g_out[(uint64_t)j * sum_l + om + t] = s;
+    }
+  }
+  __syncthreads();
+  if (wave == 0) {
+    double s = 0.0;
+    for (int e = lane; e < L * L; e += 64) s = fma(gs[e / L] * ctab[oc + e], gs[e % L], s);
+    s = wave_sum(s);
+    if (lane == 0) o[2 + l] = s;
+  }
+}
+
+// dynamic LDS: [A: n_cov + 1][C: n_cov + 1][m m^T: n_cov + 1][reduction 2 * RC * (DC + 1)]; entry n_cov of the
+// tables is the factor of a dimension beyond d (A = 1, C = 0, m m = 1).  grid (tile pairs, response chunks,
+// dimension chunks); part[((zc * nrc + rc) * npairs + pair) * RC * (DC + 1) + r * (DC + 1) + jj], jj = DC: V
+template <int DC>
+__global__ void __launch_bounds__(kSobolTW)
+k_sobol_pairs(const uint8_t *__restrict__ lev, const int *__restrict__ meta, int p, int d, int q, int n_cov,
+              const double *__restrict__ Theta, const double *__restrict__ mtab, const double *__restrict__ ctab,
+              double *__restrict__ part) {
+  constexpr int RC = kSobolRC, NF = DC + 1;
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  double *tA = smem, *tC = tA + n_cov + 1, *tM = tC + n_cov + 1, *red = tM + n_cov + 1;
+  // the tile pair (I <= J) of this block
+  int I = 0, z = blockIdx.x;
+  const int ntile = (p + kSobolTW - 1) / kSobolTW;
+  while (z >= ntile - I) {
+    z -= ntile - I;
+    ++I;
+  }
+  const int J = I + z;
+  const int j0 = blockIdx.y * RC, c0 = blockIdx.z * DC;
+  for (int l = 0; l < d; ++l) {
+    const int L = meta[l], om = meta[d + l], oc = meta[2 * d + l];
+    for (int e = threadIdx.x; e < L * L; e += kSobolTW) {
+      const double c = ctab[oc + e], mm = mtab[om + e / L] * mtab[om + e % L];
+      tC[oc + e] = c;
+      tM[oc + e] = mm;
+      tA[oc + e] = c + mm;
+    }
+  }
+  if (threadIdx.x == 0) {
+    tA[n_cov] = 1.0;
+    tC[n_cov] = 0.0;
+    tM[n_cov] = 1.0;
+  }
+  __syncthreads();
+  const int k = I * kSobolTW + threadIdx.x;
+  const bool valid = k < p;
+  const uint8_t *lv = lev + (uint64_t)(valid ? k : p - 1) * d;  // (a lane beyond p: any term, its coefficient is 0)
+  int rowb[DC];
+#pragma unroll
+  for (int jj = 0; jj < DC; ++jj) {
+    const int l = c0 + jj;
+    rowb[jj] = l < d ? meta[2 * d + l] + (int)lv[l] * meta[l] : n_cov;
+  }
+  double th[RC], acc[RC][NF];
+#pragma unroll
+  for (int r = 0; r < RC; ++r) {
+    th[r] = valid && j0 + r < q ? Theta[(uint64_t)(j0 + r) * p + k] : 0.0;
+#pragma unroll
+    for (int jj = 0; jj < NF; ++jj) acc[r][jj] = 0.0;
+  }
+  const int nj = min(kSobolTW, p - J * kSobolTW);
+  for (int kk = 0; kk < nj; ++kk) {
+    const int k2 = J * kSobolTW + kk;                   // (wave-uniform)
+    const uint8_t *lp = lev + (uint64_t)k2 * d;
+    double pa = 1.0, dd = 0.0, sufa = 1.0;
+    for (int i = 0; i < c0; ++i) {                       // dimensions before the chunk (d > DC only)
+      const int idx = meta[2 * d + i] + (int)lv[i] * meta[i] + lp[i];
+      dd = fma(tM[idx], dd, pa * tC[idx]);
+      pa *= tA[idx];
+    }
+    for (int i = c0 + DC; i < d; ++i)                    // and behind it
+      sufa *= tA[meta[2 * d + i] + (int)lv[i] * meta[i] + lp[i]];
+    int idx[DC];
+    double f[DC];
+#pragma unroll
+    for (int jj = 0; jj < DC; ++jj) idx[jj] = rowb[jj] + (c0 + jj < d ? (int)lp[c0 + jj] : 0);
+    f[DC - 1] = sufa;
+#pragma unroll
+    for (int jj = DC - 1; jj >= 1; --jj) f[jj - 1] = f[jj] * tA[idx[jj]];
+#pragma unroll
+    for (int jj = 0; jj < DC; ++jj) {
+      const double pc = pa * tC[idx[jj]];
+      f[jj] *= pc;                                       // C_l prod_{i != l} A_i
+      dd = fma(tM[idx[jj]], dd, pc);                     // prod A - prod m m up to l
+      pa *= tA[idx[jj]];
+    }
+#pragma unroll
+    for (int r = 0; r < RC; ++r) {
+      const double wv = th[r] * Theta[(uint64_t)min(j0 + r, q - 1) * p + k2];
+#pragma unroll
+      for (int jj = 0; jj < DC; ++jj) acc[r][jj] = fma(wv, f[jj], acc[r][jj]);
+      acc[r][DC] = fma(wv, dd, acc[r][DC]);
+    }
+  }
+  // the block's partials: butterfly per wave, wave 0 + wave 1; an off-diagonal tile pair stands for its mirror too
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int r = 0; r < RC; ++r)
+#pragma unroll
+    for (int jj = 0; jj < NF; ++jj) {
+      const double v = wave_sum(acc[r][jj]);
+      if (lane == 0) red[wave * RC * NF + r * NF + jj] = v;
+    }
+  __syncthreads();
+  if ((int)threadIdx.x < RC * NF) {
+    const double s = red[threadIdx.x] + red[RC * NF + threadIdx.x];
+    part[(((uint64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * RC * NF + threadIdx.x] =
+        (I == J ? 1.0 : 2.0) * s;
+  }
+}
+
+// block (output o: VT_o for o < d, V at o = d; response j), one wave over the tile pairs
+__global__ void __launch_bounds__(64)
+k_sobol_reduce(const double *__restrict__ part, int npairs, int nrc, int ndc, int dc, int d, double *__restrict__ out) {
+  const int o = blockIdx.x, j = blockIdx.y, nf = dc + 1;
+  const int zc = o < d ? o / dc : ndc - 1, jj = o < d ? o % dc : dc;
+  const int rc = j / kSobolRC, r = j % kSobolRC;
+  const double *base = part + ((uint64_t)zc * nrc + rc) * npairs * kSobolRC * nf + r * nf + jj;
+  double s = 0.0;
+  for (int b = threadIdx.x; b < npairs; b += 64) s += base[(uint64_t)b * kSobolRC * nf];
+  s = wave_sum(s);
+  if (threadIdx.x == 0) out[(uint64_t)j * (2 + 2 * d) + (o < d ? 2 + d + o : 1)] = s;
+}
+
+// threads per block and dynamic LDS of the kernels that evaluate a basis tile
+inline int eval_threads(uint64_t lmax) { return lmax <= 32 ? 256 : 64; }
+inline size_t eval_lds(uint64_t lmax) {
+  return (kIntervalTabMax + 4 * kMomP2 + lmax * eval_threads(lmax)) * sizeof(double);
+}
+
+}  // namespace
+
+size_t sobol_pairs_lds(uint64_t d, uint64_t n_cov) {
+  return (3 * (n_cov + 1) + 2 * kSobolRC * (sobol_dim_chunk(d) + 1)) * sizeof(double);
+}
+
+uint64_t sobol_part_doubles(uint64_t p, uint64_t d, uint64_t q) {
+  const uint64_t dc = sobol_dim_chunk(d), ndc = (d + dc - 1) / dc, nrc = (q + kSobolRC - 1) / kSobolRC;
+  const uint64_t nt = (p + kSobolTW - 1) / kSobolTW;
+  return ndc * nrc * (nt * (nt + 1) / 2) * kSobolRC * (dc + 1);
+}
+
+int launch_dim_moments(const obhip_model &m, obhip_terms &t, const double *d_nodes, uint64_t n, uint64_t ldx,
+                       const double *d_w, uint64_t ldw, double *d_mean, double *d_cov, int *flag_out) {
+  OB_TRY(prepare_predict(m, t, false));
+  const ModelDev &md = t.pred_md;
+  const uint64_t d = m.d;
+  uint64_t lmax = 1;
+  for (uint64_t l = 0; l < d; ++l) lmax = std::max<uint64_t>(lmax, t.maxlev[l] + 1);
+  const int nth = eval_threads(lmax);
+  const size_t lds = eval_lds(lmax);
+  const int nblk = (int)std::min<uint64_t>(kMomBlocks, (n + nth - 1) / nth);
+  const int nlt = (int)((lmax + kMomLT - 1) / kMomLT), nt2 = nlt * (nlt + 1) / 2;
+  DevBuf<double> part, wsum;
+  DevBuf<int> flag;
+  OB_TRY(part.alloc(d * nblk * std::max<uint64_t>((uint64_t)nlt * kMomP1, (uint64_t)nt2 * kMomP2)));
+  OB_TRY(wsum.alloc(d));
+  OB_TRY(flag.alloc(1));
+  OB_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), cur_stream()));
+  OB_TRY(ensure_dyn_lds((const void *)k_dim_moments<1>, lds));
+  OB_TRY(ensure_dyn_lds((const void *)k_dim_moments<2>, lds));
+  {
+    ProfScope ps("dim_moments");
+    hipLaunchKernelGGL(k_dim_moments<1>, dim3(nblk, (unsigned)d, nlt), dim3(nth), lds, cur_stream(), md.dims.p, md.ka.p,
+                       md.kb.p, md.kc.p, md.rot.p, md.tab.p, d_nodes, n, ldx, d_w, ldw, nlt, (const double *)nullptr,
+                       part.p);
+    hipLaunchKernelGGL(k_moments_fin1, dim3((unsigned)d, nlt), dim3(64), 0, cur_stream(), md.dims.p,
+                       (const double *)part.p, nblk, nlt, d_mean, wsum.p, flag.p);
+    hipLaunchKernelGGL(k_dim_moments<2>, dim3(nblk, (unsigned)d, nt2), dim3(nth), lds, cur_stream(), md.dims.p, md.ka.p,
+                       md.kb.p, md.kc.p, md.rot.p, md.tab.p, d_nodes, n, ldx, d_w, ldw, nlt, (const double *)d_mean,
+                       part.p);
+    hipLaunchKernelGGL(k_moments_fin2, dim3((unsigned)d, nt2), dim3(64), 0, cur_stream(), md.dims.p,
+                       (const double *)part.p, nblk, nt2, (const double *)wsum.p, d_cov);
+    OB_HIP(hipGetLastError());
+  }
+  return d2h(flag_out, flag.p, sizeof(int));  // (waits: the scratch above is released behind it)
+}
+
+int launch_sobol_first(const uint8_t *d_lev, const int *d_meta, uint64_t p, uint64_t d, uint64_t q, uint64_t lmax,
+                       uint64_t sum_l, const double *d_Theta, const double *d_mtab, const double *d_ctab, double *d_excl,
+                       double *d_u, double *d_out, double *d_g) {
+  ProfScope ps("sobol_first");
+  hipLaunchKernelGGL(k_sobol_excl, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, cur_stream(), d_lev, d_meta, (int)p,
+                     (int)d, d_mtab, d_excl, d_u);
+  hipLaunchKernelGGL(k_sobol_first, dim3((unsigned)d + 1, (unsigned)q), dim3(256), (lmax + 256) * sizeof(double),
+                     cur_stream(), d_lev, d_meta, (int)p, (int)d, (int)sum_l, d_Theta, d_ctab, (const double *)d_excl,
+                     (const double *)d_u, (int)lmax, d_out, d_g);
+  OB_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_sobol_pairs(const uint8_t *d_lev, const int *d_meta, uint64_t p, uint64_t d, uint64_t q, uint64_t n_cov,
+                       const double *d_Theta, const double *d_mtab, const double *d_ctab, double *d_part, double *d_out) {
+  const int dc = sobol_dim_chunk(d), ndc = (int)((d + dc - 1) / dc), nrc = (int)((q + kSobolRC - 1) / kSobolRC);
+  const int nt = (int)((p + kSobolTW - 1) / kSobolTW), npairs = nt * (nt + 1) / 2;
+  const size_t lds = sobol_pairs_lds(d, n_cov);
+  ProfScope ps("sobol_pairs");
+  const int rc = pick_or<8, 24>(dc, -1, [&](auto DCc) {
+    OB_TRY(ensure_dyn_lds((const void *)k_sobol_pairs<DCc()>, lds));
+    hipLaunchKernelGGL(k_sobol_pairs<DCc()>, dim3(npairs, nrc, ndc), dim3(kSobolTW), lds, cur_stream(), d_lev, d_meta,
+                       (int)p, (int)d, (int)q, (int)n_cov, d_Theta, d_mtab, d_ctab, d_part);
+    return 0;
+  });
+  if (rc < 0) return no_kernel();
+  OB_TRY(rc);
+  hipLaunchKernelGGL(k_sobol_reduce, dim3((unsigned)d + 1, (unsigned)q), dim3(64), 0, cur_stream(),
+                     (const double *)d_part, npairs, nrc, ndc, dc, (int)d, d_out);
+  OB_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_main_effect(const obhip_model &m, obhip_terms &t, uint64_t dim, const double *d_g, uint64_t q,
+                       const double *d_grid, uint64_t G, double *d_out) {
+  OB_TRY(prepare_predict(m, t, false));
+  const ModelDev &md = t.pred_md;
+  uint64_t lmax = 1, sum_l = 0;
+  for (uint64_t l = 0; l < m.d; ++l) {
+    lmax = std::max<uint64_t>(lmax, t.maxlev[l] + 1);
+    sum_l += t.maxlev[l] + 1;
+  }
+  const int nth = eval_threads(lmax);
+  const size_t lds = eval_lds(lmax);
+  OB_TRY(ensure_dyn_lds((const void *)k_main_effect, lds));
+  ProfScope ps("main_effect");
+  hipLaunchKernelGGL(k_main_effect, dim3((unsigned)((G + nth - 1) / nth)), dim3(nth), lds, cur_stream(), md.dims.p,
+                     md.ka.p, md.kb.p, md.kc.p, md.rot.p, md.tab.p, (int)dim, d_g, (int)sum_l, (int)q, d_grid, G, d_out);
+  OB_HIP(hipGetLastError());
+  return 0;
+}
+
+}  // namespace obhip

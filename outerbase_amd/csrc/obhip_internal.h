@@ -373,6 +373,10 @@ struct obhip_terms {
   uint64_t prec_version = 0;
   double prec_rho = 0.0;
   obhip::GramDedup dedup;             // redundant tile pairs of the panel Gram (levels only: no cap in its key)
+  // Sobol passes (sobol.cpp; levels only): the levels as bytes, [p][d], and per dimension l
+  // L_l = maxlev[l] + 1, its offset in a packed mean table and in a packed cov table ([3][d] ints)
+  obhip::DevBuf<uint8_t> sobol_lev;
+  obhip::DevBuf<int> sobol_meta;
   int prepare(const std::vector<int64_t> &cap, const std::vector<obhip::DimDesc> &dims);
 };
 
@@ -621,6 +625,24 @@ int launch_glm_rows(const GlmRows &r, double *d_sums, double *d_part);
 // d_eta (n, in/out) += o; d_mu = inverse link; d_varmu = (d mu / d eta)^2 d_vareta; o, mu, varmu may be null
 int launch_glm_response(int family, uint64_t n, const double *d_o, double *d_eta, const double *d_vareta,
                         double *d_mu, double *d_varmu);
+// kernels_sobol.hip: moment tables of the 1-D bases over a product measure and the variance
+// decomposition of the fitted mean on them (sobol.cpp; include/obhip.h, "variance-based sensitivity")
+constexpr int kSobolTW = 128;  // terms per tile of the pair sum (= threads of its blocks)
+constexpr int kSobolRC = 2;    // responses per chunk of the pair sum
+inline int sobol_dim_chunk(uint64_t d) { return d <= 8 ? 8 : 24; }  // accumulated dimensions per pass
+size_t sobol_pairs_lds(uint64_t d, uint64_t n_cov);                  // dynamic LDS of k_sobol_pairs
+uint64_t sobol_part_doubles(uint64_t p, uint64_t d, uint64_t q);     // partials of the pair sum
+// d_mean / d_cov: the packed tables; *flag_out != 0: a bad weight or a weight column without mass
+int launch_dim_moments(const obhip_model &m, obhip_terms &t, const double *d_nodes, uint64_t n, uint64_t ldx,
+                       const double *d_w, uint64_t ldw, double *d_mean, double *d_cov, int *flag_out);
+// meta: obhip_terms::sobol_meta; d_excl (p x d) and d_u (p): scratch
+int launch_sobol_first(const uint8_t *d_lev, const int *d_meta, uint64_t p, uint64_t d, uint64_t q, uint64_t lmax,
+                       uint64_t sum_l, const double *d_Theta, const double *d_mtab, const double *d_ctab, double *d_excl,
+                       double *d_u, double *d_out, double *d_g);
+int launch_sobol_pairs(const uint8_t *d_lev, const int *d_meta, uint64_t p, uint64_t d, uint64_t q, uint64_t n_cov,
+                       const double *d_Theta, const double *d_mtab, const double *d_ctab, double *d_part, double *d_out);
+int launch_main_effect(const obhip_model &m, obhip_terms &t, uint64_t dim, const double *d_g, uint64_t q,
+                       const double *d_grid, uint64_t G, double *d_out);
 // ---- runtime value -> template argument -----------------------------------------------------------
 // pick_or<1, 2, 4, 8>(ng, miss, [&](auto NG) { ... NG() ... }): the lambda is called with the
 // std::integral_constant of the listed value that v equals and its result returned; `miss` when v

@@ -1,0 +1,183 @@
+// Variance-based sensitivity of the fitted mean: the entry points (include/obhip.h, "variance-based
+// sensitivity").  No reference counterpart.  The kernels and their launches are in kernels_sobol.hip.
+// Every check that can refuse a call runs before the first device call.
+#include "obhip_internal.h"
+
+using namespace obhip;
+
+namespace {
+
+constexpr uint64_t kSobolMaxRows = 1ull << 40;
+constexpr uint64_t kSobolMaxQ = 65535;  // a grid dimension of the per-response kernels
+
+struct Layout {
+  uint64_t d = 0, lmax = 1, n_mean = 0, n_cov = 0;
+};
+
+// the packed-table layout of a term set; refuses what the kernels cannot hold
+int sobol_layout(const char *who, const obhip_terms &t, Layout &lay) {
+  lay.d = t.d;
+  if (t.d == 0 || t.d > 255) return fail(OBHIP_ERR_INVALID, std::string(who) + ": 1 to 255 dimensions");
+  for (uint64_t l = 0; l < t.d; ++l) {
+    if (t.maxlev[l] > 255)
+      return fail(OBHIP_ERR_INVALID, std::string(who) + ": a level beyond 255 in dimension " + std::to_string(l));
+    const uint64_t L = (uint64_t)t.maxlev[l] + 1;
+    lay.lmax = std::max(lay.lmax, L);
+    lay.n_mean += L;
+    lay.n_cov += L * L;
+  }
+  if (sobol_pairs_lds(t.d, lay.n_cov) > kLdsBudget)
+    return fail(OBHIP_ERR_INVALID, std::string(who) + ": the tables of these terms (" + std::to_string(lay.n_cov) +
+                                       " covariances) do not fit the LDS of a workgroup");
+  return 0;
+}
+
+uint64_t align256(uint64_t b) { return (b + 255) / 256 * 256; }
+
+// levels as bytes and the table offsets on the device, once per term set
+int ensure_sobol_tables(obhip_terms &t) {
+  if (t.sobol_lev.p && t.sobol_meta.p) return 0;
+  std::vector<uint8_t> lev(t.p * t.d);
+  for (uint64_t i = 0; i < t.p * t.d; ++i) lev[i] = (uint8_t)t.lev[i];
+  std::vector<int> meta(3 * t.d);
+  int om = 0, oc = 0;
+  for (uint64_t l = 0; l < t.d; ++l) {
+    const int L = (int)t.maxlev[l] + 1;
+    meta[l] = L;
+    meta[t.d + l] = om;
+    meta[2 * t.d + l] = oc;
+    om += L;
+    oc += L * L;
+  }
+  OB_TRY(t.sobol_lev.upload(lev.data(), lev.size()));
+  OB_TRY(t.sobol_meta.upload(meta.data(), meta.size()));
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int obhip_sobol_layout(const obhip_terms *t, uint64_t *n_mean, uint64_t *n_cov) {
+  if (!t) return fail(OBHIP_ERR_INVALID, "sobol_layout: null terms");
+  Layout lay;
+  OB_TRY(sobol_layout("sobol_layout", *t, lay));
+  if (n_mean) *n_mean = lay.n_mean;
+  if (n_cov) *n_cov = lay.n_cov;
+  return 0;
+}
+
+int obhip_dim_moments_dev(const obhip_model *m, const obhip_terms *t, const double *d_nodes, uint64_t n, uint64_t ldx,
+                          const double *d_weights, uint64_t ldw, double *d_mean, double *d_cov) {
+  if (!m || !t || !d_nodes || !d_mean || !d_cov)
+    return fail(OBHIP_ERR_INVALID, "dim_moments_dev: null model, terms, nodes, mean or cov");
+  if (n == 0) return fail(OBHIP_ERR_INVALID, "dim_moments_dev: no nodes, so no measure");
+  if (n > kSobolMaxRows) return fail(OBHIP_ERR_INVALID, "dim_moments_dev: more than 2^40 nodes in one call");
+  if (ldx < n) return fail(OBHIP_ERR_INVALID, "dim_moments_dev: leading dimension of the nodes below n");
+  if (d_weights && ldw < n) return fail(OBHIP_ERR_INVALID, "dim_moments_dev: leading dimension of the weights below n");
+  OB_TRY(check_compat(m, t));
+  Layout lay;
+  OB_TRY(sobol_layout("dim_moments_dev", *t, lay));
+  OB_TRY(require_device());
+  int flag = 0;
+  OB_TRY(launch_dim_moments(*m, *const_cast<obhip_terms *>(t), d_nodes, n, ldx, d_weights, ldw, d_mean, d_cov, &flag));
+  if (flag)
+    return fail(OBHIP_ERR_NUMERIC,
+                "dim_moments_dev: a weight is negative or not finite, or the weights of a dimension do not sum to > 0");
+  return 0;
+}
+
+int obhip_sobol_workspace_bytes(uint64_t p, uint64_t d, uint64_t q, uint64_t *bytes) {
+  if (!bytes || p == 0 || d == 0 || d > 255 || q == 0 || q > kSobolMaxQ || p > (1ull << 24))
+    return fail(OBHIP_ERR_INVALID, "sobol_workspace_bytes: null bytes, or p, d, q out of range");
+  *bytes = align256(p * d * sizeof(double)) + align256(p * sizeof(double)) +
+           align256(sobol_part_doubles(p, d, q) * sizeof(double));
+  return 0;
+}
+
+int obhip_sobol_dev(const obhip_terms *t, const double *d_Theta, uint64_t q, const double *d_mean_tab,
+                    const double *d_cov_tab, double *d_out, double *d_g, void *d_ws, uint64_t ws_bytes) {
+  if (!t || !d_Theta || !d_mean_tab || !d_cov_tab || !d_out || !d_ws)
+    return fail(OBHIP_ERR_INVALID, "sobol_dev: null terms, Theta, tables, out or workspace");
+  if (q == 0 || q > kSobolMaxQ) return fail(OBHIP_ERR_INVALID, "sobol_dev: 1 to 65535 responses");
+  Layout lay;
+  OB_TRY(sobol_layout("sobol_dev", *t, lay));
+  uint64_t need = 0;
+  OB_TRY(obhip_sobol_workspace_bytes(t->p, t->d, q, &need));
+  if (ws_bytes < need) return fail(OBHIP_ERR_INVALID, "sobol_dev: workspace smaller than obhip_sobol_workspace_bytes");
+  OB_TRY(require_device());
+  obhip_terms &tt = *const_cast<obhip_terms *>(t);
+  OB_TRY(ensure_sobol_tables(tt));
+  const uint64_t p = t->p, d = t->d;
+  char *ws = (char *)d_ws;
+  double *excl = (double *)ws;
+  double *u = (double *)(ws + align256(p * d * sizeof(double)));
+  double *part = (double *)(ws + align256(p * d * sizeof(double)) + align256(p * sizeof(double)));
+  OB_TRY(launch_sobol_first(tt.sobol_lev.p, tt.sobol_meta.p, p, d, q, lay.lmax, lay.n_mean, d_Theta, d_mean_tab,
+                            d_cov_tab, excl, u, d_out, d_g));
+  return launch_sobol_pairs(tt.sobol_lev.p, tt.sobol_meta.p, p, d, q, lay.n_cov, d_Theta, d_mean_tab, d_cov_tab, part,
+                            d_out);
+}
+
+int obhip_main_effect_dev(const obhip_model *m, const obhip_terms *t, uint64_t dim, const double *d_g, uint64_t q,
+                          const double *d_grid, uint64_t G, double *d_out) {
+  if (!m || !t || !d_g || !d_grid || !d_out)
+    return fail(OBHIP_ERR_INVALID, "main_effect_dev: null model, terms, g, grid or out");
+  if (q == 0 || q > kSobolMaxQ) return fail(OBHIP_ERR_INVALID, "main_effect_dev: 1 to 65535 responses");
+  if (G > kSobolMaxRows) return fail(OBHIP_ERR_INVALID, "main_effect_dev: more than 2^40 grid points in one call");
+  OB_TRY(check_compat(m, t));
+  if (dim >= m->d) return fail(OBHIP_ERR_INVALID, "main_effect_dev: dimension out of range");
+  Layout lay;
+  OB_TRY(sobol_layout("main_effect_dev", *t, lay));
+  if (G == 0) return 0;
+  OB_TRY(require_device());
+  return launch_main_effect(*m, *const_cast<obhip_terms *>(t), dim, d_g, q, d_grid, G, d_out);
+}
+
+int obhip_dim_moments(const obhip_model *m, const obhip_terms *t, const double *nodes, uint64_t n, uint64_t ldx,
+                      const double *weights, uint64_t ldw, double *mean, double *cov) {
+  if (!m || !t || !nodes || !mean || !cov)
+    return fail(OBHIP_ERR_INVALID, "dim_moments: null model, terms, nodes, mean or cov");
+  if (n == 0) return fail(OBHIP_ERR_INVALID, "dim_moments: no nodes, so no measure");
+  if (n > kSobolMaxRows) return fail(OBHIP_ERR_INVALID, "dim_moments: more than 2^40 nodes in one call");
+  if (ldx < n) return fail(OBHIP_ERR_INVALID, "dim_moments: leading dimension of the nodes below n");
+  if (weights && ldw < n) return fail(OBHIP_ERR_INVALID, "dim_moments: leading dimension of the weights below n");
+  OB_TRY(check_compat(m, t));
+  Layout lay;
+  OB_TRY(sobol_layout("dim_moments", *t, lay));
+  OB_TRY(require_device());
+  DevBuf<double> dx, dw, dm, dc;
+  OB_TRY(upload_cols(dx, nodes, n, m->d, ldx));
+  if (weights) OB_TRY(upload_cols(dw, weights, n, m->d, ldw));
+  OB_TRY(dm.alloc(lay.n_mean));
+  OB_TRY(dc.alloc(lay.n_cov));
+  OB_TRY(obhip_dim_moments_dev(m, t, dx.p, n, n, dw.p, n, dm.p, dc.p));
+  OB_TRY(d2h(mean, dm.p, lay.n_mean * sizeof(double)));
+  return d2h(cov, dc.p, lay.n_cov * sizeof(double));
+}
+
+int obhip_sobol(const obhip_terms *t, const double *Theta, uint64_t q, const double *mean_tab, const double *cov_tab,
+                double *out, double *g) {
+  if (!t || !Theta || !mean_tab || !cov_tab || !out)
+    return fail(OBHIP_ERR_INVALID, "sobol: null terms, Theta, tables or out");
+  if (q == 0 || q > kSobolMaxQ) return fail(OBHIP_ERR_INVALID, "sobol: 1 to 65535 responses");
+  Layout lay;
+  OB_TRY(sobol_layout("sobol", *t, lay));
+  uint64_t wsb = 0;
+  OB_TRY(obhip_sobol_workspace_bytes(t->p, t->d, q, &wsb));
+  OB_TRY(require_device());
+  DevBuf<double> dth, dm, dc, dout, dg;
+  DevBuf<char> ws;
+  OB_TRY(dth.upload(Theta, t->p * q));
+  OB_TRY(dm.upload(mean_tab, lay.n_mean));
+  OB_TRY(dc.upload(cov_tab, lay.n_cov));
+  OB_TRY(dout.alloc(q * (2 + 2 * t->d)));
+  if (g) OB_TRY(dg.alloc(q * lay.n_mean));
+  OB_TRY(ws.alloc(wsb));
+  OB_TRY(obhip_sobol_dev(t, dth.p, q, dm.p, dc.p, dout.p, dg.p, ws.p, wsb));
+  OB_TRY(d2h(out, dout.p, q * (2 + 2 * t->d) * sizeof(double)));
+  if (g) OB_TRY(d2h(g, dg.p, q * lay.n_mean * sizeof(double)));
+  return 0;
+}
+
+}  // extern "C"

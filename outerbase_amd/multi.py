@@ -152,6 +152,26 @@ class MultiFit:
              dw.data_ptr(), n, None, out.data_ptr())
         return out.cpu().numpy().T
 
+    def sobol(self, nodes, weights=None):
+        """Sobol indices of every response under the product measure of nodes / weights
+        (sensitivity.input_moments), in raw units: SobolResult with mean = y_cent + y_sca mu, the variances
+        times y_sca^2 and the indices unchanged."""
+        from . import sensitivity
+        mom = sensitivity.input_moments(self.om, self._t, nodes, weights)
+        res = sensitivity.sobol(self.om, self._t, self.coeff, mom)
+        s2 = self.y_sca * self.y_sca
+        res.mean = self.y_cent + self.y_sca * res.mean
+        res.var = res.var * s2
+        res.first_var = res.first_var * s2[None, :]
+        res.total_var = res.total_var * s2[None, :]
+        return res
+
+    def main_effects(self, dim, grid, nodes, weights=None):
+        """E[f | x_dim = z] - E[f] of every response at the points of grid (G x q), in raw units (times y_sca)"""
+        from . import sensitivity
+        mom = sensitivity.input_moments(self.om, self._t, nodes, weights)
+        return sensitivity.main_effects(self.om, self._t, self.coeff, mom, dim, grid) * self.y_sca[None, :]
+
     def torch(self):
         """a differentiable torch module of the de-standardised predictor (torch_emulator.TorchEmulator)"""
         from .torch_emulator import TorchEmulator

@@ -1,0 +1,153 @@
+"""Sobol indices and main effects of the fitted mean, in closed form.
+
+The fitted mean is a sum of products of one-dimensional functions, f(x) = sum_k theta_k prod_l
+psi_{l, t_kl}(x_l) with psi_l = getbase(l).  Under independent inputs with a discrete measure per
+dimension (nodes and weights), its variance decomposition is a sum over per-dimension moment tables
+of the psi (include/obhip.h, "variance-based sensitivity"): no pick-freeze sampling, no sampling
+error.  The measure is what the caller passes as nodes: the training rows themselves (empirical
+marginals) or a quadrature rule of a density (uniform_nodes).
+
+torch holds the device memory; all arithmetic is in libobhip.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import obmod
+from ._lib import call
+
+
+def _device():
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    call("obhip_set_stream", C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    return torch, dev
+
+
+def _levels(t):
+    return (t.maxlevels() + 1).astype(np.int64)
+
+
+class InputMoments:
+    """Result of input_moments: mean[l] (L_l) and cov[l] (L_l x L_l) per dimension, L_l = 1 + the highest
+    level the terms use in dimension l, and the packed device copies mean_dev / cov_dev that sobol and
+    main_effects read."""
+
+    def __init__(self, terms, levels, mean_dev, cov_dev):
+        self.terms, self.levels = terms, levels
+        self.mean_dev, self.cov_dev = mean_dev, cov_dev
+        pm, pc = mean_dev.cpu().numpy(), cov_dev.cpu().numpy()
+        om_ = np.concatenate([[0], np.cumsum(levels)])
+        oc_ = np.concatenate([[0], np.cumsum(levels * levels)])
+        self.mean = [pm[om_[l]:om_[l + 1]].copy() for l in range(len(levels))]
+        self.cov = [pc[oc_[l]:oc_[l + 1]].reshape(levels[l], levels[l]).copy() for l in range(len(levels))]
+
+
+class SobolResult:
+    """mean (q), var (q); first_var, total_var, first, total (d x q each): Var E[f | x_l], V - Var E[f | x_~l]
+    and their shares S_l, T_l of var (NaN where var == 0); g: the packed g_l on the device (main effects)."""
+
+    def __init__(self, out, d, g_dev):
+        self.mean, self.var = out[:, 0].copy(), out[:, 1].copy()
+        self.first_var = np.ascontiguousarray(out[:, 2:2 + d].T)
+        self.total_var = np.ascontiguousarray(out[:, 2 + d:2 + 2 * d].T)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            v = np.where(self.var == 0.0, np.nan, self.var)
+            self.first, self.total = self.first_var / v, self.total_var / v
+        self.g = g_dev
+
+
+def _check_nodes(om, nodes, weights):
+    nodes = np.asarray(nodes, dtype=np.float64)
+    if nodes.ndim != 2 or nodes.shape[1] != om.d:
+        raise ValueError("nodes must be n x d")
+    if nodes.shape[0] == 0:
+        raise ValueError("nodes has no rows: there is no measure")
+    if weights is not None:
+        weights = np.asarray(weights, dtype=np.float64)
+        if weights.shape != nodes.shape:
+            raise ValueError("weights must be n x d like nodes")
+    return nodes, weights
+
+
+def _check_theta(t, Theta):
+    Theta = np.asarray(Theta, dtype=np.float64)
+    if Theta.ndim == 1:
+        Theta = Theta[:, None]
+    if Theta.ndim != 2 or Theta.shape[0] != t.p:
+        raise ValueError("Theta must have one row per term")
+    if Theta.shape[1] == 0:
+        raise ValueError("Theta has no columns")
+    return Theta
+
+
+def uniform_nodes(lo, hi, order=64):
+    """(nodes, weights), order x d each: the Gauss-Legendre rule of `order` points on [lo_l, hi_l] per dimension
+    (numpy.polynomial.legendre.leggauss), for inputs uniform on a box; the weights of a dimension sum to
+    hi_l - lo_l and are normalised by the library.  The indices are exact for this discrete measure; how well it
+    stands for the continuous uniform density is the quadrature order, the caller's accuracy knob."""
+    lo, hi = np.atleast_1d(np.asarray(lo, dtype=np.float64)), np.atleast_1d(np.asarray(hi, dtype=np.float64))
+    if lo.shape != hi.shape or lo.ndim != 1 or not np.all(hi > lo):
+        raise ValueError("lo and hi must be vectors of one length with hi > lo")
+    if int(order) < 1:
+        raise ValueError("order must be >= 1")
+    z, w = np.polynomial.legendre.leggauss(int(order))
+    half, mid = 0.5 * (hi - lo), 0.5 * (hi + lo)
+    return mid[None, :] + half[None, :] * z[:, None], half[None, :] * w[:, None]
+
+
+def input_moments(om, terms, nodes, weights=None):
+    """The moment tables of the 1-D bases over the product measure of nodes (n x d) and weights (n x d, >= 0,
+    normalised per dimension; None: all equal) -- obhip_dim_moments_dev."""
+    nodes, weights = _check_nodes(om, nodes, weights)
+    t = obmod._terms_of(om, terms)
+    torch, dev = _device()
+    n = nodes.shape[0]
+    nm, nc = C.c_uint64(0), C.c_uint64(0)
+    call("obhip_sobol_layout", t._h, C.byref(nm), C.byref(nc))
+    dx = torch.from_numpy(np.ascontiguousarray(nodes.T)).to(dev)
+    dw = None if weights is None else torch.from_numpy(np.ascontiguousarray(weights.T)).to(dev)
+    mean = torch.empty(nm.value, dtype=torch.float64, device=dev)
+    cov = torch.empty(nc.value, dtype=torch.float64, device=dev)
+    call("obhip_dim_moments_dev", om._h, t._h, dx.data_ptr(), n, n, None if dw is None else dw.data_ptr(), n,
+         mean.data_ptr(), cov.data_ptr())
+    return InputMoments(t, _levels(t), mean, cov)
+
+
+def sobol(om, terms, Theta, moments):
+    """SobolResult of the responses Theta (p x q, or p) under the measure of `moments` -- obhip_sobol_dev."""
+    t = obmod._terms_of(om, terms)
+    Theta = _check_theta(t, Theta)
+    torch, dev = _device()
+    q, d = Theta.shape[1], t.d
+    wsb = C.c_uint64(0)
+    call("obhip_sobol_workspace_bytes", t.p, d, q, C.byref(wsb))
+    dth = torch.from_numpy(np.ascontiguousarray(Theta.T)).to(dev)
+    ws = torch.empty(wsb.value, dtype=torch.uint8, device=dev)
+    out = torch.empty((q, 2 + 2 * d), dtype=torch.float64, device=dev)
+    g = torch.empty((q, int(moments.levels.sum())), dtype=torch.float64, device=dev)
+    call("obhip_sobol_dev", t._h, dth.data_ptr(), q, moments.mean_dev.data_ptr(), moments.cov_dev.data_ptr(),
+         out.data_ptr(), g.data_ptr(), ws.data_ptr(), wsb.value)
+    torch.cuda.synchronize()
+    return SobolResult(out.cpu().numpy(), d, g)
+
+
+def main_effects(om, terms, Theta, moments, dim, grid):
+    """E[f | x_dim = z] - E[f] at the points z of grid (G), G x q: the main-effect curve of every response."""
+    t = obmod._terms_of(om, terms)
+    Theta = _check_theta(t, Theta)
+    grid = np.ascontiguousarray(grid, dtype=np.float64)
+    if grid.ndim != 1:
+        raise ValueError("grid must be a vector")
+    if not 0 <= int(dim) < t.d:
+        raise ValueError("dim out of range (0-based)")
+    res = sobol(om, t, Theta, moments)
+    q, G = Theta.shape[1], grid.shape[0]
+    if G == 0:
+        return np.zeros((0, q))
+    torch, dev = _device()
+    dz = torch.from_numpy(grid).to(dev)
+    out = torch.empty((q, G), dtype=torch.float64, device=dev)
+    call("obhip_main_effect_dev", om._h, t._h, int(dim), res.g.data_ptr(), q, dz.data_ptr(), G, out.data_ptr())
+    out -= torch.from_numpy(res.mean).to(dev)[:, None]
+    return out.cpu().numpy().T
