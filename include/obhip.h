@@ -68,6 +68,10 @@ typedef struct obhip_comm obhip_comm;   /* the ranks of a row-sharded job (no re
 typedef struct obhip_normal_acc obhip_normal_acc; /* the normal equations of the rows seen so far
                                                      (no reference counterpart: obfit takes all
                                                      rows at once, R/fitting.R:40-120) */
+typedef struct obhip_posterior obhip_posterior;   /* the posterior covariance of the coefficients,
+                                                     resident on the device (no reference
+                                                     counterpart: predr_std inverts H per call,
+                                                     loglik_std.cpp:227) */
 
 /* ---- library ----------------------------------------------------------- */
 /* 5.  (2 -> 3: obhip_standardise_dev, obhip_destandardise_dev, obhip_fit_newton_count,
@@ -903,6 +907,60 @@ int obhip_predict_std(const obhip_model *m, const obhip_terms *t, const double *
 int obhip_margadj_full(const obhip_basis *b, const obhip_terms *t, const obhip_model *m,
                        const double *H, double sigma, double rho, double *val, double *gradhyp,
                        double *gradpara);
+
+/* ---- posterior handle and sequential design (no reference counterpart) -------------------
+ * An obhip_posterior owns, for one model and term set, the total Hessian H (p x p), its factor
+ * H = L L^T with X = L^-T, and sigma.  All variances are in standardised units, without the noise
+ * e^{2 sigma} unless asked for.  d_x is column-major n x d (leading dimension n), on the device.
+ * Every argument check runs before the first launch and a refused call changes nothing; a Hessian
+ * that is not positive definite is OBHIP_ERR_NUMERIC, as the other solve entries report it (the
+ * create entries wait for their factorisation). */
+/* d_H: symmetric p x p on the device, copied */
+int obhip_posterior_create_dev(obhip_posterior **out, const obhip_model *m, const obhip_terms *t,
+                               const double *d_H, double sigma);
+int obhip_posterior_destroy(obhip_posterior *post);
+/* p, sigma and log det H = 2 sum log L_kk; any pointer may be NULL */
+int obhip_posterior_info(const obhip_posterior *post, uint64_t *p, double *sigma, double *logdet);
+/* H formed exactly as obhip_normal_acc_solve_dev forms it: e^{-2 sigma} (T - T_minus) + diag(prec);
+ * minus may be NULL.  Neither accumulator is written. */
+int obhip_normal_acc_posterior_dev(const obhip_normal_acc *acc, const obhip_normal_acc *minus,
+                                   double sigma, double rho, obhip_posterior **out);
+/* d_var[i] = b_i^T inv(H) b_i (+ e^{2 sigma} when with_noise) at the n rows of d_x; n = 0: no-op */
+int obhip_posterior_var_dev(const obhip_posterior *post, const double *d_x, uint64_t n,
+                            double *d_var, int with_noise);
+/* *out = a NEW handle for H + e^{-2 sigma} B^T B of the n rows of d_x (the Gram kernels): the
+ * posterior once the simulator has been run at those rows, whatever it returns. */
+int obhip_posterior_condition_dev(const obhip_posterior *post, const double *d_x, uint64_t n,
+                                  obhip_posterior **out);
+
+/* Greedy sequential design over m candidate rows d_xcand (column-major m x d).  With nu =
+ * e^{2 sigma}, d_i = b_i^T inv(H) b_i and a run at j taking H to H + b_j b_j^T / nu:
+ *   OBHIP_DESIGN_MAXVAR  picks argmax w_i d_i (greedy D-optimality: log det H grows by
+ *                        log(1 + d_j / nu)); score = w_j d_j, trace[t] = the cumulative gain;
+ *   OBHIP_DESIGN_IMSE    picks argmax w_i num_i / (nu + d_i), num_i = b_i^T S M S b_i, S = inv(H),
+ *                        M = sum_r u_r b_r b_r^T / sum u over the r reference rows d_xref
+ *                        (column-major r x d): the drop of the integrated variance tr(M S);
+ *                        score = that weighted drop, trace[t] = tr(M S_t).
+ * After every pick S, d and num are downdated by the rank-one formulas: per
+ * step the candidates are passed over once, in one kernel, and the host waits for the device once.
+ * The lowest index wins a tie; a candidate that is already picked (replace = 0), has weight 0 or
+ * a score that is not finite is never picked.  d_weights (m) and d_uref (r) may be NULL: all ones;
+ * d_xref, r, d_uref are ignored for MAXVAR.  Out: d_index (k, int64) and d_score (k), of which
+ * *n_picked are written -- fewer than k when no eligible candidate is left, which is no error --
+ * d_var (m, may be NULL): d_i after all picks; d_trace (k + 1, may be NULL): entries 0 .. *n_picked.
+ * No atomics anywhere: two calls give the same bits.  u with a negative or non-finite entry or
+ * without mass: OBHIP_ERR_NUMERIC. */
+#define OBHIP_DESIGN_MAXVAR 0
+#define OBHIP_DESIGN_IMSE 1
+int obhip_design_select_dev(const obhip_posterior *post, const double *d_xcand, uint64_t m,
+                            int criterion, const double *d_xref, uint64_t r, const double *d_uref,
+                            const double *d_weights, uint64_t k, int replace, int64_t *d_index,
+                            double *d_score, double *d_var, double *d_trace, uint64_t *n_picked);
+/* the same on host buffers; xcand m x d and xref r x d column-major with leading dimensions m, r */
+int obhip_design_select(const obhip_posterior *post, const double *xcand, uint64_t m, int criterion,
+                        const double *xref, uint64_t r, const double *uref, const double *weights,
+                        uint64_t k, int replace, int64_t *index, double *score, double *var,
+                        double *trace, uint64_t *n_picked);
 
 /* ---- the model layer: lpdf, loglik_*, logpr_gauss, lpdfvec, predictor ------------------
  * Module rows src/interfaceR.cpp:696-762; classes src/fit.h:23-361; arithmetic

@@ -34,7 +34,7 @@ _BASE = {
     "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint16_t": C.c_uint16, "void": None, "char": C.c_char, "size_t": C.c_size_t,
 }
 _HANDLES = ("obhip_model", "obhip_basis", "obhip_terms", "obhip_comm", "obhip_lpdf",
-            "obhip_predictor", "obhip_normal_acc")
+            "obhip_predictor", "obhip_normal_acc", "obhip_posterior")
 _STRUCTS = ("obhip_glm_info",)  # small host structs, passed by address
 
 

@@ -311,6 +311,31 @@ int obhip_normal_acc_solve_dev(const obhip_normal_acc *acc, const obhip_normal_a
   return solve_columns(p, d_H, d_cholws, rhs.p + p, q - 1, 1.0, d_Theta + p, (char *)d_workspace + single);
 }
 
+// the posterior of the rows in acc (without those of minus): H as obhip_normal_acc_solve_dev forms it
+int obhip_normal_acc_posterior_dev(const obhip_normal_acc *acc, const obhip_normal_acc *minus, double sigma, double rho,
+                                   obhip_posterior **out) {
+  if (!acc || !out || !std::isfinite(sigma) || !std::isfinite(rho))
+    return fail(OBHIP_ERR_INVALID, "normal_acc_posterior_dev: bad argument");
+  if (minus && (minus->model != acc->model || !same_terms(minus->terms, acc->terms) || minus->p != acc->p || minus->q != acc->q))
+    return fail(OBHIP_ERR_INVALID, "normal_acc_posterior_dev: the accumulators differ in model, terms or responses");
+  const obhip_model *m = acc->model;
+  OB_TRY(check_compat(m, acc->terms));
+  OB_TRY(check_version(acc, "normal_acc_posterior_dev"));
+  if (minus) OB_TRY(check_version(minus, "normal_acc_posterior_dev"));
+  if (minus && (minus->rows > acc->rows || minus->geq > acc->geq))
+    return fail(OBHIP_ERR_STATE, "normal_acc_posterior_dev: more rows to take out than the accumulator holds");
+  OB_TRY(require_device());
+  obhip_terms &t = *const_cast<obhip_terms *>(acc->terms);
+  const uint64_t p = acc->p;
+  const double *d_prec = nullptr;
+  OB_TRY(terms_prec_dev(m, t, rho, &d_prec));
+  const double *d_minus = minus && (minus->rows > 0 || minus->geq > 0) ? minus->st.p : nullptr;
+  DevBuf<double> H;
+  OB_TRY(H.alloc(p * p));
+  OB_TRY(launch_unpack_tri(p, acc->st.p, d_minus, H.p, true, std::exp(-2.0 * sigma), d_prec, nullptr));
+  return posterior_from_hessian(out, m, acc->terms, H.p, sigma);
+}
+
 int obhip_cv_score_dev(const double *d_mean, const double *d_Y_raw, uint64_t n, uint64_t q, uint64_t ld,
                        const double *d_meansd, double *d_out) {
   if (!d_out || q == 0 || q > kMaxResponses || (n != 0 && (!d_mean || !d_Y_raw || ld < n)))

@@ -560,6 +560,51 @@ struct PostFactor {
 int post_factor_build(const double *d_H, uint64_t p, PostFactor &f, bool want_inverse);
 int post_var_dev(const obhip_model &m, obhip_terms &t, const PostFactor &f, const double *d_x,
                  uint64_t n, double e2sigma, double *d_var);
+}  // namespace obhip
+// posterior.cpp: the device-resident posterior of one model and term set (include/obhip.h)
+struct obhip_posterior {
+  const obhip_model *model = nullptr;
+  const obhip_terms *terms = nullptr;
+  uint64_t p = 0;
+  double sigma = 0.0, logdet = 0.0;
+  obhip::DevBuf<double> H;  // p x p, symmetric
+  obhip::PostFactor f;
+};
+namespace obhip {
+// *out = a new handle that takes the symmetric p x p d_H over (copied); waits for the factorisation
+int posterior_from_hessian(obhip_posterior **out, const obhip_model *m, const obhip_terms *t, const double *d_H,
+                           double sigma);
+// design.cpp / kernels_design.hip: one greedy step of the sequential design over the candidates (fused: the
+// basis of a 64-row tile in LDS, a = B s and c = B h on the matrix cores, downdate, score and argmax in
+// the epilogue) and the p-space work between two steps
+constexpr int kDesignScal = 8;  // doubles of the step's scalar block: gamma, tau, d_j, nu, -, nothing left, -, -
+struct DesignStep {
+  int crit = 0;
+  bool replace = false;
+  uint64_t n = 0;
+  const double *x = nullptr;        // candidates, column-major n x d
+  const double *w = nullptr;        // weights or null
+  const double *sh = nullptr;       // [p][16] term-major: column 0 = s, column 1 = h, the rest zero
+  const double *scal = nullptr;     // kDesignScal doubles the previous step wrote
+  double *dvar = nullptr, *num = nullptr;  // n each (num: IMSE only)
+  const uint8_t *picked = nullptr;  // n
+  double *part_score = nullptr;     // per workgroup
+  int64_t *part_idx = nullptr;
+};
+bool design_step_supports(const obhip_terms &t);
+uint64_t design_step_parts(uint64_t n, bool fused);
+int launch_design_step(const obhip_model &m, obhip_terms &t, const DesignStep &s);
+// the same downdate, score and argmax with a = ac[i] and c = ac[n + i] read from HBM
+int launch_design_update(const DesignStep &s, const double *d_ac);
+// part[] -> the step's pick: index and score appended at slot `step`, x_j gathered into d_xj (1 x d), the row
+// marked in picked; no eligible candidate: scal[5] = 1 and nothing else written
+int launch_design_pick(const DesignStep &s, uint64_t nparts, uint64_t d, uint64_t step, int64_t *d_index,
+                       double *d_score, double *d_xj, uint8_t *d_picked, double *d_scal);
+// s = S b, h = T b (T null: h = 0), gamma = nu + b.s, tau = b.h into scal, trace[step + 1], the [p][16] block,
+// then S -= s s^T / gamma and T -= (s h^T + h s^T) / gamma - s s^T tau / gamma^2
+int launch_design_pspace(int crit, uint64_t p, uint64_t pp, const double *d_b, double *d_S, double *d_T, double *d_sv,
+                         double *d_hv, double *d_sh, double *d_scal, double *d_trace, uint64_t step);
+
 // kernels_grad.hip
 int ensure_gradbasis(obhip_basis &b);
 int ensure_gradbasis_sq(obhip_basis &b);

@@ -202,3 +202,87 @@ extern "C" int obhip_margadj_full(const obhip_basis *bc, const obhip_terms *tc, 
   }
   return 0;
 }
+
+// ---- the device-resident posterior handle (include/obhip.h, "posterior handle") ------------------
+namespace obhip {
+int posterior_from_hessian(obhip_posterior **out, const obhip_model *m, const obhip_terms *t, const double *d_H,
+                           double sigma) {
+  std::unique_ptr<obhip_posterior> q(new obhip_posterior());
+  const uint64_t p = t->p;
+  q->model = m;
+  q->terms = t;
+  q->p = p;
+  q->sigma = sigma;
+  OB_TRY(q->H.alloc(p * p));
+  OB_HIP(hipMemcpyAsync(q->H.p, d_H, p * p * sizeof(double), hipMemcpyDeviceToDevice, cur_stream()));
+  OB_TRY(post_factor_build(q->H.p, p, q->f, true));  // OBHIP_ERR_NUMERIC: not positive definite
+  std::vector<double> ld(p);
+  OB_HIP(hipMemcpy2DAsync(ld.data(), sizeof(double), q->f.L.p, (p + 1) * sizeof(double), sizeof(double), p,
+                          hipMemcpyDeviceToHost, cur_stream()));
+  OB_HIP(hipStreamSynchronize(cur_stream()));
+  double logdet = 0;
+  for (double v : ld) logdet += 2.0 * std::log(v);
+  q->logdet = logdet;
+  *out = q.release();
+  return 0;
+}
+}  // namespace obhip
+
+extern "C" int obhip_posterior_create_dev(obhip_posterior **out, const obhip_model *m, const obhip_terms *t,
+                                          const double *d_H, double sigma) {
+  if (!out || !m || !t || !d_H || !std::isfinite(sigma))
+    return fail(OBHIP_ERR_INVALID, "posterior_create_dev: bad argument");
+  OB_TRY(check_compat(m, t));
+  OB_TRY(require_device());
+  return posterior_from_hessian(out, m, t, d_H, sigma);
+}
+
+extern "C" int obhip_posterior_destroy(obhip_posterior *post) {
+  if (post) (void)hipStreamSynchronize(cur_stream());
+  delete post;
+  return 0;
+}
+
+extern "C" int obhip_posterior_info(const obhip_posterior *post, uint64_t *p, double *sigma, double *logdet) {
+  if (!post) return fail(OBHIP_ERR_INVALID, "posterior_info: null argument");
+  if (p) *p = post->p;
+  if (sigma) *sigma = post->sigma;
+  if (logdet) *logdet = post->logdet;
+  return 0;
+}
+
+extern "C" int obhip_posterior_var_dev(const obhip_posterior *post, const double *d_x, uint64_t n, double *d_var,
+                                       int with_noise) {
+  if (!post || (n != 0 && (!d_x || !d_var))) return fail(OBHIP_ERR_INVALID, "posterior_var_dev: null argument");
+  OB_TRY(check_compat(post->model, post->terms));
+  if (post->terms->p != post->p) return fail(OBHIP_ERR_INVALID, "posterior_var_dev: the terms changed since the handle was made");
+  OB_TRY(require_device());
+  if (n == 0) return 0;
+  return post_var_dev(*post->model, *const_cast<obhip_terms *>(post->terms), post->f, d_x, n,
+                      with_noise ? std::exp(2.0 * post->sigma) : 0.0, d_var);
+}
+
+extern "C" int obhip_posterior_condition_dev(const obhip_posterior *post, const double *d_x, uint64_t n,
+                                             obhip_posterior **out) {
+  if (!post || !out || !d_x || n == 0) return fail(OBHIP_ERR_INVALID, "posterior_condition_dev: bad argument");
+  OB_TRY(check_compat(post->model, post->terms));
+  if (post->terms->p != post->p)
+    return fail(OBHIP_ERR_INVALID, "posterior_condition_dev: the terms changed since the handle was made");
+  OB_TRY(require_device());
+  obhip_terms &t = *const_cast<obhip_terms *>(post->terms);
+  const uint64_t p = post->p;
+  obhip_basis *b = nullptr;
+  OB_TRY(obhip_basis_create_dev(&b, post->model, d_x, n, t.maxlev.data()));
+  struct Guard {
+    obhip_basis *b;
+    ~Guard() { obhip_basis_destroy(b); }
+  } guard{b};
+  DevBuf<double> G;
+  OB_TRY(G.alloc(p * p));
+  OB_TRY(launch_gram(*b, t, G.p));
+  const double e2 = std::exp(-2.0 * post->sigma);
+  const double *H = post->H.p;
+  double *g = G.p;
+  OB_TRY(vmap(p * p, [=] __device__(uint64_t i) { g[i] = H[i] + e2 * g[i]; }));
+  return posterior_from_hessian(out, post->model, post->terms, G.p, post->sigma);
+}

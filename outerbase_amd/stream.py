@@ -239,6 +239,22 @@ class NewtonAccumulator:
         return MultiFit(self.om, self._t, theta.cpu().numpy().T.copy(), meansd.cpu().numpy(), diagH.cpu().numpy(),
                         float(sigma), float(rho))
 
+    def posterior(self, sigma=None, rho=DEFAULT_RHO, minus=None):
+        """The posterior covariance of the coefficients given the rows in the accumulator (without those of
+        minus): a design.Posterior on the Hessian that fit(sigma, rho, minus) factors, formed on the device
+        (obhip_normal_acc_posterior_dev).  It carries the responses' meansd (q x 3) of the same rows.
+        sigma=None: log(0.01)."""
+        import torch
+        from .design import Posterior
+        if sigma is None:
+            sigma = math.log(0.01)
+        _, _, meansd = self._solve_dev(float(sigma), float(rho), minus)     # checks minus, sets the stream
+        h = C.c_void_p()
+        call("obhip_normal_acc_posterior_dev", self._h, None if minus is None else minus._h, float(sigma), float(rho),
+             C.byref(h))
+        torch.cuda.synchronize()
+        return Posterior(self.om, self._t, h, meansd.cpu().numpy().copy())
+
 
 def _check_grad_x(om, x, dims, weights):
     x = np.asarray(x, dtype=np.float64)
