@@ -962,6 +962,38 @@ int obhip_design_select(const obhip_posterior *post, const double *xcand, uint64
                         uint64_t k, int replace, int64_t *index, double *score, double *var,
                         double *trace, uint64_t *n_picked);
 
+/* ---- posterior draws (no reference counterpart) -------------------------------------------
+ * The posterior of the coefficients of one response is N(theta, inv(H)), so with z_s ~ N(0, I_p)
+ * the draw Theta[:, s] = theta + L^-T z_s has exactly that law; its sample path at row i is
+ * b_i^T Theta[:, s].  The library contains no random number generator: the caller supplies the
+ * normals d_z, column-major p x S with leading dimension ldz >= p.  d_theta (p) is the posterior
+ * mean of one response; everything is in standardised units.  The rules of the posterior block
+ * hold: every argument check runs before the first launch, a refused call changes nothing.  No
+ * atomics anywhere and one fixed order of summation: two calls give the same bits.
+ *
+ * draw      d_Theta (p x S, leading dimension p): Theta_ks = theta_k + sum_{j >= k} X_kj z_js from the
+ *           handle's resident X = L^-T, j ascending, theta added last.
+ * sample    d_path (n x S, leading dimension n) = B(d_x) Theta: the multi-response predictor's
+ *           batched pass on the drawn coefficients (its bits); n = 0: no-op.
+ * extremum  per draw s the row of d_xcand (column-major m x d) with the smallest path value
+ *           (maximize != 0: the largest) and that value, the m x S paths never stored.  The lowest
+ *           index wins among equal values (-0.0 and 0.0 are equal).  A candidate with d_skip[i] != 0
+ *           (d_skip may be NULL), a coordinate that is not finite or a value that is not finite is
+ *           never chosen; a draw without an eligible candidate gets index -1 and value NaN, which
+ *           is no error.  The values carry the bits sample gives the same rows. */
+int obhip_posterior_draw_dev(const obhip_posterior *post, const double *d_theta,
+                             const double *d_z, uint64_t ldz, uint64_t S,
+                             double *d_Theta /* p x S, ld = p */);
+int obhip_posterior_sample_dev(const obhip_posterior *post, const double *d_theta,
+                               const double *d_z, uint64_t ldz, uint64_t S,
+                               const double *d_x, uint64_t n,
+                               double *d_path /* n x S, ld = n */);
+int obhip_posterior_extremum_dev(const obhip_posterior *post, const double *d_theta,
+                                 const double *d_z, uint64_t ldz, uint64_t S,
+                                 const double *d_xcand, uint64_t m,
+                                 const uint8_t *d_skip /* m or NULL */, int maximize,
+                                 int64_t *d_index /* S */, double *d_value /* S */);
+
 /* ---- the model layer: lpdf, loglik_*, logpr_gauss, lpdfvec, predictor ------------------
  * Module rows src/interfaceR.cpp:696-762; classes src/fit.h:23-361; arithmetic
  * src/fit.cpp:37-612 and src/lpdfs/{loglik_std,loglik_gauss,loglik_gda,logpr_gauss}.cpp.

@@ -604,6 +604,32 @@ int launch_design_pick(const DesignStep &s, uint64_t nparts, uint64_t d, uint64_
 // then S -= s s^T / gamma and T -= (s h^T + h s^T) / gamma - s s^T tau / gamma^2
 int launch_design_pspace(int crit, uint64_t p, uint64_t pp, const double *d_b, double *d_S, double *d_T, double *d_sv,
                          double *d_hv, double *d_sh, double *d_scal, double *d_trace, uint64_t step);
+// sample.cpp / kernels_sample.hip: draws from N(theta, inv(H)) and the per-draw extremum of their sample
+// paths over a candidate set (include/obhip.h, "posterior draws")
+constexpr uint64_t kDrawChunk = 64;  // draws of one launch of k_draw outside the fused pass (which takes up to 128)
+// Theta_ks = theta_k + sum_{j >= k} X_kj z_js for the qc <= 128 columns of d_z, j ascending, theta added last:
+// into the term-major [p][qw] block d_tht (columns qc .. qw - 1 zero; may be null) and the column-major
+// p x qc d_Theta (leading dimension p; may be null)
+int launch_draw(const PostFactor &f, const double *d_theta, const double *d_z, uint64_t ldz, int qc, uint64_t qw,
+                double *d_tht, double *d_Theta);
+// d_elig[i] = 1: row i of d_x (column-major n x d) is not skipped and all its coordinates are finite
+int launch_sample_elig(const double *d_x, uint64_t n, uint64_t d, const uint8_t *d_skip, uint8_t *d_elig);
+bool sample_ext_supports(const obhip_terms &t);
+int sample_ext_nqb_max(const obhip_terms &t);  // widest pass (16 nqb draws, nqb <= 8) whose LDS fits
+// One pass of the fused kernel over the n candidates for the 16 nqb columns of the term-major block d_tht:
+// per workgroup (64 rows) and column the best key = sgn * value (sgn = +1: minimum, -1: maximum) among the
+// eligible rows with a finite value and the lowest row that has it, into part_key / part_idx [block][16 nqb];
+// no such row: +inf and INT64_MAX
+int launch_sample_ext(const obhip_model &m, obhip_terms &t, const double *d_tht, int nqb, const double *d_x,
+                      uint64_t n, const uint8_t *d_elig, double sgn, double *part_key, int64_t *part_idx);
+constexpr uint64_t kColextRows = 256;  // rows per workgroup of k_sample_colext
+// the same partials from nr rows of stored paths (d_path: nr x qc, leading dimension ld; global rows row0 ..),
+// 256 rows per workgroup, into part_*[(row0 / 256 + block) * stride + column]
+int launch_sample_colext(const double *d_path, uint64_t ld, uint64_t nr, uint64_t row0, int qc, const uint8_t *d_elig,
+                         double sgn, uint64_t stride, double *part_key, int64_t *part_idx);
+// per column the partials in ascending block order -> d_index[s] (-1: no eligible row), d_value[s] (NaN)
+int launch_sample_pick(const double *part_key, const int64_t *part_idx, uint64_t nparts, uint64_t stride, int qc,
+                       double sgn, int64_t *d_index, double *d_value);
 
 // kernels_grad.hip
 int ensure_gradbasis(obhip_basis &b);

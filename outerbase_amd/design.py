@@ -15,6 +15,12 @@ accumulator carries meansd (q x 3: centre, scale, rows), so var * meansd[j, 1] *
 variance in raw units; the selection does not depend on that scale, which multiplies every candidate's
 score alike.
 
+Draws.  The posterior of one response's coefficients is N(theta, inv(H)): draw gives coefficient samples
+theta + L^-T z, sample their joint sample paths over rows x, thompson the optimum of every draw over a
+candidate set in one fused pass per block of draws (csrc/kernels_sample.hip; the m x S paths are never
+stored) -- Thompson sampling, the simplest batch acquisition that uses the response.  torch supplies the
+normals (or the caller does, z=), the library the arithmetic.
+
 torch holds the device memory; all arithmetic is in libobhip.
 """
 import ctypes as C
@@ -51,6 +57,16 @@ class DesignResult:
     every candidate after all picks; trace (n_picked + 1): maxvar: the cumulative gain of log det H,
     imse: the integrated variance tr(M S_t), either from t = 0.  Fewer than k picks: no eligible
     candidate was left."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+class ThompsonResult:
+    """index (S): per draw the candidate row at which its sample path is smallest (maximize: largest), -1
+    when no candidate was eligible; value (S): the path there (NaN); picks: the distinct indices in order of
+    first appearance, -1 left out; counts: per pick the number of draws that chose it -- counts / S is the
+    empirical probability that the candidate is the optimum."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -191,3 +207,117 @@ class Posterior:
         return DesignResult(index=index.cpu().numpy()[:n].copy(), score=score.cpu().numpy()[:n].copy(),
                             var=var.cpu().numpy(), trace=trace.cpu().numpy()[:n + 1].copy(), criterion=criterion,
                             n_picked=n, k=k)
+
+    # -- draws -------------------------------------------------------------------------------
+    def _draw_args(self, theta, n_draws, seed, z):
+        """the host side of the draws' arguments, checked: (theta, z^T or None, S, seed)"""
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.shape != (self.p,):
+            raise ValueError("theta must be the p standardised coefficients of one response")
+        if (z is None) == (n_draws is None):
+            raise ValueError("give exactly one of z (p x S) and n_draws")
+        if z is not None:
+            z = np.asarray(z, dtype=np.float64)
+            if z.ndim != 2 or z.shape[0] != self.p or z.shape[1] < 1:
+                raise ValueError("z must be p x S with S >= 1")
+            return theta, np.ascontiguousarray(z.T), z.shape[1], None       # row s = column s of z
+        if int(n_draws) < 1:
+            raise ValueError("n_draws must be >= 1")
+        if seed is None:
+            raise ValueError("n_draws needs a seed")
+        return theta, None, int(n_draws), int(seed)
+
+    def _draw_dev(self, args, dev):
+        """(d_theta, d_Z: column-major p x S with leading dimension p, S)"""
+        import torch
+        theta, zt, S, seed = args
+        if zt is not None:
+            dz = torch.from_numpy(zt).to(dev)
+        else:
+            gen = torch.Generator(dev).manual_seed(seed)
+            dz = torch.randn(self.p, S, dtype=torch.float64, device=dev, generator=gen).t().contiguous()
+        return torch.from_numpy(theta).to(dev), dz, S
+
+    def _scale(self, response):
+        """(centre, scale) the sample paths of `response` are de-standardised with, or None"""
+        if response is None or self.meansd is None:
+            return None
+        cen, sca = float(self.meansd[int(response), 0]), float(self.meansd[int(response), 1])
+        if not sca > 0:
+            raise ValueError("response %d has scale %g: nothing to de-standardise with" % (int(response), sca))
+        return cen, sca
+
+    def draw(self, theta, n_draws=None, seed=None, z=None):
+        """Coefficient draws theta + L^-T z_s from N(theta, inv(H)) -> p x S, standardised units.  theta: the p
+        standardised coefficients of one response (MultiFit.coeff[:, j]).  Exactly one of z (p x S normals)
+        and n_draws: with n_draws, Z = torch.randn(p, S, float64, on the device) from
+        torch.Generator(device).manual_seed(seed).  A seed reproduces on the same torch build only; z= is the
+        portable form."""
+        import torch
+        self._need()
+        args = self._draw_args(theta, n_draws, seed, z)
+        dev = _stream()
+        dth, dz, S = self._draw_dev(args, dev)
+        out = torch.empty((S, self.p), dtype=torch.float64, device=dev)
+        call("obhip_posterior_draw_dev", self._h, dth.data_ptr(), dz.data_ptr(), self.p, S, out.data_ptr())
+        torch.cuda.synchronize()
+        return out.cpu().numpy().T.copy()
+
+    def sample(self, x, theta, n_draws=None, seed=None, z=None, response=None):
+        """Joint sample paths B(x) (theta + L^-T z_s) at the rows x (n x d) -> n x S.  Arguments as draw (a seed
+        reproduces on the same torch build only; z= is the portable form).  response=j on a posterior that
+        carries meansd: the paths are de-standardised with row j (centre + scale * path); otherwise they stay in
+        standardised units."""
+        import torch
+        self._need()
+        x = _rows(self.om, x, "x")
+        sc = self._scale(response)
+        args = self._draw_args(theta, n_draws, seed, z)
+        n = x.shape[0]
+        if n == 0:
+            return np.zeros((0, args[2]))
+        dev = _stream()
+        dth, dz, S = self._draw_dev(args, dev)
+        dx = _dev_cols(x, dev)
+        out = torch.empty((S, n), dtype=torch.float64, device=dev)
+        call("obhip_posterior_sample_dev", self._h, dth.data_ptr(), dz.data_ptr(), self.p, S, dx.data_ptr(), n,
+             out.data_ptr())
+        torch.cuda.synchronize()
+        path = out.cpu().numpy().T.copy()
+        return path if sc is None else sc[0] + sc[1] * path
+
+    def thompson(self, xcand, theta, n_draws=None, seed=None, z=None, maximize=False, skip=None, response=None):
+        """Per draw the candidate row of xcand (m x d) at which its sample path is smallest (maximize=True:
+        largest) and the path there -> ThompsonResult.  Arguments as draw (a seed reproduces on the same torch
+        build only; z= is the portable form).  skip (m, nonzero = leave out): rows that are never chosen, like
+        rows with a coordinate that is not finite.  The lowest index wins among equal values.  response=j on a
+        posterior that carries meansd de-standardises value with row j; its scale is positive, so the optimum
+        does not move."""
+        import torch
+        self._need()
+        xcand = _rows(self.om, xcand, "xcand")
+        m = xcand.shape[0]
+        if m == 0:
+            raise ValueError("thompson needs candidates")
+        if skip is not None:
+            skip = np.ascontiguousarray(np.asarray(skip) != 0, dtype=np.uint8)
+            if skip.shape != (m,):
+                raise ValueError("skip must have one entry per candidate")
+        sc = self._scale(response)
+        args = self._draw_args(theta, n_draws, seed, z)
+        dev = _stream()
+        dth, dz, S = self._draw_dev(args, dev)
+        dx = _dev_cols(xcand, dev)
+        dk = torch.from_numpy(skip).to(dev) if skip is not None else None
+        index = torch.full((S,), -1, dtype=torch.int64, device=dev)
+        value = torch.full((S,), float("nan"), dtype=torch.float64, device=dev)
+        call("obhip_posterior_extremum_dev", self._h, dth.data_ptr(), dz.data_ptr(), self.p, S, dx.data_ptr(), m,
+             None if dk is None else dk.data_ptr(), int(bool(maximize)), index.data_ptr(), value.data_ptr())
+        torch.cuda.synchronize()
+        index, value = index.cpu().numpy(), value.cpu().numpy()
+        if sc is not None:
+            value = sc[0] + sc[1] * value
+        picks, first, counts = np.unique(index[index >= 0], return_index=True, return_counts=True)
+        order = np.argsort(first, kind="stable")
+        return ThompsonResult(index=index, value=value, picks=picks[order], counts=counts[order],
+                              maximize=bool(maximize), n_draws=S)
