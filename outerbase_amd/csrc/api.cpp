@@ -716,10 +716,8 @@ int fit_cg_dev_impl(const obhip_basis *b, const obhip_terms *tc, const obhip_mod
     // enqueued before the host looks -- every kernel of an iteration returns at once when an earlier
     // one ended the loop (k_cg_iter's guard, the stop flags of the Hessian product), the device
     // counts the steps made (S_ITERS).  Same iterates, same iteration count, a fraction of the
-    // host round trips.  OBHIP_CG_BATCH sets the batch (1 = off); default 8 below 2^22 rows x terms.
-    const char *be = getenv("OBHIP_CG_BATCH");
-    const uint64_t batch = be ? (uint64_t)std::max(1, atoi(be))
-                              : ((double)b->n_pad * (double)t.p_pad <= 4194304.0 ? 8 : 1);
+    // host round trips.  The batch is 8 up to 2^22 rows x terms, otherwise 1 (= off).
+    const uint64_t batch = (double)b->n_pad * (double)t.p_pad <= 4194304.0 ? 8 : 1;
     const bool batched = batch > 1 && can_spec && !many;
     // one iteration with the host in the loop; returns kStop when the loop ends (k then counts the
     // iterations made), 0 to go on, an error code otherwise

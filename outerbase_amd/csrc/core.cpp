@@ -43,7 +43,6 @@ int require_device() {
 }
 
 hipStream_t cur_stream() { return g_stream; }
-void set_cur_stream(hipStream_t s) { g_stream = s; }
 
 int d2h(void *dst, const void *src, size_t bytes) {
   OB_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, cur_stream()));

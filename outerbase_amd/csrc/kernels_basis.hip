@@ -49,7 +49,7 @@ __device__ __forceinline__ int bb_tab_size(const DimDesc &D) {
 // times (20 x 16 KB per block at d = 20) and put more waves on a CU.
 // (4 / 8 / 16 tiles per block at the headline shape: 0.476 / 0.426 / 0.655 ms -- sixteen spill)
 template <int NW>
-__global__ void __launch_bounds__(NW * 64, NW == 4 ? 5 : 6)
+__global__ void __launch_bounds__(NW * 64, 6)
 k_build_basis(const DimDesc *__restrict__ dims, const double *__restrict__ ka,
               const double *__restrict__ kb, const double *__restrict__ kc,
               const double *__restrict__ rot, const double *__restrict__ tab,
@@ -152,16 +152,10 @@ k_getbase(DimDesc D, const double *__restrict__ ka, const double *__restrict__ k
 int launch_build_basis(obhip_basis &b) {
   ProfScope ps("build_basis");
   const uint64_t tiles = b.n_pad / kTileRows;
-  static const int nw = getenv("OBHIP_BB_WAVES") ? atoi(getenv("OBHIP_BB_WAVES")) : 8;
-#define OB_BB(NW_)                                                                                             \
-  hipLaunchKernelGGL(k_build_basis<NW_>, dim3((unsigned)((tiles + NW_ - 1) / NW_)), dim3(NW_ * 64), 0,        \
-                     cur_stream(), b.md.dims.p, b.md.ka.p, b.md.kb.p, b.md.kc.p, b.md.rot.p, b.md.tab.p, b.x.p, \
-                     b.n, (int)b.d, b.md.Mc, tiles, b.bm.p, b.scale.p)
-  if (nw == 4)
-    OB_BB(4);
-  else
-    OB_BB(8);
-#undef OB_BB
+  constexpr int kNw = 8;  // 64-row tiles per workgroup
+  hipLaunchKernelGGL(k_build_basis<kNw>, dim3((unsigned)((tiles + kNw - 1) / kNw)), dim3(kNw * 64), 0, cur_stream(),
+                     b.md.dims.p, b.md.ka.p, b.md.kb.p, b.md.kc.p, b.md.rot.p, b.md.tab.p, b.x.p, b.n, (int)b.d,
+                     b.md.Mc, tiles, b.bm.p, b.scale.p);
   OB_HIP(hipGetLastError());
   return 0;
 }

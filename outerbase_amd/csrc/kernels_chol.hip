@@ -6,9 +6,10 @@
 // H is p x p, row-major, full symmetric storage on entry; on exit its lower
 // triangle holds L (H = L L^T), the strict upper triangle is scratch.
 //
-// Several 64-column panels per trailing update (two from p = 4096, four from p = 8192): panel j, a
+// Several 64-column panels per trailing update (chol_panels_at: one below p = 3072; from there by
+// the rows left when a pass starts -- eight from 8192, four from 4096, else two): panel j, a
 // strip update of the next 64 columns only with the panels of the pass so far, panel j + 1, ...,
-// then ONE pass over the trailing matrix with all panels of the pass (k = 128 or 256, staged
+// then ONE pass over the trailing matrix with all panels of the pass (k = 128 to 512, staged
 // through LDS in parts).  The trailing update reads and writes the whole trailing triangle; every
 // doubling of the panels per pass halves that traffic.
 //   k_chol_panel2: every workgroup re-factorises the 64 x 64 diagonal block itself

@@ -1190,23 +1190,19 @@ int launch_tmm_ge0(obhip_basis &b, obhip_terms &t, bool squared, const double *d
                                       // and no synchronisation at the end of this function)
   const uint64_t ntiles = b.n_pad / kTileRows;
   // a tile of more than half the LDS leaves one block per CU: 16 waves in it instead of 8
-  // (OBHIP_GE0_WAVES=8|16 forces either: A/B runs)
   // ... and where TWO tiles fit the LDS, 16 waves with the next tile prefetched into the second
   // buffer (k_tmm_ge0_db; nw = 32 stands for it below)
-  static const int force_nw = getenv("OBHIP_GE0_WAVES") ? atoi(getenv("OBHIP_GE0_WAVES")) : 0;
   // Hyper-parameters beyond a multiple of 16 (d = 20 mat25: 4 of 20) in groups of four on the
-  // 4 x 4 x 4 matrix instruction instead of a mostly empty 16-block.  OBHIP_GE0_FOURS: 0 = never,
-  // 1 = 1 to 8 left over take a pass of their own (NHB = 0), 2 (default) = behind a 16-block they
-  // ride along with it (the products formed once; 22-39 registers of the W2 = 2 kernel spilled
-  // outside the read pipeline).  d = 20 mat25 at the headline terms, 20 hyper-parameters: dense part
-  // 5.47 / 4.52 / 3.50 ms, obfit evaluation 30.8 / 29.8 / 28.5 ms (tools/r05_fours_ab.sh).
-  static const int fours = getenv("OBHIP_GE0_FOURS") ? atoi(getenv("OBHIP_GE0_FOURS")) : 2;
+  // 4 x 4 x 4 matrix instruction instead of a mostly empty 16-block: 1 to 8 left over take a pass of
+  // their own (NHB = 0), behind a 16-block they ride along with it (the products formed once; 22-39
+  // registers of the W2 = 2 kernel spilled outside the read pipeline).  d = 20 mat25 at the headline
+  // terms, 20 hyper-parameters, never / a pass of their own / riding along: dense part
+  // 5.47 / 4.52 / 3.50 ms, obfit evaluation 30.8 / 29.8 / 28.5 ms (profiles/r05_fours_ab.txt).
   const size_t tile_lds = ge0_tile_bytes(t, 16);
   const bool two_tiles = 2 * tile_lds <= kLdsTile;
   bool one_per_cu = tile_lds > 80 * 1024;
   int nw = one_per_cu ? 16 : 8;
   if (two_tiles) nw = 32;
-  if (force_nw == 8 || force_nw == 16 || (force_nw == 32 && two_tiles)) nw = force_nw;
   if (nw == 32) one_per_cu = true;
   const uint64_t tpb = (uint64_t)(nw == 32 ? 16 : nw) * 64;
   const uint64_t pblocks = (t.p_pad + tpb - 1) / tpb;
@@ -1222,8 +1218,8 @@ int launch_tmm_ge0(obhip_basis &b, obhip_terms &t, bool squared, const double *d
     const int rem = nhyp - h0;
     // n4 > 0: 16 + 4 n4 hyper-parameters in this pass; n4 < 0: 4 |n4| only
     int n4 = 0;
-    if (fours == 2 && nw == 32 && rem > 16 && rem <= 24) n4 = (rem - 16 + 3) / 4;
-    if (fours >= 1 && nw == 32 && rem <= 8) n4 = -((rem + 3) / 4);
+    if (nw == 32 && rem > 16 && rem <= 24) n4 = (rem - 16 + 3) / 4;
+    if (nw == 32 && rem <= 8) n4 = -((rem + 3) / 4);
     if (n4 > 0 && 2 * ge0_tile_bytes(t, 16 + 4 * n4) > kLdsTile) n4 = 0;
     const int nh = n4 > 0 ? rem : (n4 < 0 ? rem : std::min(16, rem));
     const int hs = n4 > 0 ? 16 + 4 * n4 : (n4 < 0 ? -4 * n4 : 16);

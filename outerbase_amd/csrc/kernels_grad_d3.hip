@@ -221,13 +221,13 @@ int launch_tmm_d3(obhip_basis &b, const obhip_terms::GeD3 &g, int mode, const do
   const obhip_terms &v = *g.v;
   const uint64_t ntiles = b.n_pad / kTileRows;
   // 8 waves x 4 view-terms per lane, the tile loaded between the barriers (the other block of the CU
-  // computes meanwhile; with prefetch registers this shape spills 77).  OBHIP_D3_VARIANT=0 (A/B runs):
-  // 2 per lane, the tile prefetched into registers -- 1.21 against 1.11 ms per launch at d = 8, 1.96
-  // against 1.91 at C3 (half the row-weight v_readlanes per view-term).  Also measured: 2 per lane
-  // without prefetch 1.27, 16 waves x 1 per lane 1.42 (before the weights went into the staged columns).
-  static const int variant = getenv("OBHIP_D3_VARIANT") ? atoi(getenv("OBHIP_D3_VARIANT")) : 1;
+  // computes meanwhile; with prefetch registers this shape spills 77); up to 1024 view-terms 2 per lane,
+  // the tile prefetched into registers.  Measured with 2 per lane at every size: 1.21 against 1.11 ms
+  // per launch at d = 8, 1.96 against 1.91 at C3 (half the row-weight v_readlanes per view-term).  Also
+  // measured: 2 per lane without prefetch 1.27, 16 waves x 1 per lane 1.42 (before the weights went into
+  // the staged columns).
   constexpr int nw = 8;
-  const int nu = variant == 1 && v.p_pad > 1024 ? 4 : 2;
+  const int nu = v.p_pad > 1024 ? 4 : 2;
   const uint64_t tpb = (uint64_t)nw * nu * 64;
   const uint64_t pblocks = (v.p_pad + tpb - 1) / tpb;
   // two resident blocks per CU, one round

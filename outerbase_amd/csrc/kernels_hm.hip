@@ -45,8 +45,8 @@ constexpr int kHm2RedSlots = 64;  // [4 rows][16 waves] partial sums of one sub-
 // sub-chunk accumulates zeros (prod = 0, wprev = 0); the kernel's epilogue flushes the last one.
 // Step 1's sums s[r] += a_u prod[u][r] ride in the pipeline as well when the registers allow
 // (SIN: a_u and s[r] in 16 VGPRs); otherwise the coefficients live in LDS and the sums are taken
-// after the pipeline has drained (the update() form, which also carries y, yhat and the residual
-// sum, and 6-factor terms at 4 per lane).
+// after the pipeline has drained (the update() form at 4 terms per lane, which also carries y, yhat
+// and the residual sum).
 template <int W, int NU, bool SIN>
 struct Hm2Ctx {
   uint32_t ad[NU][W];
@@ -324,46 +324,33 @@ int run_hm2(const obhip_basis &b, obhip_terms &t, const double *d_a, const doubl
 }  // namespace
 
 // two tile buffers, the row weights, the wave partials and -- for the instantiations that keep
-// it in LDS (launch_hm2 below: 4 terms per lane in the update() form or with 6-factor terms) -- the
+// it in LDS (launch_hm2 below: 4 terms per lane in the update() form) -- the
 // coefficient vector, one slot per lane and unit
-size_t hm2_lds_bytes(const obhip_terms &t, bool ro, int variant) {
-  const int w2 = (int)(t.W / 2);
+size_t hm2_lds_bytes(const obhip_terms &t, bool ro) {
   const int nu = t.p_pad <= 1024 ? 1 : (t.p_pad <= 2048 ? 2 : 4);
-  size_t slots = 0;
-  if (variant == 2 || variant == 3)
-    slots = ro ? 4608 : 0;  // (12 waves x 6 units, 8 x 8: the experiments at 4-factor terms)
-  else if ((w2 >= 2 && variant == 5) || (w2 == 3 && variant == 7) || (nu == 4 && ro))
-    slots = 4096;  // the instantiations that keep the coefficients in LDS (launch_hm2): variants 5
-                   // and 7 are 16 waves x 4 units whatever p_pad is (round-4 advice), the update()
-                   // form at 4 units per lane
+  const size_t slots = nu == 4 && ro ? 4096 : 0;  // the update() form at 4 units per lane
   return ((size_t)2 * t.Mu * kTlPitch + 2 * 128 + 2 * kHm2RedSlots + slots) * sizeof(double);
 }
 
 // the terms this kernel takes in the form asked for (launch_hessmult_fused asks before it falls
 // back to k_hm_tl): up to 147 used columns for the Hessian product at 4-factor terms, 118 where the
 // coefficients live in LDS too
-bool hm2_supports(const obhip_terms &t, bool ro, int variant) {
+bool hm2_supports(const obhip_terms &t, bool ro) {
   const int w2 = (int)(t.W / 2);
-  return w2 >= 1 && w2 <= 3 && t.p_pad <= 4096 && hm2_lds_bytes(t, ro, variant) <= kLdsTile;
+  return w2 >= 1 && w2 <= 3 && t.p_pad <= 4096 && hm2_lds_bytes(t, ro) <= kLdsTile;
 }
 
-// variant: 0 = automatic; experiments at 4-factor terms (OBHIP_HM2_VARIANT): 2 = 12 waves x 6
-// terms per lane, 3 = 8 x 8, 5 = 16 x 4 with the coefficients in LDS and 12 reads in flight,
-// 6 = 16 x 4, sums in the pipeline, 12 reads in flight (2 spilled registers)
+// 16 waves; 1, 2 or 4 terms per lane by p_pad
 int launch_hm2(const obhip_basis &b, obhip_terms &t, const double *d_a, const double *d_y, double ca,
                double cb, double *part, double *d_yhat, double *sspart, unsigned nsplit, uint64_t ntiles,
-               uint64_t tps, int variant, const double *stop0, const double *stop1) {
-  const size_t lds = hm2_lds_bytes(t, d_y != nullptr, variant);
+               uint64_t tps, const double *stop0, const double *stop1) {
+  const size_t lds = hm2_lds_bytes(t, d_y != nullptr);
   const int w2 = (int)(t.W / 2);
   const uint64_t pp = t.p_pad;
 #define OB_HM2(W2_, NU_, WAVES_, INFL_, SIN_) \
   return run_hm2<W2_, NU_, WAVES_, INFL_, SIN_>(b, t, d_a, d_y, ca, cb, part, d_yhat, sspart, nsplit, ntiles, tps, lds, \
                                                 stop0, stop1)
   if (w2 == 2) {
-    if (variant == 2 && pp <= 12 * 6 * 64) OB_HM2(2, 6, 12, 12, true);
-    if (variant == 3 && pp <= 8 * 8 * 64) OB_HM2(2, 8, 8, 12, true);
-    if (variant == 5) OB_HM2(2, 4, 16, 12, false);
-    if (variant == 6) OB_HM2(2, 4, 16, 12, true);
     if (pp <= 16 * 1 * 64) OB_HM2(2, 1, 16, 12, true);
     if (pp <= 16 * 2 * 64) OB_HM2(2, 2, 16, 12, true);
     OB_HM2(2, 4, 16, 8, true);
@@ -371,8 +358,6 @@ int launch_hm2(const obhip_basis &b, obhip_terms &t, const double *d_a, const do
   if (w2 == 3) {  // terms of 5 and 6 factors (obfit's eight-dimensional examples)
     // (n = 1e6, p = 4096, d = 8, tools/hm_bench.py: sums outside the pipeline, 8 reads in flight 1.797 ms,
     // 12 in flight 1.780, sums inside -- 128 VGPRs, two of them spilled outside the loops -- 1.723)
-    if (variant == 5) OB_HM2(3, 4, 16, 12, false);
-    if (variant == 7) OB_HM2(3, 4, 16, 8, false);
     if (pp <= 16 * 1 * 64) OB_HM2(3, 1, 16, 12, true);
     if (pp <= 16 * 2 * 64) OB_HM2(3, 2, 16, 12, true);
     OB_HM2(3, 4, 16, 8, true);

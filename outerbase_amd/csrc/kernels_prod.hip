@@ -1270,8 +1270,7 @@ int launch_tmm(const obhip_basis &b, obhip_terms &t, const double *d_a, double *
         OB_TRY(launch_star_tmm(b, t, d_a, squared, part, nullptr, nullptr, (unsigned)rs.nsplit, ntiles, rs.tps));
         break;
       case kTl: {
-        static const bool nopf = getenv("OBHIP_TL_NOPREFETCH") != nullptr;
-        const bool pf = !nopf && t.Mu <= (uint64_t)kTlWaves * kTlPre;
+        const bool pf = t.Mu <= (uint64_t)kTlWaves * kTlPre;
         OB_TRY(run_tmm_tl(b, t, squared, pf, npair, d_a, part, nullptr, nullptr, rs, ntiles));
         break;
       }
@@ -1287,8 +1286,7 @@ namespace {
 // k_hm_tl: one block of 8 waves x nu groups x 64 terms; kNotFused where no instantiation takes (W2, nu)
 int run_hm_tl(const obhip_basis &b, obhip_terms &t, int nu, const double *d_a, const double *d_y, double ca,
               double cb, double *part, double *d_yhat, double *sspart, const RowSplit &rs, uint64_t ntiles) {
-  static const bool nopf = getenv("OBHIP_HM_NOPREFETCH") != nullptr;
-  const bool pf = !nopf && t.Mu <= (uint64_t)kTlWaves * kTlPre;
+  const bool pf = t.Mu <= (uint64_t)kTlWaves * kTlPre;
   return pick_or<1, 2, 3, 4>((int)(t.W / 2), kNotFused, [&](auto W2) {
     return pick_or<1, 2, 4, 8>(nu, kNotFused, [&](auto NU) {
       if constexpr (NU() > tl_max_units(W2())) return (int)kNotFused;
@@ -1306,12 +1304,7 @@ int run_hm_tl(const obhip_basis &b, obhip_terms &t, int nu, const double *d_a, c
 
 bool hm2_wanted() {
   static const bool off = getenv("OBHIP_HESSMULT_FUSED") && atoi(getenv("OBHIP_HESSMULT_FUSED")) == 0;
-  static const bool v1 = getenv("OBHIP_HM_V1") && atoi(getenv("OBHIP_HM_V1")) != 0;
-  return !off && !v1;
-}
-int hm2_variant() {
-  static const int variant = getenv("OBHIP_HM2_VARIANT") ? atoi(getenv("OBHIP_HM2_VARIANT")) : 0;
-  return variant;
+  return !off;
 }
 }  // namespace
 
@@ -1320,7 +1313,7 @@ int hm2_variant() {
 bool hessmult_fused_skippable(const obhip_basis &b, obhip_terms &t) {
   if (t.prepare(b.md.cap, b.md.dims_h) != 0) return false;
   if (!hm2_wanted() || beyond_lds(t)) return false;
-  return (hm3_wanted() && hm2_variant() == 0 && star_supports(t, true)) || hm2_supports(t, false, hm2_variant());
+  return (hm3_wanted() && star_supports(t, true)) || hm2_supports(t, false);
 }
 
 // d_out (p) = B^T (c_a B a + c_b y) in one pass over the basis (k_hm_tl); d_yhat (n, may be
@@ -1332,12 +1325,10 @@ int launch_hessmult_fused(const obhip_basis &b, obhip_terms &t, const double *d_
                           const double *d_stop0, const double *d_stop1, const HmThen *then) {
   OB_TRY(t.prepare(b.md.cap, b.md.dims_h));
   static const bool off = getenv("OBHIP_HESSMULT_FUSED") && atoi(getenv("OBHIP_HESSMULT_FUSED")) == 0;
-  // OBHIP_HM_V1=1: the round-3 kernel (A/B runs); OBHIP_HM2_VARIANT: block shapes of k_hm2
-  const int variant = hm2_variant();
   const int w2 = (int)(t.W / 2);
   // OBHIP_HM3=0: k_hm2 instead of the two-phase kernel on shared sub-products (A/B)
-  const bool use3 = hm2_wanted() && hm3_wanted() && variant == 0 && !beyond_lds(t) && star_supports(t, true);
-  const bool use2 = use3 || (hm2_wanted() && !beyond_lds(t) && hm2_supports(t, d_y != nullptr, variant));
+  const bool use3 = hm2_wanted() && hm3_wanted() && !beyond_lds(t) && star_supports(t, true);
+  const bool use2 = use3 || (hm2_wanted() && !beyond_lds(t) && hm2_supports(t, d_y != nullptr));
   if (d_stop0 && !use2) return fail(OBHIP_ERR_STATE, "hessmult: stop flags need the k_hm2 / k_hm3 path");
   const int numax = tl_max_units(w2);
   if (!use2 && (off || beyond_lds(t) || w2 < 1 || w2 > kMaxW2 || t.p_pad > (uint64_t)kTlWaves * numax * 64 ||
@@ -1358,8 +1349,8 @@ int launch_hessmult_fused(const obhip_basis &b, obhip_terms &t, const double *d_
       OB_TRY(launch_star_hess(b, t, d_a, d_y, ca, cb, part, d_yhat, sspart, (unsigned)nsplit, ntiles, tps,
                               d_stop0, d_stop1));
     else if (use2)
-      OB_TRY(launch_hm2(b, t, d_a, d_y, ca, cb, part, d_yhat, sspart, (unsigned)nsplit, ntiles, tps, variant,
-                        d_stop0, d_stop1));
+      OB_TRY(launch_hm2(b, t, d_a, d_y, ca, cb, part, d_yhat, sspart, (unsigned)nsplit, ntiles, tps, d_stop0,
+                        d_stop1));
     else
       OB_TRY(run_hm_tl(b, t, nu, d_a, d_y, ca, cb, part, d_yhat, sspart, rs, ntiles));
   }

@@ -790,8 +790,7 @@ int launch_star_predict(const obhip_model &m, obhip_terms &t, const double *d_th
   const bool wv = d_coeffvar != nullptr && d_var != nullptr;
   // (with the variance the kernel spills more for the two registers than the early request gains:
   // 1.83 -> 1.88 ms; without, 1.35 -> 1.24 ms on the same box)
-  static const bool pfx_on = !(getenv("OBHIP_PREDICT_PFX") && atoi(getenv("OBHIP_PREDICT_PFX")) == 0);
-  const bool pfx = pfx_on && !wv;
+  const bool pfx = !wv;
   return pick<1, 2, 3>((int)(t.W / 2), [&](auto W2) {
     return pick_bool(wv, [&](auto VAR) {
       // reads in flight (W2 = 2 with the variance: ring depth 8 and / or early inputs, 1.79-1.86 ms either way)

@@ -325,7 +325,6 @@ struct Loglik : obhip_lpdf {
   DevBuf<double> xch;  // staging of the host-side results that are summed
   DevBuf<double> y, yhat, r, tmp, ones, dcoeff, dpv;
   DevBuf<double> red;         // scratch of the two-stage sums
-  DevBuf<double> yhatge_ab;   // n x nhyp, only with OBHIP_GRADHYP_MATRIX (A/B aid)
   // sum_i d(B^2)_ik/dhyp_h (p x nhyp, this rank's rows, unscaled) when backward() formed it in the
   // same sweep as gradhyp (grad_dual_dev); diaghessgradhyp() of the one-noise-level likelihoods
   // then only scales it.  want_dhg: set by lpdfvec around the update() that needs both.
@@ -453,22 +452,16 @@ struct Loglik : obhip_lpdf {
     OB_TRY(d2h(grad.data(), dpv.p, p * sizeof(double)));
     if (compute_gradhyp) {
       gradhyp.assign(nhyp(), 0.0);
-      static const bool matrix_form = getenv("OBHIP_GRADHYP_MATRIX") != nullptr;  // A/B aid
-      if (matrix_form) {  // rounds 1-3: the matrix, then its product with r (one more B c pass)
-        OB_TRY(grad_mm_dev(*ob, *t, false, coeff.data(), dcoeff.p, tmp.p, yhatge_ab));
-        OB_TRY(grad_wdot_dev(yhatge_ab.p, r.p, n, nhyp(), gradhyp.data()));
-      } else {
-        int fused = kNotFused;
-        if (want_dhg && dhg_ones && !dhg_valid) {
-          dhg_cache.resize(nterms * nhyp());
-          fused = grad_dual_dev(*ob, *t, coeff.data(), yhat.p, r.p, nullptr, gradhyp.data(), dhg_cache.data());
-          if (fused != kNotFused) {
-            OB_TRY(fused);
-            dhg_valid = true;
-          }
+      int fused = kNotFused;
+      if (want_dhg && dhg_ones && !dhg_valid) {
+        dhg_cache.resize(nterms * nhyp());
+        fused = grad_dual_dev(*ob, *t, coeff.data(), yhat.p, r.p, nullptr, gradhyp.data(), dhg_cache.data());
+        if (fused != kNotFused) {
+          OB_TRY(fused);
+          dhg_valid = true;
         }
-        if (fused == kNotFused) OB_TRY(grad_mm_dot_dev(*ob, *t, coeff.data(), yhat.p, r.p, gradhyp.data()));
       }
+      if (fused == kNotFused) OB_TRY(grad_mm_dot_dev(*ob, *t, coeff.data(), yhat.p, r.p, gradhyp.data()));
       OB_TRY(sum_ranks(gradhyp.data(), nhyp()));
     }
     return 0;

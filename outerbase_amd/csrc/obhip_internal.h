@@ -38,7 +38,6 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line);
 
 int require_device();
 hipStream_t cur_stream();
-void set_cur_stream(hipStream_t s);  // (internal: a second stream inside one entry point; restored before it returns)
 // model state stamps are drawn from one process-wide counter: device tables cached under
 // (model address, stamp) can then never be taken for those of another model that came to live at
 // the same address
@@ -504,10 +503,10 @@ int launch_star_predict(const obhip_model &m, obhip_terms &t, const double *d_th
                         double *d_mean, const double *d_coeffvar, double e2sigma, double *d_var);
 // kernels_hm.hip: the second-generation kernel (two tile buffers fed by LDS-direct loads, four
 // waves per SIMD) and the terms it takes
-bool hm2_supports(const obhip_terms &t, bool ro, int variant);
+bool hm2_supports(const obhip_terms &t, bool ro);
 int launch_hm2(const obhip_basis &b, obhip_terms &t, const double *d_a, const double *d_y, double ca,
                double cb, double *part, double *d_yhat, double *sspart, unsigned nsplit, uint64_t ntiles,
-               uint64_t tps, int variant, const double *stop0, const double *stop1);
+               uint64_t tps, const double *stop0, const double *stop1);
 // kernels_gram.hip
 // where k_gram_reduce puts the summed tiles: full symmetric p x p (raw G, or with `form` the
 // Hessian e2 G + diag(prec) and its diagonal) or the packed upper triangle of a row-sharded

@@ -956,8 +956,9 @@ def test_newton_solve_sizes_against_library_solve(p):
 
 @pytest.mark.parametrize("panels", [1, 2, 4, 8])
 def test_cholesky_schedules_with_one_to_eight_panels_per_pass(panels):
-    """The blocked Cholesky with 1, 2, 4 and 8 panels per trailing pass (csrc/kernels_chol.hip: the
-    default is 1 below p = 4096, 2 from there, 4 from 8192) at sizes where a pass ends inside a
+    """The blocked Cholesky with 1, 2, 4 and 8 panels per trailing pass (csrc/kernels_chol.hip,
+    chol_panels_at: the default is 1 below p = 3072, from there 8, 4 or 2 by the rows left when a pass
+    starts -- 8 from 8192, 4 from 4096, else 2) at sizes where a pass ends inside a
     panel, right behind one, and in the middle of a pass; the solution and L itself against torch.
     The setting is read once per process: a child process per schedule."""
     import os

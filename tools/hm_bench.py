@@ -1,5 +1,6 @@
 """Times the likelihood's Hessian product (lpdf$hessmult: B^T (e^{-2 sigma} B g), the PCG's inner
-pass) on terms of a given shape (tuning aid; OBHIP_HM2_VARIANT / OBHIP_HM_V1 select the kernel).
+pass) on terms of a given shape (tuning aid; the launcher picks the kernel by the terms' shape,
+OBHIP_HM3=0 / OBHIP_HESSMULT_FUSED=0 force the earlier generations).
 
   python tools/hm_bench.py [n] [p] [d] [cov] [maxlev]      defaults 1000000 4096 8 mat25pow 12
 """
