@@ -994,6 +994,44 @@ int obhip_posterior_extremum_dev(const obhip_posterior *post, const double *d_th
                                  const uint8_t *d_skip /* m or NULL */, int maximize,
                                  int64_t *d_index /* S */, double *d_value /* S */);
 
+/* ---- acquisition picks (no reference counterpart) -----------------------------------------
+ * k of the m candidate rows d_xcand (column-major m x d), picked one after the other by a criterion
+ * of the latent mean mu_i = b_i^T theta and the latent variance d_i = b_i^T inv(H) b_i (without the
+ * noise; sd = sqrt(max(d, 0))), all in standardised units.  Written for minimisation; maximize != 0
+ * applies the same to -mu, -best, -level and -lie_value.  With t = best - xi - mu, u = t / sd:
+ *   OBHIP_ACQ_EI        t Phi(u) + sd phi(u)            (sd = 0: max(t, 0))   expected improvement
+ *   OBHIP_ACQ_PI        Phi(u)                          (sd = 0: t > 0)       probability of improvement
+ *   OBHIP_ACQ_LCB       kappa sd - mu                                         confidence bound
+ *   OBHIP_ACQ_STRADDLE  kappa sd - |mu - level|                               contour f = level
+ * params (host, 4 doubles): best, xi, kappa, level; what a criterion does not use is not looked at,
+ * except that xi must be finite and kappa finite and >= 0 always.  The largest score is picked, the
+ * lowest index among equal scores (EI and PI underflow to exact zeros far from the incumbent).  A
+ * candidate with d_skip[i] != 0 (d_skip may be NULL), one that is picked already, one with a
+ * coordinate that is not finite or a score that is not finite is never picked.  After pick j the
+ * run there is given a value y* without being made -- OBHIP_LIE_BELIEVER: y* = mu_j, the mean does
+ * not move; OBHIP_LIE_CONSTANT: y* = lie_value -- and with s = inv(H) b_j, gamma = e^{2 sigma} + b_j^T s,
+ * a_i = b_i^T s every candidate's mu_i += a_i (y* - mu_j) / gamma, d_i -= a_i^2 / gamma; for EI and PI
+ * best becomes min(best, y*).  Per pick the candidates are passed over by the one-response
+ * predictor and one update kernel, and the host waits for the device once.
+ * d_theta (p): the standardised coefficients of one response.  Out: d_index (k, int64) and d_score
+ * (k), of which *n_picked are written -- fewer than k when no eligible candidate is left, which is
+ * no error; d_score0 (m, may be NULL): every candidate's score at the first step, eligible or not;
+ * d_mean, d_var (m each, may be NULL): mu_i and d_i after all fantasies.  No atomics anywhere: two
+ * calls give the same bits.  The rules of the posterior block hold: every argument check runs
+ * before the first launch and a refused call changes nothing. */
+enum { OBHIP_ACQ_EI = 0, OBHIP_ACQ_PI = 1, OBHIP_ACQ_LCB = 2, OBHIP_ACQ_STRADDLE = 3 };
+enum { OBHIP_LIE_BELIEVER = 0, OBHIP_LIE_CONSTANT = 1 };
+int obhip_acquire_dev(const obhip_posterior *post, const double *d_theta, const double *d_xcand,
+                      uint64_t m, int criterion, const double *params /* host: best, xi, kappa, level */,
+                      int maximize, int lie, double lie_value, const uint8_t *d_skip /* m or NULL */,
+                      uint64_t k, int64_t *d_index, double *d_score, double *d_score0,
+                      double *d_mean, double *d_var, uint64_t *n_picked);
+/* the same on host buffers; xcand m x d column-major with leading dimension m */
+int obhip_acquire(const obhip_posterior *post, const double *theta, const double *xcand, uint64_t m,
+                  int criterion, const double *params, int maximize, int lie, double lie_value,
+                  const uint8_t *skip, uint64_t k, int64_t *index, double *score, double *score0,
+                  double *mean, double *var, uint64_t *n_picked);
+
 /* ---- the model layer: lpdf, loglik_*, logpr_gauss, lpdfvec, predictor ------------------
  * Module rows src/interfaceR.cpp:696-762; classes src/fit.h:23-361; arithmetic
  * src/fit.cpp:37-612 and src/lpdfs/{loglik_std,loglik_gauss,loglik_gda,logpr_gauss}.cpp.

@@ -16,7 +16,7 @@ from .fitting import BFGS_lpdf, BFGS_std, obfit, obpred, obpred_grad
 from .multi import MultiFit, fit_newton_multi
 from .glm import GlmFit, fit_glm
 from .sensitivity import InputMoments, SobolResult, input_moments, main_effects, sobol, uniform_nodes
-from .design import DesignResult, Posterior, ThompsonResult
+from .design import AcquireResult, DesignResult, Posterior, ThompsonResult
 from .torch_emulator import TorchEmulator
 from .driver import HotPath, MultiHotPath
 from .stream import (CVResult, NewtonAccumulator, cv_folds, cv_newton_multi, design_dx,
@@ -33,6 +33,6 @@ __all__ = [
     "design_dx", "fit_newton_grad",
     "predict_jac", "predict_vjp", "TorchEmulator",
     "GlmFit", "fit_glm",
-    "Posterior", "DesignResult", "ThompsonResult",
+    "Posterior", "DesignResult", "ThompsonResult", "AcquireResult",
     "InputMoments", "SobolResult", "input_moments", "uniform_nodes", "sobol", "main_effects",
 ]

@@ -29,11 +29,6 @@ namespace {
 
 uint64_t pad128(uint64_t v) { return (v + 127) / 128 * 128; }
 
-struct BasisGuard {
-  obhip_basis *b = nullptr;
-  ~BasisGuard() { obhip_basis_destroy(b); }
-};
-
 // d_M (p x p) = sum_r u_r b_r b_r^T / sum u over the rows of d_xref
 int reference_moment(const obhip_model &m, obhip_terms &t, const double *d_xref, uint64_t r, const double *d_u,
                      double *d_M) {
@@ -63,14 +58,20 @@ int reference_moment(const obhip_model &m, obhip_terms &t, const double *d_xref,
   return launch_gram(*g.b, t, d_M);
 }
 
+}  // namespace
+
+namespace obhip {
 // d_out[i] = b_i^T Q b_i at the n rows of d_x, Q symmetric (norms false: Y = Q B^T, then b_i . y_i), or
 // || X^T b_i ||^2 for the upper triangular X = L^-T (norms true: Z = B X, then the squares of row i).  Either
 // way a stored product of launch_atb and one thread per row that sums its p entries in ascending order: two
 // bit-identical rows get bit-identical results wherever they stand, which the tie rule of the selection rests
 // on.  (post_var_dev's fused row norms are the same mathematics but sum a row's columns in an order that
-// depends on the row's place in its tile; they stay what obhip_posterior_var_dev returns.)
+// depends on the row's place in its tile; they stay what obhip_posterior_var_dev returns.)  That holds for rows
+// whose 128-row tiles have the same index mod 8 only: launch_atb's stored product starts a tile's chunks of k
+// at (I + J) mod 8.  fixed_order (the acquisition entry) takes the product that does not; the selection keeps
+// the bits it has always returned.
 int row_forms_dev(const obhip_model &m, obhip_terms &t, const double *d_Q, bool norms, uint64_t p, uint64_t pp,
-                  const double *d_x, uint64_t n, double *d_out) {
+                  const double *d_x, uint64_t n, double *d_out, bool fixed_order) {
   // row chunks so that the two blocks (pp x rows doubles each) stay below 1 GB each
   const uint64_t cmax = std::max<uint64_t>(128, ((1ull << 30) / (pp * sizeof(double))) / 128 * 128);
   DevBuf<double> Bcm, Ycm, xc;
@@ -92,14 +93,14 @@ int row_forms_dev(const obhip_model &m, obhip_terms &t, const double *d_Q, bool 
     const double *B = Bcm.p, *Y = Ycm.p;
     double *out = d_out + r0;
     if (norms) {
-      OB_TRY(launch_atb(2, Bcm.p, npad, npad, d_Q, pp, pp, pp, true, Ycm.p, pp));  // Z = B X, npad x pp
+      OB_TRY(launch_atb(fixed_order ? 3 : 2, Bcm.p, npad, npad, d_Q, pp, pp, pp, true, Ycm.p, pp));  // Z = B X, npad x pp
       OB_TRY(vmap(nr, [=] __device__(uint64_t i) {
         double s = 0.0;
         for (uint64_t k = 0; k < p; ++k) s = fma(Y[i * pp + k], Y[i * pp + k], s);
         out[i] = s;
       }));
     } else {
-      OB_TRY(launch_atb(2, d_Q, pp, pp, Bcm.p, npad, npad, pp, false, Ycm.p, npad));  // Y = Q B^T, pp x npad
+      OB_TRY(launch_atb(fixed_order ? 3 : 2, d_Q, pp, pp, Bcm.p, npad, npad, pp, false, Ycm.p, npad));  // Y = Q B^T, pp x npad
       OB_TRY(vmap(nr, [=] __device__(uint64_t i) {
         double s = 0.0;
         for (uint64_t k = 0; k < p; ++k) s = fma(B[k * npad + i], Y[k * npad + i], s);
@@ -110,6 +111,9 @@ int row_forms_dev(const obhip_model &m, obhip_terms &t, const double *d_Q, bool 
   }
   return 0;
 }
+}  // namespace obhip
+
+namespace {
 
 int check_select(const char *who, const obhip_posterior *post, const void *xcand, uint64_t m, int criterion,
                  const void *xref, uint64_t r, uint64_t k, const void *index, const void *score,

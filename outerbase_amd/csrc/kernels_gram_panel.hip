@@ -171,7 +171,7 @@ __device__ __forceinline__ void lds_rd_h1(const uint32_t (&baddr)[4], double (&b
 // For the last two the k range of column tile J ends at (J + 1) * 128 when `tri` says Bm is
 // upper triangular.  DBG: one block reports its s_memtime / s_memrealtime span (clock and
 // matrix-pipe cycles per chunk under load, OBHIP_GRAM_DBG=1); production carries none of it.
-constexpr int kAtbGram = 0, kAtbNorm = 1, kAtbStore = 2;
+constexpr int kAtbGram = 0, kAtbNorm = 1, kAtbStore = 2, kAtbStoreFixed = 3;  // 3: kAtbStore, one order of k
 __host__ __device__ inline uint64_t atb_task(uint64_t I, uint64_t J, uint64_t y, uint64_t type = 0) {
   return I | (J << 24) | (y << 48) | (type << 62);
 }
@@ -196,7 +196,9 @@ __device__ __forceinline__ uint32_t atb_wave_code(uint32_t type, int wave) {
   return (tab >> (8 * wave)) & 0xffu;
 }
 
-template <int MODE, bool DBG>
+// FIXED: every task walks its chunks of k from chunk 0 (no rotation by (I + J) mod 8), so that an entry of C is
+// summed in one order whatever tile it stands in
+template <int MODE, bool DBG, bool FIXED = false>
 __global__ void __launch_bounds__(256, 2)
 k_atb_dma2(const double *__restrict__ A, uint64_t ldA, const double *__restrict__ Bm, uint64_t ldB,
            int nb, int npairs, uint64_t ntiles, uint64_t split_base /* Gram: tiles per row split ... */,
@@ -247,7 +249,7 @@ k_atb_dma2(const double *__restrict__ A, uint64_t ldA, const double *__restrict_
   // together are NOT merged (each goes out to the fabric), so sharers in lockstep miss
   // together; one chunk (~3.6 us) apart, the first brings the line in and seven hit.  The
   // window of 8 chunks x 16 panels x 16 KB = 2 MB stays inside the 4-MB L2.
-  const int rot = nchunks > 0 ? ((I + J) & 7) % nchunks : 0;
+  const int rot = !FIXED && nchunks > 0 ? ((I + J) & 7) % nchunks : 0;
   auto issue = [&](int ch, int buf) {
     const uint32_t l = lds0 + buf * tszb;
     int cr = ch + rot;
@@ -838,7 +840,9 @@ int launch_gram_panel(const obhip_basis &bc, obhip_terms &t, const GramSink &sin
 // A is K x M (leading dimension ldA), Bm is K x N (ldB); K a multiple of 64 and M, N multiples
 // of 128 (callers pad with zeros).  tri: Bm[k][c] = 0 for k > c (column tile J needs
 // k < (J + 1) * 128 only).  mode kAtbNorm: out[J * ldo + i] = sum_{c in tile J} C[i][c]^2;
-// mode kAtbStore: out[i * ldo + c] = C[i][c].  Tasks go to the XCDs in 8 x 8 squares of
+// mode kAtbStore: out[i * ldo + c] = C[i][c]; kAtbStoreFixed: the same with every entry summed over k in one
+// order (kAtbStore starts a tile's chunks of k at (I + J) mod 8: two equal rows of A^T in tiles I and I' get
+// sums that differ in their last bits).  Tasks go to the XCDs in 8 x 8 squares of
 // (row tile, column tile) like the Gram's.
 int launch_atb(int mode, const double *A, uint64_t ldA, uint64_t M, const double *Bm, uint64_t ldB,
                uint64_t N, uint64_t K, bool tri, double *out, uint64_t ldo) {
@@ -925,6 +929,11 @@ int launch_atb(int mode, const double *A, uint64_t ldA, uint64_t M, const double
   } else if (mode == kAtbStore) {
     OB_TRY(ensure_dyn_lds((const void *)k_atb_dma2<kAtbStore, false>, lds));
     hipLaunchKernelGGL((k_atb_dma2<kAtbStore, false>), dim3((unsigned)ntasks), dim3(256), lds,
+                       cur_stream(), A, ldA, Bm, ldB, 0, 0, ktiles, ktiles, tri ? 1 : 0, dtab.p, out,
+                       ldo, nullptr);
+  } else if (mode == kAtbStoreFixed) {
+    OB_TRY(ensure_dyn_lds((const void *)k_atb_dma2<kAtbStore, false, true>, lds));
+    hipLaunchKernelGGL((k_atb_dma2<kAtbStore, false, true>), dim3((unsigned)ntasks), dim3(256), lds,
                        cur_stream(), A, ldA, Bm, ldB, 0, 0, ktiles, ktiles, tri ? 1 : 0, dtab.p, out,
                        ldo, nullptr);
   } else {

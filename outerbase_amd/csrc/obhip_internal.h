@@ -543,7 +543,8 @@ int launch_materialize_rows(const obhip_basis &b, obhip_terms &t, double *d_B, G
 int ensure_bmat(obhip_basis &b, obhip_terms &t, GramFuse *fuse = nullptr);  // b.bmat = design matrix of (b, t)
 bool gram_panel_supports(const obhip_basis &b, const obhip_terms &t);
 // C = A^T Bm on the matrix cores (kernels_gram_panel.hip): mode 1 = row norms of C into
-// out[J * ldo + i] per 128-column tile J, mode 2 = C stored row-major with ldo
+// out[J * ldo + i] per 128-column tile J, mode 2 = C stored row-major with ldo, mode 3 = mode 2 with every entry
+// summed over k in one order wherever it stands (mode 2 rotates a tile's start by its indices)
 int launch_atb(int mode, const double *A, uint64_t ldA, uint64_t M, const double *Bm, uint64_t ldB,
                uint64_t N, uint64_t K, bool tri, double *out, uint64_t ldo);
 // kernels_trtri.hip: X (pp x pp, zeroed) = L^-T in its upper triangle; transpose of an n x n block
@@ -576,6 +577,16 @@ int posterior_from_hessian(obhip_posterior **out, const obhip_model *m, const ob
 // design.cpp / kernels_design.hip: one greedy step of the sequential design over the candidates (fused: the
 // basis of a 64-row tile in LDS, a = B s and c = B h on the matrix cores, downdate, score and argmax in
 // the epilogue) and the p-space work between two steps
+struct BasisGuard {
+  obhip_basis *b = nullptr;
+  ~BasisGuard() { obhip_basis_destroy(b); }
+};
+// design.cpp: b_i^T Q b_i (norms false) or || X^T b_i ||^2 (norms true) at the n rows of d_x, a stored product
+// and one ascending sum per row.  fixed_order: the stored product by launch_atb's mode 3, and only then do
+// bit-identical rows get bit-identical results wherever they stand (without it: when their 128-row tiles of a
+// chunk have the same index mod 8 -- what obhip_design_select has always returned)
+int row_forms_dev(const obhip_model &m, obhip_terms &t, const double *d_Q, bool norms, uint64_t p, uint64_t pp,
+                  const double *d_x, uint64_t n, double *d_out, bool fixed_order = false);
 constexpr int kDesignScal = 8;  // doubles of the step's scalar block: gamma, tau, d_j, nu, -, nothing left, -, -
 struct DesignStep {
   int crit = 0;
@@ -603,6 +614,30 @@ int launch_design_pick(const DesignStep &s, uint64_t nparts, uint64_t d, uint64_
 // then S -= s s^T / gamma and T -= (s h^T + h s^T) / gamma - s s^T tau / gamma^2
 int launch_design_pspace(int crit, uint64_t p, uint64_t pp, const double *d_b, double *d_S, double *d_T, double *d_sv,
                          double *d_hv, double *d_sh, double *d_scal, double *d_trace, uint64_t step);
+// acquire.cpp / kernels_acquire.hip: acquisition picks (include/obhip.h, "acquisition picks")
+// the step's scalar block: the kDesignScal doubles launch_design_pspace writes, then delta = y* - mu_j and the
+// incumbent (in the sign the criterion is scored with)
+constexpr int kAcqDelta = kDesignScal, kAcqBest = kDesignScal + 1, kAcqScal = kDesignScal + 2;
+struct AcqStep {
+  int crit = 0, lie = 0;
+  uint64_t n = 0;
+  double sgn = 1.0, xi = 0.0, kappa = 0.0, level = 0.0, lie_value = 0.0;  // level: signed; lie_value: as given
+  const double *x = nullptr;       // candidates, column-major n x d
+  const double *a = nullptr;       // n: b_i^T s of the previous pick (zeros before the first)
+  const uint8_t *elig = nullptr;   // n: launch_sample_elig's map
+  uint8_t *picked = nullptr;       // n
+  double *mu = nullptr, *dvar = nullptr;  // n each
+  double *scal = nullptr;          // kAcqScal doubles
+  double *part_score = nullptr;    // per workgroup of 256 rows
+  int64_t *part_idx = nullptr;
+};
+constexpr uint64_t kAcqRows = 256;
+// downdate of every candidate by the previous pick, its score, one (best score, lowest index) pair per workgroup;
+// d_score0 (may be null): every row's score as formed
+int launch_acq_update(const AcqStep &s, double *d_score0);
+// the partial pairs -> the step's pick: index and score appended at slot `step`, the row marked, x_j gathered
+// into d_xj, delta and the incumbent into scal; no eligible candidate: scal[5] = 1 and nothing else written
+int launch_acq_pick(const AcqStep &s, uint64_t d, uint64_t step, int64_t *d_index, double *d_score, double *d_xj);
 // sample.cpp / kernels_sample.hip: draws from N(theta, inv(H)) and the per-draw extremum of their sample
 // paths over a candidate set (include/obhip.h, "posterior draws")
 constexpr uint64_t kDrawChunk = 64;  // draws of one launch of k_draw outside the fused pass (which takes up to 128)

@@ -21,6 +21,11 @@ candidate set in one fused pass per block of draws (csrc/kernels_sample.hip; the
 stored) -- Thompson sampling, the simplest batch acquisition that uses the response.  torch supplies the
 normals (or the caller does, z=), the library the arithmetic.
 
+Acquisition.  acquire picks k candidates one after the other by expected improvement, probability of
+improvement, a confidence bound or the straddle contour criterion of the latent mean and variance; after
+every pick the run there is given a value without being made (the kriging believer or a constant liar) and
+every candidate's mean and variance are downdated on the device (csrc/kernels_acquire.hip).
+
 torch holds the device memory; all arithmetic is in libobhip.
 """
 import ctypes as C
@@ -31,6 +36,8 @@ from . import obmod
 from ._lib import call, lib
 
 CRITERIA = {"maxvar": 0, "imse": 1}
+ACQUISITIONS = {"ei": 0, "pi": 1, "lcb": 2, "straddle": 3}
+LIES = {"believer": 0, "constant": 1}
 
 
 def _stream():
@@ -67,6 +74,16 @@ class ThompsonResult:
     when no candidate was eligible; value (S): the path there (NaN); picks: the distinct indices in order of
     first appearance, -1 left out; counts: per pick the number of draws that chose it -- counts / S is the
     empirical probability that the candidate is the optimum."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+class AcquireResult:
+    """index (n_picked): the picked candidates in order; score (n_picked): each one's criterion when it was
+    picked; score0 (m): every candidate's criterion at the first step, eligible or not; mean, var (m): the latent
+    mean and variance (without the noise) of every candidate after all fantasies; criterion.  Fewer than k
+    picks: no eligible candidate was left."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -207,6 +224,87 @@ class Posterior:
         return DesignResult(index=index.cpu().numpy()[:n].copy(), score=score.cpu().numpy()[:n].copy(),
                             var=var.cpu().numpy(), trace=trace.cpu().numpy()[:n + 1].copy(), criterion=criterion,
                             n_picked=n, k=k)
+
+    # -- acquisition -------------------------------------------------------------------------
+    def acquire(self, xcand, theta, k=1, criterion="ei", best=None, level=None, kappa=1.96, xi=0.0, maximize=False,
+                lie="believer", lie_value=None, skip=None, response=None):
+        """Pick k of the candidate rows xcand (m x d) one after the other by a criterion of the latent mean mu and
+        standard deviation sd (without the noise) of the response with the standardised coefficients theta (p).
+        Written for minimisation (maximize=True: the same on -mu, -best, -level, -lie_value), t = best - xi - mu,
+        u = t / sd:
+          "ei"        t Phi(u) + sd phi(u), expected improvement on the incumbent best (required);
+          "pi"        Phi(u), probability of improvement on best (required);
+          "lcb"       kappa sd - mu, the confidence bound;
+          "straddle"  kappa sd - |mu - level|, the contour f = level (required).
+        After a pick the run there is given a value without being made -- lie="believer": its mean, the means do
+        not move; lie="constant": lie_value (None: best for ei / pi) -- every candidate's mean and variance are
+        conditioned on it, and for ei / pi the incumbent becomes the smaller of best and that value.  skip (m,
+        nonzero = leave out): rows that are never picked, like rows with a coordinate that is not finite, rows
+        picked before and rows whose score is not finite.  The lowest index wins among equal scores: ei and pi
+        underflow to exact zeros far from the incumbent.  response=j on a posterior that carries meansd: best,
+        level, lie_value and xi are given in raw units of response j and standardised on the way in; mean, var and
+        the ei / lcb / straddle scores are de-standardised on the way out (pi has no unit).  The scale is positive,
+        so the picks do not move.  -> AcquireResult"""
+        import torch
+        self._need()
+        if criterion not in ACQUISITIONS:
+            raise ValueError("criterion must be one of %s" % sorted(ACQUISITIONS))
+        if lie not in LIES:
+            raise ValueError("lie must be one of %s" % sorted(LIES))
+        xcand = _rows(self.om, xcand, "xcand")
+        m, k = xcand.shape[0], int(k)
+        if m == 0 or k < 1:
+            raise ValueError("acquire needs candidates and k >= 1")
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.shape != (self.p,):
+            raise ValueError("theta must be the p standardised coefficients of one response")
+        if criterion in ("ei", "pi") and best is None:
+            raise ValueError("criterion %r needs best, the incumbent" % criterion)
+        if criterion == "straddle" and level is None:
+            raise ValueError("criterion 'straddle' needs level")
+        if lie == "constant" and lie_value is None:
+            if criterion not in ("ei", "pi"):
+                raise ValueError("lie='constant' needs lie_value")
+            lie_value = best
+        best, level = 0.0 if best is None else float(best), 0.0 if level is None else float(level)
+        lie_value, kappa, xi = 0.0 if lie_value is None else float(lie_value), float(kappa), float(xi)
+        if not all(np.isfinite(v) for v in (best, level, lie_value, xi)):
+            raise ValueError("best, level, lie_value and xi must be finite")
+        if not (np.isfinite(kappa) and kappa >= 0):
+            raise ValueError("kappa must be finite and >= 0")
+        if skip is not None:
+            skip = np.ascontiguousarray(np.asarray(skip) != 0, dtype=np.uint8)
+            if skip.shape != (m,):
+                raise ValueError("skip must have one entry per candidate")
+        sc = self._scale(response)
+        if sc is not None:                                       # raw units -> standardised
+            best, level, lie_value, xi = (best - sc[0]) / sc[1], (level - sc[0]) / sc[1], (lie_value - sc[0]) / sc[1], xi / sc[1]
+        dev = _stream()
+        f64, nan = torch.float64, float("nan")
+        dx = _dev_cols(xcand, dev)
+        dth = torch.from_numpy(theta).to(dev)
+        dk = torch.from_numpy(skip).to(dev) if skip is not None else None
+        index = torch.full((k,), -1, dtype=torch.int64, device=dev)
+        score = torch.full((k,), nan, dtype=f64, device=dev)
+        score0, mean, var = (torch.full((m,), nan, dtype=f64, device=dev) for _ in range(3))
+        params = (C.c_double * 4)(best, xi, kappa, level)
+        npk = C.c_uint64(0)
+        call("obhip_acquire_dev", self._h, dth.data_ptr(), dx.data_ptr(), m, ACQUISITIONS[criterion], params,
+             int(bool(maximize)), LIES[lie], lie_value, None if dk is None else dk.data_ptr(), k, index.data_ptr(),
+             score.data_ptr(), score0.data_ptr(), mean.data_ptr(), var.data_ptr(), C.byref(npk))
+        torch.cuda.synchronize()
+        n = npk.value
+        score, score0, mean, var = (a.cpu().numpy() for a in (score, score0, mean, var))
+        score = score[:n].copy()
+        if sc is not None:
+            mean, var = sc[0] + sc[1] * mean, sc[1] ** 2 * var
+            if criterion in ("ei", "straddle"):
+                score, score0 = sc[1] * score, sc[1] * score0
+            elif criterion == "lcb":                             # kappa sd - mu: the centre comes back with the sign of -mu
+                off = sc[0] if maximize else -sc[0]
+                score, score0 = sc[1] * score + off, sc[1] * score0 + off
+        return AcquireResult(index=index.cpu().numpy()[:n].copy(), score=score, score0=score0, mean=mean, var=var,
+                             criterion=criterion, n_picked=n, k=k)
 
     # -- draws -------------------------------------------------------------------------------
     def _draw_args(self, theta, n_draws, seed, z):
