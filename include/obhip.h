@@ -689,6 +689,36 @@ int obhip_dim_moments(const obhip_model *m, const obhip_terms *t, const double *
                       uint64_t ldx, const double *weights, uint64_t ldw, double *mean, double *cov);
 int obhip_sobol(const obhip_terms *t, const double *Theta, uint64_t q, const double *mean_tab,
                 const double *cov_tab, double *out, double *g);
+/* Which inputs matter together: for every pair of dimensions i < j, in the order (0,1), (0,2), ..
+ * (0,d-1), (1,2), .. -- n_pairs = d (d - 1) / 2 of them -- with t = t_ki, s = t_kj:
+ *   G_ij[t,s] = sum_{k: t_ki = t, t_kj = s} theta_k prod_{l != i,j} m_l[t_kl]   (L_i x L_j, row-major; no division)
+ *   V2_ij     = tr(C_i G_ij C_j G_ij^T)              = Var E[f | x_i, x_j] - V1_i - V1_j, the pure second order
+ *   VT2_ij    = sum_{k,k'} theta_k theta_k' C_i[t,t'] C_j[s,s'] prod_{l != i,j} A_l[t_kl, t_k'l]
+ *                                                    = the variances of all subsets that hold both i and j
+ * and E[f | x_i = z, x_j = z'] = sum_{t,s} G_ij[t,s] psi_{i,t}(z) psi_{j,s}(z').  The limits are those of
+ * obhip_sobol_dev, refused with a message before any device call; fixed summation order, no atomics. */
+/* *n_pairs = d (d - 1) / 2, *n_G = sum_{i<j} L_i L_j: a packed G holds G_ij in pair order (either may be NULL) */
+int obhip_sobol2_layout(const obhip_terms *t, uint64_t *n_pairs, uint64_t *n_G);
+int obhip_sobol2_workspace_bytes(uint64_t p, uint64_t d, uint64_t q, uint64_t *bytes);
+/* d_Theta and the tables as obhip_sobol_dev takes them (every C_l symmetric).  d_out: q x 2 n_pairs
+ * row-major, per response [V2 of every pair, VT2 of every pair].  d_G (may be NULL; d_out has the same
+ * bits either way): the packed G, response j at j * n_G.  d_ws: obhip_sobol2_workspace_bytes(p, d, q).
+ * d = 1 has no pairs: nothing is written (d_out, d_G and d_ws are not looked at) and the call returns OK. */
+int obhip_sobol2_dev(const obhip_terms *t, const double *d_Theta, uint64_t q,
+                     const double *d_mean_tab, const double *d_cov_tab, double *d_out, double *d_G,
+                     void *d_ws, uint64_t ws_bytes);
+/* The conditional mean E[f | x_dim_i = z_a, x_dim_j = z'_b] on the grid d_grid_i (Gi) x d_grid_j (Gj):
+ * d_out[(r Gi + a) Gj + b] for response r -- q slabs of Gi x Gj, row-major, b fastest.  d_G as
+ * obhip_sobol2_dev writes it for q responses.  The caller subtracts the two main effects and mu for the
+ * interaction surface.  Gi Gj = 0 is a no-op; dim_i == dim_j or a dimension out of range is
+ * OBHIP_ERR_INVALID; dim_i > dim_j reads G transposed. */
+int obhip_interaction_effect_dev(const obhip_model *m, const obhip_terms *t, uint64_t dim_i,
+                                 uint64_t dim_j, const double *d_G, uint64_t q,
+                                 const double *d_grid_i, uint64_t Gi, const double *d_grid_j,
+                                 uint64_t Gj, double *d_out);
+/* host-buffer form: out q x 2 n_pairs, G (may be NULL) q x n_G */
+int obhip_sobol2(const obhip_terms *t, const double *Theta, uint64_t q, const double *mean_tab,
+                 const double *cov_tab, double *out, double *G);
 
 /* ---- streaming Newton fit: rows come and go, one pass over each (no reference counterpart) ----
  * obfit (R/fitting.R:40-120) and every fit entry above take all rows at once and form the whole

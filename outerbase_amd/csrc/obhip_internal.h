@@ -376,6 +376,9 @@ struct obhip_terms {
   // L_l = maxlev[l] + 1, its offset in a packed mean table and in a packed cov table ([3][d] ints)
   obhip::DevBuf<uint8_t> sobol_lev;
   obhip::DevBuf<int> sobol_meta;
+  // and per pair of dimensions i < j, in the order (0,1), (0,2), .. (0,d-1), (1,2), ..: i, j and the
+  // offset of G_ij in a packed G ([d (d - 1) / 2][3] ints)
+  obhip::DevBuf<int> sobol_pairs;
   int prepare(const std::vector<int64_t> &cap, const std::vector<obhip::DimDesc> &dims);
 };
 
@@ -748,6 +751,23 @@ int launch_sobol_pairs(const uint8_t *d_lev, const int *d_meta, uint64_t p, uint
                        const double *d_Theta, const double *d_mtab, const double *d_ctab, double *d_part, double *d_out);
 int launch_main_effect(const obhip_model &m, obhip_terms &t, uint64_t dim, const double *d_g, uint64_t q,
                        const double *d_grid, uint64_t G, double *d_out);
+// second-order and total-interaction variances and the interaction surface
+constexpr int kSobol2T = 5;  // dimensions per block of the d x d triangle of outputs: T x T accumulators per pass
+inline int sobol2_reg_dims(uint64_t d) { return d <= 8 ? 8 : 24; }  // dimensions whose row offsets stay in registers
+size_t sobol2_pairs_lds(uint64_t n_cov);                             // dynamic LDS of k_sobol_pairs2
+uint64_t sobol2_part_doubles(uint64_t p, uint64_t d, uint64_t q);    // partials of its pair sum
+// pairs: obhip_terms::sobol_pairs; gmax: the largest L_i L_j; d_out q x 2 n_pairs (the V2 half), d_G may be null
+int launch_sobol2_second(const uint8_t *d_lev, const int *d_meta, const int *d_pairs, uint64_t p, uint64_t d, uint64_t q,
+                         uint64_t n_pairs, uint64_t n_G, uint64_t gmax, const double *d_Theta, const double *d_mtab,
+                         const double *d_ctab, double *d_out, double *d_G);
+// the VT2 half of d_out
+int launch_sobol2_pairs(const uint8_t *d_lev, const int *d_meta, const int *d_pairs, uint64_t p, uint64_t d, uint64_t q,
+                        uint64_t n_cov, const double *d_Theta, const double *d_mtab, const double *d_ctab,
+                        double *d_part, double *d_out);
+// d_Gij: G of the pair (di, dj) of response 0, response j at j * n_G
+int launch_interaction_effect(const obhip_model &m, obhip_terms &t, uint64_t di, uint64_t dj, const double *d_Gij,
+                              uint64_t n_G, uint64_t q, const double *d_grid_i, uint64_t Gi, const double *d_grid_j,
+                              uint64_t Gj, double *d_out);
 // ---- runtime value -> template argument -----------------------------------------------------------
 // pick_or<1, 2, 4, 8>(ng, miss, [&](auto NG) { ... NG() ... }): the lambda is called with the
 // std::integral_constant of the listed value that v equals and its result returned; `miss` when v

@@ -54,6 +54,36 @@ int ensure_sobol_tables(obhip_terms &t) {
   return 0;
 }
 
+// the pairs i < j of dimensions in the order (0,1), (0,2), .. (0,d-1), (1,2), ..
+struct PairLayout {
+  uint64_t n_pairs = 0, n_G = 0, gmax = 1;
+};
+
+PairLayout pair_layout(const obhip_terms &t) {
+  PairLayout pl;
+  for (uint64_t i = 0; i < t.d; ++i)
+    for (uint64_t j = i + 1; j < t.d; ++j) {
+      const uint64_t g = ((uint64_t)t.maxlev[i] + 1) * ((uint64_t)t.maxlev[j] + 1);
+      ++pl.n_pairs;
+      pl.n_G += g;
+      pl.gmax = std::max(pl.gmax, g);
+    }
+  return pl;
+}
+
+// i, j and the offset of G_ij on the device, once per term set
+int ensure_sobol_pairs(obhip_terms &t) {
+  if (t.sobol_pairs.p || t.d < 2) return 0;
+  std::vector<int> pr;
+  int go = 0;
+  for (uint64_t i = 0; i < t.d; ++i)
+    for (uint64_t j = i + 1; j < t.d; ++j) {
+      pr.push_back((int)i), pr.push_back((int)j), pr.push_back(go);
+      go += ((int)t.maxlev[i] + 1) * ((int)t.maxlev[j] + 1);
+    }
+  return t.sobol_pairs.upload(pr.data(), pr.size());
+}
+
 }  // namespace
 
 extern "C" {
@@ -119,6 +149,72 @@ int obhip_sobol_dev(const obhip_terms *t, const double *d_Theta, uint64_t q, con
                             d_out);
 }
 
+int obhip_sobol2_layout(const obhip_terms *t, uint64_t *n_pairs, uint64_t *n_G) {
+  if (!t) return fail(OBHIP_ERR_INVALID, "sobol2_layout: null terms");
+  Layout lay;
+  OB_TRY(sobol_layout("sobol2_layout", *t, lay));
+  const PairLayout pl = pair_layout(*t);
+  if (n_pairs) *n_pairs = pl.n_pairs;
+  if (n_G) *n_G = pl.n_G;
+  return 0;
+}
+
+int obhip_sobol2_workspace_bytes(uint64_t p, uint64_t d, uint64_t q, uint64_t *bytes) {
+  if (!bytes || p == 0 || d == 0 || d > 255 || q == 0 || q > kSobolMaxQ || p > (1ull << 24))
+    return fail(OBHIP_ERR_INVALID, "sobol2_workspace_bytes: null bytes, or p, d, q out of range");
+  *bytes = std::max<uint64_t>(256, align256(sobol2_part_doubles(p, d, q) * sizeof(double)));
+  return 0;
+}
+
+int obhip_sobol2_dev(const obhip_terms *t, const double *d_Theta, uint64_t q, const double *d_mean_tab,
+                     const double *d_cov_tab, double *d_out, double *d_G, void *d_ws, uint64_t ws_bytes) {
+  if (!t || !d_Theta || !d_mean_tab || !d_cov_tab)
+    return fail(OBHIP_ERR_INVALID, "sobol2_dev: null terms, Theta or tables");
+  if (q == 0 || q > kSobolMaxQ) return fail(OBHIP_ERR_INVALID, "sobol2_dev: 1 to 65535 responses");
+  Layout lay;
+  OB_TRY(sobol_layout("sobol2_dev", *t, lay));
+  if (t->d == 1) return 0;  // no pairs: nothing to write
+  if (!d_out || !d_ws) return fail(OBHIP_ERR_INVALID, "sobol2_dev: null out or workspace");
+  uint64_t need = 0;
+  OB_TRY(obhip_sobol2_workspace_bytes(t->p, t->d, q, &need));
+  if (ws_bytes < need)
+    return fail(OBHIP_ERR_INVALID, "sobol2_dev: workspace smaller than obhip_sobol2_workspace_bytes");
+  const PairLayout pl = pair_layout(*t);
+  OB_TRY(require_device());
+  obhip_terms &tt = *const_cast<obhip_terms *>(t);
+  OB_TRY(ensure_sobol_tables(tt));
+  OB_TRY(ensure_sobol_pairs(tt));
+  OB_TRY(launch_sobol2_second(tt.sobol_lev.p, tt.sobol_meta.p, tt.sobol_pairs.p, t->p, t->d, q, pl.n_pairs, pl.n_G,
+                              pl.gmax, d_Theta, d_mean_tab, d_cov_tab, d_out, d_G));
+  return launch_sobol2_pairs(tt.sobol_lev.p, tt.sobol_meta.p, tt.sobol_pairs.p, t->p, t->d, q, lay.n_cov, d_Theta,
+                             d_mean_tab, d_cov_tab, (double *)d_ws, d_out);
+}
+
+int obhip_interaction_effect_dev(const obhip_model *m, const obhip_terms *t, uint64_t dim_i, uint64_t dim_j,
+                                 const double *d_G, uint64_t q, const double *d_grid_i, uint64_t Gi,
+                                 const double *d_grid_j, uint64_t Gj, double *d_out) {
+  if (!m || !t || !d_G || !d_grid_i || !d_grid_j || !d_out)
+    return fail(OBHIP_ERR_INVALID, "interaction_effect_dev: null model, terms, G, grids or out");
+  if (q == 0 || q > kSobolMaxQ) return fail(OBHIP_ERR_INVALID, "interaction_effect_dev: 1 to 65535 responses");
+  if (Gi > (1ull << 32) || Gj > (1ull << 32) || Gi * Gj > (1ull << 32))
+    return fail(OBHIP_ERR_INVALID, "interaction_effect_dev: more than 2^32 grid points in one call");
+  OB_TRY(check_compat(m, t));
+  if (dim_i >= m->d || dim_j >= m->d) return fail(OBHIP_ERR_INVALID, "interaction_effect_dev: dimension out of range");
+  if (dim_i == dim_j) return fail(OBHIP_ERR_INVALID, "interaction_effect_dev: the two dimensions are the same");
+  Layout lay;
+  OB_TRY(sobol_layout("interaction_effect_dev", *t, lay));
+  if (Gi * Gj == 0) return 0;
+  OB_TRY(require_device());
+  // G is stored for the lower dimension first: the other order reads it transposed
+  const uint64_t lo = std::min(dim_i, dim_j), hi = std::max(dim_i, dim_j);
+  uint64_t goff = 0;
+  for (uint64_t i = 0; i <= lo; ++i)
+    for (uint64_t j = i + 1; j < (i == lo ? hi : t->d); ++j)
+      goff += ((uint64_t)t->maxlev[i] + 1) * ((uint64_t)t->maxlev[j] + 1);
+  return launch_interaction_effect(*m, *const_cast<obhip_terms *>(t), dim_i, dim_j, d_G + goff, pair_layout(*t).n_G, q,
+                                   d_grid_i, Gi, d_grid_j, Gj, d_out);
+}
+
 int obhip_main_effect_dev(const obhip_model *m, const obhip_terms *t, uint64_t dim, const double *d_g, uint64_t q,
                           const double *d_grid, uint64_t G, double *d_out) {
   if (!m || !t || !d_g || !d_grid || !d_out)
@@ -177,6 +273,32 @@ int obhip_sobol(const obhip_terms *t, const double *Theta, uint64_t q, const dou
   OB_TRY(obhip_sobol_dev(t, dth.p, q, dm.p, dc.p, dout.p, dg.p, ws.p, wsb));
   OB_TRY(d2h(out, dout.p, q * (2 + 2 * t->d) * sizeof(double)));
   if (g) OB_TRY(d2h(g, dg.p, q * lay.n_mean * sizeof(double)));
+  return 0;
+}
+
+int obhip_sobol2(const obhip_terms *t, const double *Theta, uint64_t q, const double *mean_tab, const double *cov_tab,
+                 double *out, double *G) {
+  if (!t || !Theta || !mean_tab || !cov_tab) return fail(OBHIP_ERR_INVALID, "sobol2: null terms, Theta or tables");
+  if (q == 0 || q > kSobolMaxQ) return fail(OBHIP_ERR_INVALID, "sobol2: 1 to 65535 responses");
+  Layout lay;
+  OB_TRY(sobol_layout("sobol2", *t, lay));
+  if (t->d == 1) return 0;
+  if (!out) return fail(OBHIP_ERR_INVALID, "sobol2: null out");
+  uint64_t wsb = 0;
+  OB_TRY(obhip_sobol2_workspace_bytes(t->p, t->d, q, &wsb));
+  const PairLayout pl = pair_layout(*t);
+  OB_TRY(require_device());
+  DevBuf<double> dth, dm, dc, dout, dg;
+  DevBuf<char> ws;
+  OB_TRY(dth.upload(Theta, t->p * q));
+  OB_TRY(dm.upload(mean_tab, lay.n_mean));
+  OB_TRY(dc.upload(cov_tab, lay.n_cov));
+  OB_TRY(dout.alloc(q * 2 * pl.n_pairs));
+  if (G) OB_TRY(dg.alloc(q * pl.n_G));
+  OB_TRY(ws.alloc(wsb));
+  OB_TRY(obhip_sobol2_dev(t, dth.p, q, dm.p, dc.p, dout.p, dg.p, ws.p, wsb));
+  OB_TRY(d2h(out, dout.p, q * 2 * pl.n_pairs * sizeof(double)));
+  if (G) OB_TRY(d2h(G, dg.p, q * pl.n_G * sizeof(double)));
   return 0;
 }
 

@@ -172,6 +172,28 @@ class MultiFit:
         mom = sensitivity.input_moments(self.om, self._t, nodes, weights)
         return sensitivity.main_effects(self.om, self._t, self.coeff, mom, dim, grid) * self.y_sca[None, :]
 
+    def sobol2(self, nodes, weights=None):
+        """Second-order and total-interaction indices of every response under the product measure of nodes /
+        weights, in raw units: Sobol2Result with the variances times y_sca^2 and the shares unchanged."""
+        from . import sensitivity
+        mom = sensitivity.input_moments(self.om, self._t, nodes, weights)
+        res = sensitivity.sobol2(self.om, self._t, self.coeff, mom)
+        s2 = self.y_sca * self.y_sca
+        res.var = res.var * s2
+        res.first_var = res.first_var * s2[None, :]
+        res.second_var = res.second_var * s2[None, :]
+        res.total_interaction_var = res.total_interaction_var * s2[None, :]
+        res.closed_var = res.closed_var * s2[None, :]
+        res._mats(self.om.d)
+        return res
+
+    def interaction_effects(self, dim_i, dim_j, grid_i, grid_j, nodes, weights=None):
+        """the interaction surface of every response on grid_i x grid_j (Gi x Gj x q), in raw units (times y_sca)"""
+        from . import sensitivity
+        mom = sensitivity.input_moments(self.om, self._t, nodes, weights)
+        return (sensitivity.interaction_effects(self.om, self._t, self.coeff, mom, dim_i, dim_j, grid_i, grid_j)
+                * self.y_sca[None, None, :])
+
     def torch(self):
         """a differentiable torch module of the de-standardised predictor (torch_emulator.TorchEmulator)"""
         from .torch_emulator import TorchEmulator

@@ -57,6 +57,42 @@ class SobolResult:
         self.g = g_dev
 
 
+def _pair_matrix(v, pairs, d):
+    """n_pairs x q -> symmetric d x d x q with a NaN diagonal"""
+    m = np.full((d, d, v.shape[1]), np.nan)
+    m[pairs[:, 0], pairs[:, 1]] = v
+    m[pairs[:, 1], pairs[:, 0]] = v
+    return m
+
+
+class Sobol2Result:
+    """pairs (n_pairs x 2): the pairs i < j of dimensions in the order (0,1), (0,2), .. (0,d-1), (1,2), ..
+    Per pair and response (n_pairs x q), and as symmetric d x d x q matrices with a NaN diagonal (*_mat):
+    second_var = Var E[f | x_i, x_j] - V1_i - V1_j, the pure second-order variance; total_interaction_var, the
+    variances of all subsets that hold both i and j (superset importance); second, total_interaction: their
+    shares of var (NaN where var == 0).  closed_var (n_pairs x q) = V1_i + V1_j + second_var = Var E[f | x_i, x_j].
+    var (q) and first_var (d x q) are those of sobol; G: the packed G_ij on the device (interaction surfaces)."""
+
+    def __init__(self, out, d, G_dev, first):
+        q = out.shape[0]
+        self.pairs = np.array([(i, j) for i in range(d) for j in range(i + 1, d)], dtype=np.int64).reshape(-1, 2)
+        n_pairs = len(self.pairs)
+        self.var, self.first_var = first.var, first.first_var
+        self.second_var = np.ascontiguousarray(out[:, :n_pairs].T).reshape(n_pairs, q)
+        self.total_interaction_var = np.ascontiguousarray(out[:, n_pairs:].T).reshape(n_pairs, q)
+        i, j = self.pairs[:, 0], self.pairs[:, 1]
+        self.closed_var = self.first_var[i] + self.first_var[j] + self.second_var
+        with np.errstate(divide="ignore", invalid="ignore"):
+            v = np.where(self.var == 0.0, np.nan, self.var)
+            self.second, self.total_interaction = self.second_var / v, self.total_interaction_var / v
+        self.G = G_dev
+        self._mats(d)
+
+    def _mats(self, d):
+        for name in ("second_var", "total_interaction_var", "second", "total_interaction"):
+            setattr(self, name + "_mat", _pair_matrix(getattr(self, name), self.pairs, d))
+
+
 def _check_nodes(om, nodes, weights):
     nodes = np.asarray(nodes, dtype=np.float64)
     if nodes.ndim != 2 or nodes.shape[1] != om.d:
@@ -151,3 +187,54 @@ def main_effects(om, terms, Theta, moments, dim, grid):
     call("obhip_main_effect_dev", om._h, t._h, int(dim), res.g.data_ptr(), q, dz.data_ptr(), G, out.data_ptr())
     out -= torch.from_numpy(res.mean).to(dev)[:, None]
     return out.cpu().numpy().T
+
+
+def sobol2(om, terms, Theta, moments):
+    """Sobol2Result of the responses Theta (p x q, or p) under the measure of `moments`: which inputs matter
+    together -- obhip_sobol2_dev, and sobol for var and the first-order variances."""
+    t = obmod._terms_of(om, terms)
+    Theta = _check_theta(t, Theta)
+    first = sobol(om, t, Theta, moments)
+    torch, dev = _device()
+    q, d = Theta.shape[1], t.d
+    npairs, nG, wsb = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    call("obhip_sobol2_layout", t._h, C.byref(npairs), C.byref(nG))
+    call("obhip_sobol2_workspace_bytes", t.p, d, q, C.byref(wsb))
+    dth = torch.from_numpy(np.ascontiguousarray(Theta.T)).to(dev)
+    ws = torch.empty(wsb.value, dtype=torch.uint8, device=dev)
+    out = torch.empty((q, 2 * npairs.value), dtype=torch.float64, device=dev)
+    G = torch.empty((q, nG.value), dtype=torch.float64, device=dev)
+    call("obhip_sobol2_dev", t._h, dth.data_ptr(), q, moments.mean_dev.data_ptr(), moments.cov_dev.data_ptr(),
+         out.data_ptr() if npairs.value else None, G.data_ptr() if nG.value else None, ws.data_ptr(), wsb.value)
+    torch.cuda.synchronize()
+    return Sobol2Result(out.cpu().numpy(), d, G, first)
+
+
+def interaction_effects(om, terms, Theta, moments, dim_i, dim_j, grid_i, grid_j):
+    """E[f | x_i = z, x_j = z'] - E[f | x_i = z] - E[f | x_j = z'] + E[f] on grid_i (Gi) x grid_j (Gj), Gi x Gj x q:
+    the two-input interaction surface of every response, both main effects and the mean taken off."""
+    t = obmod._terms_of(om, terms)
+    Theta = _check_theta(t, Theta)
+    grid_i = np.ascontiguousarray(grid_i, dtype=np.float64)
+    grid_j = np.ascontiguousarray(grid_j, dtype=np.float64)
+    if grid_i.ndim != 1 or grid_j.ndim != 1:
+        raise ValueError("grid_i and grid_j must be vectors")
+    dim_i, dim_j = int(dim_i), int(dim_j)
+    if not (0 <= dim_i < t.d and 0 <= dim_j < t.d):
+        raise ValueError("dim_i or dim_j out of range (0-based)")
+    if dim_i == dim_j:
+        raise ValueError("dim_i and dim_j must differ")
+    q, Gi, Gj = Theta.shape[1], grid_i.shape[0], grid_j.shape[0]
+    if Gi * Gj == 0:
+        return np.zeros((Gi, Gj, q))
+    res = sobol2(om, t, Theta, moments)
+    mi = main_effects(om, t, Theta, moments, dim_i, grid_i)                     # Gi x q, mu taken off
+    mj = main_effects(om, t, Theta, moments, dim_j, grid_j)
+    mu = sobol(om, t, Theta, moments).mean
+    torch, dev = _device()
+    dzi, dzj = torch.from_numpy(grid_i).to(dev), torch.from_numpy(grid_j).to(dev)
+    out = torch.empty((q, Gi, Gj), dtype=torch.float64, device=dev)
+    call("obhip_interaction_effect_dev", om._h, t._h, dim_i, dim_j, res.G.data_ptr(), q, dzi.data_ptr(), Gi,
+         dzj.data_ptr(), Gj, out.data_ptr())
+    surf = out.cpu().numpy().transpose(1, 2, 0)
+    return surf - mi[:, None, :] - mj[None, :, :] - mu[None, None, :]
