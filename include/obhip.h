@@ -1175,6 +1175,55 @@ int obhip_predictor_var(obhip_predictor *p, double *out);
 int obhip_predictor_gradmean(obhip_predictor *p, double *out);
 int obhip_predictor_d(const obhip_predictor *p, uint64_t *d); /* input dimensions of its model */
 
+/* ---- product of two input blocks (no reference counterpart) -----------------------------------
+ * The emulator at every pair (row i of xa, row j of xb): the dimensions dims_b (0-based, strictly
+ * ascending, 1 <= ndims_b <= d - 1) take their inputs from xb (nb rows, one column per entry of
+ * dims_b, in that order), all other dimensions, ascending, from xa (na rows).  In the notation of
+ * obhip_predict_grad_dev a design-matrix entry is s prod_{l: t_kl > 0} r_{l,t_kl}, a product over
+ * the dimensions, so with A the dimensions of xa and B those of xb
+ *     mean[i, j] = sA_i sB_j sum_k theta_k U_ik V_jk
+ *     var[i, j]  = sA_i^2 sB_j^2 sum_k c_k U_ik^2 V_jk^2 + e^{2 sigma}    (obhip_predict_dev's diagonal form)
+ *     U_ik = prod_{l in A, t_kl > 0} r_{l,t_kl}(xa_i)      sA_i = prod_{l in A} R_l0(xa_i)     (V, sB likewise)
+ * : a matrix product with inner dimension p whose operands are formed from two basis tiles on the
+ * fly, on the matrix cores.  The na nb rows of the full-width input are never written.  Term sets
+ * whose two side tiles do not fit the kernel's LDS (obhip_product_layout reports it), and
+ * OBHIP_FORCE_GENERIC, are expanded in bounded row chunks and go through obhip_predict_multi_dev.
+ * OBHIP_ERR_INVALID before any device call, nothing written: a dims_b entry out of range, repeated
+ * or unsorted; lda < na; d_var without d_coeffvar.  na = 0 or nb = 0: nothing to do. */
+/* host only: the used basis columns of the two sides (the ones column counted on both:
+ * mu_a + mu_b = used columns of the terms + 1) and whether the fused kernel takes the split */
+int obhip_product_layout(const obhip_terms *t, const uint32_t *dims_b, uint64_t ndims_b,
+                         uint64_t *mu_a, uint64_t *mu_b, int *fused);
+/* d_mean[(r nb + j) lda + i], r < q: response r (column r of d_Theta, p x q with leading dimension
+ * p) at the pair (i, j); d_var[j lda + i] (may be NULL, needs d_coeffvar): the variance, the same for
+ * every response in standardised units.  d_xa na x |A|, d_xb nb x |B|, column-major without padding. */
+int obhip_predict_product_dev(const obhip_model *m, const obhip_terms *t, const double *d_Theta,
+                              uint64_t q, const uint32_t *dims_b, uint64_t ndims_b,
+                              const double *d_xa, uint64_t na, const double *d_xb, uint64_t nb,
+                              double *d_mean, uint64_t lda, const double *d_coeffvar, double sigma,
+                              double *d_var);
+/* The sums of a Gaussian likelihood of field data y (na, standardised) at the settings xa for every
+ * candidate row of xb, one response: with r_ij = y_i - mean_ij and v_ij = var_ij + obsvar_i (var_ij
+ * = e^{2 sigma} without d_coeffvar, obsvar_i = 0 without d_obsvar) d_out (nb x 2, column-major) =
+ * [chi2_j = sum_i r_ij^2 / v_ij, logdet_j = sum_i log v_ij].  The na x nb matrices are not written;
+ * the sums run in a fixed order without atomics: two calls give the same bits.  A negative or
+ * non-finite d_obsvar entry is found on the device: OBHIP_ERR_NUMERIC, d_out untouched. */
+int obhip_product_loglik_dev(const obhip_model *m, const obhip_terms *t, const double *d_theta,
+                             const uint32_t *dims_b, uint64_t ndims_b, const double *d_xa,
+                             uint64_t na, const double *d_y, const double *d_obsvar,
+                             const double *d_xb, uint64_t nb, const double *d_coeffvar, double sigma,
+                             double *d_out);
+/* host-buffer forms like obhip_predict_multi: xa, xb with leading dimensions ldxa, ldxb; they refuse
+ * a negative or non-finite obsvar with OBHIP_ERR_INVALID before any device call */
+int obhip_predict_product(const obhip_model *m, const obhip_terms *t, const double *Theta, uint64_t q,
+                          const uint32_t *dims_b, uint64_t ndims_b, const double *xa, uint64_t na,
+                          uint64_t ldxa, const double *xb, uint64_t nb, uint64_t ldxb, double *mean,
+                          uint64_t lda, const double *coeffvar, double sigma, double *var);
+int obhip_product_loglik(const obhip_model *m, const obhip_terms *t, const double *theta,
+                         const uint32_t *dims_b, uint64_t ndims_b, const double *xa, uint64_t na,
+                         uint64_t ldxa, const double *y, const double *obsvar, const double *xb,
+                         uint64_t nb, uint64_t ldxb, const double *coeffvar, double sigma, double *out);
+
 /* ---- synthetic workload of BASELINE.md section 3 (benchmark input) ------ */
 /* rows [row0, row0+n) of the counter-based SplitMix64 stream; d_x is n x d
  * column-major, d_y n (raw, not standardised).  kinds: d entries. */

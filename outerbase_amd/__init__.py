@@ -19,6 +19,7 @@ from .sensitivity import (InputMoments, Sobol2Result, SobolResult, input_moments
                           sobol, sobol2, uniform_nodes)
 from .design import AcquireResult, DesignResult, Posterior, ThompsonResult
 from .torch_emulator import TorchEmulator
+from .product import CalibrationLoglik, predict_product, product_layout, product_loglik
 from .driver import HotPath, MultiHotPath
 from .stream import (CVResult, NewtonAccumulator, cv_folds, cv_newton_multi, design_dx,
                      fit_newton_grad)
@@ -37,4 +38,5 @@ __all__ = [
     "Posterior", "DesignResult", "ThompsonResult", "AcquireResult",
     "InputMoments", "SobolResult", "input_moments", "uniform_nodes", "sobol", "main_effects",
     "Sobol2Result", "sobol2", "interaction_effects",
+    "predict_product", "product_loglik", "product_layout", "CalibrationLoglik",
 ]

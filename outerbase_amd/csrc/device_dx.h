@@ -191,6 +191,28 @@ __device__ __forceinline__ void build_tile(const DimDesc *__restrict__ dims, con
   part[wave * kTileRows + store.lane] = sc;
 }
 
+// build_tile for one side of a product of two input blocks (kernels_product.hip): the dimensions
+// side[0 .. nside) instead of 0 .. d, column s of x holding dimension side[s]; the wave takes the
+// entries slot, slot + WAVES, ... (slot: its place in the round the caller deals the two sides' dimensions
+// in).  store.cpos maps the compact columns of the side's dimensions to the side's own used columns, so the
+// row scale that lands in part[wave][64] is the product of R_l0 over this side's dimensions only.
+template <int WAVES, int PITCH>
+__device__ __forceinline__ void build_tile_side(const DimDesc *__restrict__ dims, const double *__restrict__ ka,
+                                                const double *__restrict__ kb, const double *__restrict__ kc,
+                                                const double *__restrict__ rot, const double *__restrict__ tab,
+                                                const int *__restrict__ side, int nside,
+                                                const double *__restrict__ x, uint64_t ldx, uint64_t row, bool valid,
+                                                int wave, int slot, const StoreTile<PITCH> &store, double *part) {
+  double sc = 1.0;
+  for (int s = slot; s < nside; s += WAVES) {
+    const DimDesc D = dims[side[s]];
+    const double xv = valid ? x[(uint64_t)s * ldx + row] : 0.5;
+    sc *= build_dim_any(D, ka, kb, kc, rot, tab, xv, store);
+  }
+  if (wave == 0) store.tile[store.lane] = 1.0;  // used column 0 = all ones
+  part[wave * kTileRows + store.lane] = sc;
+}
+
 // the row scale of this lane's row: the waves' shares multiplied in wave order
 template <int WAVES>
 __device__ __forceinline__ double tile_scale(const double *part, int lane) {

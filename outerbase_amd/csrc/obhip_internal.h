@@ -379,6 +379,19 @@ struct obhip_terms {
   // and per pair of dimensions i < j, in the order (0,1), (0,2), .. (0,d-1), (1,2), ..: i, j and the
   // offset of G_ij in a packed G ([d (d - 1) / 2][3] ints)
   obhip::DevBuf<int> sobol_pairs;
+  // product of two input blocks (product.cpp, kernels_product.hip): the tables of the last split
+  // (dims_b) asked for, against the column layout `cap`.  Each side has its own used columns (0 = the
+  // ones column, then the used levels of its dimensions in ascending (dimension, level) order).
+  struct Product {
+    std::vector<uint32_t> dims_b;      // key: the split ...
+    std::vector<int64_t> cap;          // ... and the level caps of pred_md the compact columns refer to
+    uint64_t mu_a = 0, mu_b = 0;       // used columns of the sides
+    uint64_t wa = 0, wb = 0;           // padded widths of the sides' column lists (even, >= 2)
+    obhip::DevBuf<int> side_a, side_b;       // the sides' dimensions (A ascending, B in the order of dims_b)
+    obhip::DevBuf<int> dim_src;              // d: column s of xa as s, column s of xb as -(s + 1)
+    obhip::DevBuf<int32_t> cpos_a, cpos_b;   // compact column -> the side's used column or -1 (Mc each)
+    obhip::DevBuf<uint16_t> cols_a, cols_b;  // p x wa, p x wb: right-aligned, padded with column 0
+  } product;
   int prepare(const std::vector<int64_t> &cap, const std::vector<obhip::DimDesc> &dims);
 };
 
@@ -714,6 +727,41 @@ bool predict_multi_supports(const obhip_terms &t);
 int launch_theta_term_major(const double *d_Theta, uint64_t p, int qc, uint64_t qw, double *d_T);
 int launch_predict_multi(const obhip_model &m, obhip_terms &t, const double *d_Theta, uint64_t q,
                          const double *d_x, uint64_t n, double *d_mean);
+// kernels_product.hip / product.cpp: the predictor on the product of two input blocks (include/obhip.h,
+// "product of two input blocks").  One call of the fused kernel or of the row route:
+struct ProductCall {
+  const double *theta = nullptr;     // p x q, leading dimension p
+  uint64_t q = 1;
+  const double *xa = nullptr, *xb = nullptr;  // na x |A|, nb x |B|, column-major without padding
+  uint64_t na = 0, nb = 0;
+  const double *coeffvar = nullptr;  // p or null
+  double sigma = 0.0;
+  double *mean = nullptr;            // store epilogue: mean[(r nb + j) lda + i] ...
+  uint64_t lda = 0;
+  double *var = nullptr;             // ... and var[j lda + i] (needs coeffvar)
+  const double *y = nullptr, *obsvar = nullptr;  // likelihood epilogue (mean == nullptr, q == 1): ...
+  double *part = nullptr;            // ... part[(w tiles_a + A tile) nb + j], w = 0: sum r^2 / v, 1: sum log v
+};
+constexpr uint64_t kProductTile = 64;  // rows of a side per workgroup (= kTileRows)
+size_t predict_product_lds(uint64_t mu_a, uint64_t mu_b, uint64_t wa, uint64_t wb);
+// the fused kernel's domain: both side tiles and the staging within kLdsBudget, column lists of even width
+bool predict_product_supports(uint64_t mu_a, uint64_t mu_b, uint64_t wa, uint64_t wb);
+// t.product and t.pred_md are prepared for the split (product.cpp: ensure_product_tables)
+int launch_predict_product(const obhip_model &m, obhip_terms &t, const ProductCall &c);
+// rows [j0, j0 + nj) x [i0, i0 + ni) of the product as full-width rows: d_X[l rows + (j - j0) ni + (i - i0)]
+int launch_product_expand(const obhip_terms &t, const double *d_xa, uint64_t na, const double *d_xb, uint64_t nb,
+                          uint64_t i0, uint64_t ni, uint64_t j0, uint64_t nj, double *d_X);
+// d_mean[(r nb + j0 + jj) lda + i0 + ii] = d_src[r rows + jj ni + ii], r < q
+int launch_product_scatter(const double *d_src, uint64_t q, uint64_t nb, uint64_t lda, uint64_t i0, uint64_t ni,
+                           uint64_t j0, uint64_t nj, double *d_dst);
+// the likelihood terms of a chunk of rows (d_var null: e2sigma), reduced per A tile in the fused kernel's order
+int launch_product_lik_rows(const double *d_mean, const double *d_var, double e2sigma, const double *d_y,
+                            const double *d_obsvar, uint64_t na, uint64_t nb, uint64_t i0, uint64_t ni, uint64_t j0,
+                            uint64_t nj, double *d_part);
+// d_out[w nb + j] = the partials of the A tiles added in ascending order
+int launch_product_sum_tiles(const double *d_part, uint64_t tiles_a, uint64_t nb, double *d_out);
+// *bad_out != 0: an entry of d_v (n) is negative or not finite (waits for the device)
+int launch_check_nonneg(const double *d_v, uint64_t n, int *bad_out);
 // kernels_glm.hip: the row pass between two Newton steps of the GLM fit (glm.cpp) and the response scale
 // of its predictor.  eta_i = (eta ? eta[i] : o ? o[i] : 0) + (deta ? alpha deta[i] : 0); scale, scale_w and
 // u have n rounded up to a multiple of 64 entries; scale_w == nullptr: a trial pass, only the sums

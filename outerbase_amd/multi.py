@@ -194,6 +194,55 @@ class MultiFit:
         return (sensitivity.interaction_effects(self.om, self._t, self.coeff, mom, dim_i, dim_j, grid_i, grid_j)
                 * self.y_sca[None, None, :])
 
+    def predict_product(self, xa, xb, dims_b, var=False):
+        """De-standardised mean (na x nb x q) at every pair (xa[i], xb[j]): the dimensions dims_b (0-based,
+        ascending) take their inputs from xb, the others from xa (product.predict_product; the na nb
+        full-width rows are never written).  With var=True also the variance (na x nb x q), scaled by
+        y_sca^2 as predict scales it."""
+        from . import product
+        xa, xb, db = product.check_blocks(self.om.d, xa, xb, dims_b)
+        na, nb, q = xa.shape[0], xb.shape[0], self.q
+        if na == 0 or nb == 0:
+            z = np.zeros((na, nb, q))
+            return (z, z.copy()) if var else z
+        mean, v = product.predict_product_dev(self.om, self._t, self.coeff, xa, xb, db,
+                                              1.0 / self.diagH if var else None, self.sigma)
+        mean = mean.permute(2, 1, 0).cpu().numpy() * self.y_sca[None, None, :] + self.y_cent[None, None, :]
+        if not var:
+            return mean
+        return mean, v.cpu().numpy().T[:, :, None] * (self.y_sca * self.y_sca)[None, None, :]
+
+    def calibration_loglik(self, x_field, y_field, t_cand, dims_t, obs_var=None, response=0, emulator_var=True):
+        """Gaussian log-likelihood of the field data y_field (na, raw units) observed at the settings x_field
+        (na x the dimensions not in dims_t) for every candidate t_cand[j] (nb x len(dims_t)) of the
+        dimensions dims_t, under the emulator of one response:
+            r_ij = y_i - mean_ij,  v_ij = emulator variance_ij (emulator_var; else its noise term) + obs_var_i
+            loglik_j = -(chi2_j + logdet_j) / 2 - (na / 2) log 2 pi,  chi2 = sum_i r^2 / v,  logdet = sum_i log v.
+        obs_var: na variances in raw units (or one for all rows; None: 0).  Returns a CalibrationLoglik with
+        loglik, chi2, logdet (nb each).  The sums are formed on the device tile by tile
+        (obhip_product_loglik_dev); the na x nb matrices are never written."""
+        from . import product
+        x_field, t_cand, _ = product.check_blocks(self.om.d, x_field, t_cand, dims_t)
+        if not (isinstance(response, (int, np.integer)) and 0 <= response < self.q):
+            raise ValueError("response must be in 0 .. q - 1")
+        y = np.asarray(y_field, dtype=np.float64)
+        na = x_field.shape[0]
+        if y.shape != (na,):
+            raise ValueError("y_field must have one entry per row of x_field")
+        cent, sca = self.y_cent[response], self.y_sca[response]
+        ov = None
+        if obs_var is not None:
+            ov = np.broadcast_to(np.asarray(obs_var, dtype=np.float64), (na,)) if np.ndim(obs_var) == 0 \
+                else np.asarray(obs_var, dtype=np.float64)
+            if ov.shape != (na,):
+                raise ValueError("obs_var must be a number or have one entry per row of x_field")
+            ov = ov / (sca * sca)
+        chi2, logdet = product.product_loglik(self.om, self._t, self.coeff[:, response], x_field, (y - cent) / sca,
+                                              t_cand, dims_t, obsvar=ov,
+                                              coeffvar=1.0 / self.diagH if emulator_var else None, sigma=self.sigma)
+        logdet = logdet + 2.0 * na * math.log(sca)
+        return product.CalibrationLoglik(-0.5 * (chi2 + logdet) - 0.5 * na * math.log(2.0 * math.pi), chi2, logdet)
+
     def torch(self):
         """a differentiable torch module of the de-standardised predictor (torch_emulator.TorchEmulator)"""
         from .torch_emulator import TorchEmulator

@@ -1,0 +1,153 @@
+"""Prediction on the product of two input blocks and the calibration likelihood built on it.
+
+The emulator at every pair (row i of xa, row j of xb): the dimensions dims_b take their inputs from xb, all
+others from xa.  Field settings x candidate parameters (calibration), control x environment (robust design),
+grid x data rows (slices, ICE curves).  The na nb full-width rows are never written: a design-matrix entry is
+a product over the dimensions, so the pair's mean is a matrix product of two on-the-fly operands
+(include/obhip.h, "product of two input blocks").
+
+torch holds the device memory; all arithmetic is in libobhip.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import obmod
+from ._lib import call
+
+
+def check_dims_b(d, dims_b):
+    """dims_b as uint32: 0-based, strictly ascending, 1 to d - 1 entries below d"""
+    db = np.asarray(dims_b)
+    if db.ndim != 1 or db.size < 1 or db.size > d - 1 or not np.issubdtype(db.dtype, np.integer):
+        raise ValueError("dims_b must name 1 to d - 1 dimensions (0-based integers)")
+    if db.min() < 0 or db.max() >= d:
+        raise ValueError("dims_b entry out of range")
+    if np.any(np.diff(db) <= 0):
+        raise ValueError("dims_b must be strictly ascending")
+    return np.ascontiguousarray(db, dtype=np.uint32)
+
+
+def check_blocks(d, xa, xb, dims_b):
+    db = check_dims_b(d, dims_b)
+    xa = np.asarray(xa, dtype=np.float64)
+    xb = np.asarray(xb, dtype=np.float64)
+    if xa.ndim != 2 or xa.shape[1] != d - db.size:
+        raise ValueError("xa must be na x (d - len(dims_b))")
+    if xb.ndim != 2 or xb.shape[1] != db.size:
+        raise ValueError("xb must be nb x len(dims_b)")
+    return xa, xb, db
+
+
+def product_layout(om, terms, dims_b):
+    """(mu_a, mu_b, fused): the used basis columns of the two sides and whether the fused kernel takes the
+    split (obhip_product_layout; host only)"""
+    t = obmod._terms_of(om, terms)
+    db = check_dims_b(om.d, dims_b)
+    ma, mb, fu = C.c_uint64(0), C.c_uint64(0), C.c_int(0)
+    call("obhip_product_layout", t._h, db.ctypes.data, db.size, C.byref(ma), C.byref(mb), C.byref(fu))
+    return ma.value, mb.value, bool(fu.value)
+
+
+def _device():
+    import torch
+    call("obhip_set_stream", C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _cols(a, dev):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a.T)).to(dev)  # column-major
+
+
+def predict_product_dev(om, t, Theta, xa, xb, db, coeffvar, sigma):
+    """device tensors (mean q x nb x na, var nb x na or None) in standardised units"""
+    import torch
+    dev = _device()
+    p, q = Theta.shape
+    na, nb = xa.shape[0], xb.shape[0]
+    mean = torch.empty((q, nb, na), dtype=torch.float64, device=dev)
+    var = dcv = None
+    if coeffvar is not None:
+        dcv = torch.from_numpy(np.ascontiguousarray(coeffvar, dtype=np.float64)).to(dev)
+        var = torch.empty((nb, na), dtype=torch.float64, device=dev)
+    dxa, dxb, dth = _cols(xa, dev), _cols(xb, dev), _cols(Theta, dev)
+    call("obhip_predict_product_dev", om._h, t._h, dth.data_ptr(), q, db.ctypes.data, db.size, dxa.data_ptr(), na,
+         dxb.data_ptr(), nb, mean.data_ptr(), na, None if dcv is None else dcv.data_ptr(), sigma,
+         None if var is None else var.data_ptr())
+    return mean, var
+
+
+def predict_product(om, terms, Theta, xa, xb, dims_b, coeffvar=None, sigma=None):
+    """mean (na, nb, q) of the q coefficient vectors Theta (p x q, or p) at every pair (xa[i], xb[j]); with
+    coeffvar (p) also the variance (na, nb) of the diagonal form B^2 coeffvar + e^{2 sigma}, returned as
+    (mean, var).  Standardised units.  sigma=None: log(0.01)."""
+    t = obmod._terms_of(om, terms)
+    xa, xb, db = check_blocks(om.d, xa, xb, dims_b)
+    Theta = np.asarray(Theta, dtype=np.float64)
+    if Theta.ndim == 1:
+        Theta = Theta[:, None]
+    if Theta.ndim != 2 or Theta.shape[0] != t.p or Theta.shape[1] == 0:
+        raise ValueError("Theta must be p x q")
+    if coeffvar is not None:
+        coeffvar = np.asarray(coeffvar, dtype=np.float64)
+        if coeffvar.shape != (t.p,):
+            raise ValueError("coeffvar must have p entries")
+    if sigma is None:
+        sigma = math.log(0.01)
+    na, nb, q = xa.shape[0], xb.shape[0], Theta.shape[1]
+    if na == 0 or nb == 0:
+        z = np.zeros((na, nb, q))
+        return z if coeffvar is None else (z, np.zeros((na, nb)))
+    mean, var = predict_product_dev(om, t, Theta, xa, xb, db, coeffvar, float(sigma))
+    mean = mean.permute(2, 1, 0).cpu().numpy()
+    return mean if var is None else (mean, var.cpu().numpy().T)
+
+
+class CalibrationLoglik:
+    """loglik, chi2 = sum_i r_ij^2 / v_ij and logdet = sum_i log v_ij per candidate j, in raw units"""
+
+    def __init__(self, loglik, chi2, logdet):
+        self.loglik, self.chi2, self.logdet = loglik, chi2, logdet
+
+
+def product_loglik(om, terms, theta, xa, y, xb, dims_b, obsvar=None, coeffvar=None, sigma=None):
+    """(chi2, logdet), nb each, of the standardised field data y (na) at the settings xa for every candidate
+    row of xb: r = y - mean, v = var + obsvar (var = e^{2 sigma} without coeffvar) -- obhip_product_loglik_dev"""
+    import torch
+    t = obmod._terms_of(om, terms)
+    xa, xb, db = check_blocks(om.d, xa, xb, dims_b)
+    theta = np.asarray(theta, dtype=np.float64)
+    if theta.shape != (t.p,):
+        raise ValueError("theta must have p entries")
+    y = np.asarray(y, dtype=np.float64)
+    na, nb = xa.shape[0], xb.shape[0]
+    if y.shape != (na,):
+        raise ValueError("y must have one entry per row of xa")
+    if not np.all(np.isfinite(y)):
+        raise ValueError("y must be finite")
+    if obsvar is not None:
+        obsvar = np.asarray(obsvar, dtype=np.float64)
+        if obsvar.shape != (na,):
+            raise ValueError("obsvar must have one entry per row of xa")
+        if not np.all(np.isfinite(obsvar)) or np.any(obsvar < 0):
+            raise ValueError("obsvar must be finite and not negative")
+    if coeffvar is not None:
+        coeffvar = np.asarray(coeffvar, dtype=np.float64)
+        if coeffvar.shape != (t.p,):
+            raise ValueError("coeffvar must have p entries")
+    if sigma is None:
+        sigma = math.log(0.01)
+    if na == 0 or nb == 0:
+        return np.zeros(nb), np.zeros(nb)
+    dev = _device()
+    vec = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    dth, dy, dov, dcv = vec(theta), vec(y), vec(obsvar), vec(coeffvar)
+    dxa, dxb = _cols(xa, dev), _cols(xb, dev)
+    out = torch.empty((2, nb), dtype=torch.float64, device=dev)
+    call("obhip_product_loglik_dev", om._h, t._h, dth.data_ptr(), db.ctypes.data, db.size, dxa.data_ptr(), na,
+         dy.data_ptr(), None if dov is None else dov.data_ptr(), dxb.data_ptr(), nb,
+         None if dcv is None else dcv.data_ptr(), float(sigma), out.data_ptr())
+    out = out.cpu().numpy()
+    return out[0].copy(), out[1].copy()
