@@ -918,6 +918,63 @@ int obhip_predict_vjp_multi_dev(const obhip_model *m, const obhip_terms *t, cons
 int obhip_predict_jac_multi(const obhip_model *m, const obhip_terms *t, const double *Theta,
                             uint64_t q, const double *x, uint64_t n, uint64_t ldx, double *mean,
                             double *jac);
+/* Hessian-vector and Jacobian-vector product of the multi-response predictor by the inputs, for one
+ * direction per row (row i of V is v).  The reference has no counterpart.  Notation of
+ * obhip_predict_grad_dev, per row, standardised units; with R''_l = (d2cov_l/dx_l^2) . rotmat_l
+ *   kappa_l = R''_l0 / R_l0        r''_lt = (R''_lt - 2 r'_lt R'_l0 - r_lt R''_l0) / R_l0   (t >= 1)
+ * d2cov/dx2, with k'(h) = -(1/3) h (1 + |h|) e^{-|h|} and k''(h) = -(1/3) (1 + |h| - h^2) e^{-|h|}:
+ *   mat25     u = x / e^{2 th0}:                                       k''(h) / e^{4 th0}
+ *   mat25pow  a = e^{th1/4}, t = x^a / e^{2 th0 + th1/4}, dt/dx = a t / x, d2t/dx2 = a (a - 1) t / x^2:
+ *             k''(h) (dt/dx)^2 + k'(h) d2t/dx2
+ *   mat25ang  cx = cos x / e^{2 th0}, sx = sin x / e^{2 th1}, q = hs cx - hc sx,
+ *             q' = cx^2 + sx^2 - hs sin x / e^{2 th0} - hc cos x / e^{2 th1}:
+ *             -(1/3) e^{-h} ((1 + h) q' - q^2)                         -- nothing divides by h
+ * For response j with the coefficients Theta[:, j], E_klm = P_k without the factors of l and m:
+ *   rho.v     = sum_l v_l rho_l
+ *   S_j       = sum_k Theta_kj P_k
+ *   Sd_j      = sum_k Theta_kj sum_{m: t_km > 0} v_m E_km r'_m,t
+ *   g_lj      = sum_{k: t_kl > 0} Theta_kj E_kl r'_l,t
+ *   h_lj      = sum_{k: t_kl > 0} Theta_kj (v_l E_kl r''_l,t + r'_l,t sum_{m != l: t_km > 0} v_m E_klm r'_m,t)
+ *   mean_ij   = s S_j
+ *   jvp_ij    = sum_l v_l dmean_ij/dx_l = s ((rho.v) S_j + Sd_j)
+ *   (H_j v)_l = sum_m v_m d2mean_ij/dx_l dx_m
+ *             = s ((rho_l (rho.v) + v_l (kappa_l - rho_l^2)) S_j + rho_l Sd_j + (rho.v) g_lj + h_lj)
+ *   hvp_il    = sum_j W_ij (H_j v)_l          vjp_il = sum_j W_ij s (rho_l S_j + g_lj)
+ * Per (row, term) O(f) multiplies through products of (value, directional derivative) pairs; no d x d
+ * block is formed.  One fused kernel per chunk of responses (blocks of 16, at most 32): per 32-row
+ * tile the basis with both derivatives is evaluated once, S and Sd come from one dense pass and
+ * (rho.v) g_l + h_l (and g_l when d_vjp is passed) from one pass per dimension over its view, all
+ * contracted with Theta on the matrix cores; each finished block is contracted with the tile's rows of
+ * W in response order before it leaves the chip.  Neither the Jacobian nor any n x d x q or n x d x d
+ * array is written, not even as scratch; q = 1 takes the same kernel.  Fused while the tile of
+ * 3 Mu + 3 d columns of 33 doubles, eight blocks of 16 x 33 doubles, 18 x 32 doubles and Mu ints fit
+ * 160 KB of LDS (obhip_predict_hvp_layout); beyond that and under OBHIP_FORCE_GENERIC the same
+ * contraction runs from a pooled HBM tile per block (any term set obhip_predict_grad_dev accepts).  No
+ * atomics and one summation order: two calls give the same bits, and the bits of an output do not
+ * depend on which optional outputs are passed.
+ * d_Theta: p x q column-major, ld = p.  d_x, d_V, d_vjp, d_hvp: n x d column-major, ld = n.  d_mean,
+ * d_jvp: n x q column-major, ld = n.  d_W: n x q column-major, ldw >= n (the padding is not read),
+ * required when d_vjp or d_hvp is passed.  d_mean and d_vjp may be NULL; at least one of d_jvp and
+ * d_hvp is required.  A null m, t, d_Theta, d_x or d_V, q = 0, ldw < n, n > 2^40, neither d_jvp nor
+ * d_hvp, d_vjp or d_hvp without d_W and terms of another model's dimension count return
+ * OBHIP_ERR_INVALID before any device call, nothing written; n = 0 is a no-op.  Runs on the stream
+ * of obhip_set_stream. */
+int obhip_predict_hvp_multi_dev(const obhip_model *m, const obhip_terms *t, const double *d_Theta,
+                                uint64_t q, const double *d_x, uint64_t n, const double *d_W,
+                                uint64_t ldw, const double *d_V, double *d_mean, double *d_vjp,
+                                double *d_jvp, double *d_hvp);
+/* the same on host buffers: x with ldx, W with ldw, the n x d arrays V, vjp and hvp with ldg, mean
+ * and jvp n x q with ld = n */
+int obhip_predict_hvp_multi(const obhip_model *m, const obhip_terms *t, const double *Theta, uint64_t q,
+                            const double *x, uint64_t n, uint64_t ldx, const double *W, uint64_t ldw,
+                            const double *V, uint64_t ldg, double *mean, double *vjp, double *jvp,
+                            double *hvp);
+/* what obhip_predict_hvp_multi_dev will do with these terms and q responses: the used basis columns,
+ * the rows of a tile (32), the LDS bytes of a workgroup of the first launch and whether the tile
+ * lives in LDS (1) or in pooled HBM scratch (0).  From the levels alone; every output may be NULL.
+ * Host only. */
+int obhip_predict_hvp_layout(const obhip_terms *t, uint64_t q, uint64_t *mu, uint64_t *tile_rows,
+                             uint64_t *lds_bytes, int *fused);
 /* predr_std (loglik_std.cpp:218-256), the predictor of the loglik_std model with the full
  * posterior covariance of the coefficients: mean = B theta, var_i = b_i^T inv(H) b_i +
  * e^{2 sigma} (:249-256; the reference uses arma::inv; here H = L L^T by the library's own

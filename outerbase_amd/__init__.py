@@ -10,8 +10,8 @@ from . import _lib
 from ._lib import ObhipError, device_count
 from .obmod import (covf, covf_mat25, covf_mat25ang, covf_mat25pow, gethyp, getpara, hypnames,
                     listcov, loglik_gauss, loglik_gda, loglik_std, logpr_gauss, lpdf, lpdfvec,
-                    outerbase, outermod, predict_grad, predict_jac, predict_vjp, predictor, setcovfs, setknot,
-                    term_dim_views)
+                    outerbase, outermod, predict_grad, predict_hess, predict_hvp, predict_jac, predict_vjp,
+                    predictor, setcovfs, setknot, term_dim_views)
 from .fitting import BFGS_lpdf, BFGS_std, obfit, obpred, obpred_grad
 from .multi import MultiFit, fit_newton_multi
 from .glm import GlmFit, fit_glm
@@ -33,7 +33,7 @@ __all__ = [
     "NewtonAccumulator", "cv_newton_multi", "cv_folds", "CVResult",
     "predict_grad", "obpred_grad", "term_dim_views",
     "design_dx", "fit_newton_grad",
-    "predict_jac", "predict_vjp", "TorchEmulator",
+    "predict_jac", "predict_vjp", "predict_hvp", "predict_hess", "TorchEmulator",
     "GlmFit", "fit_glm",
     "Posterior", "DesignResult", "ThompsonResult", "AcquireResult",
     "InputMoments", "SobolResult", "input_moments", "uniform_nodes", "sobol", "main_effects",

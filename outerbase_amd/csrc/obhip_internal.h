@@ -361,6 +361,11 @@ struct obhip_terms {
     const obhip_model *tab_model = nullptr;
     uint64_t tab_version = ~0ull;
     std::vector<int64_t> tab_cap;
+    // second-derivative interval tables (predict_hvp.cpp): the layout of dtab, the sums of d2k/du2
+    obhip::DevBuf<double> d2tab;
+    const obhip_model *tab2_model = nullptr;
+    uint64_t tab2_version = ~0ull;
+    std::vector<int64_t> tab2_cap;
     // staging of the derivative design matrix (kernels_materialize_dx.hip): used column -> dimension
     obhip::DevBuf<int32_t> udim;     // Mu (-1: the ones column)
     std::vector<int64_t> udim_cap;   // column layout it was made for
@@ -863,7 +868,7 @@ int launch_prod(Kernel kernel, dim3 grid, dim3 block, size_t lds, const ProdTabs
 }
 
 // ---- what the fused predictors share on the host -------------------------------------------------
-// (kernels_predict, _star, _multi, _predict_dx, _materialize_dx, _predict_jac)
+// (kernels_predict, _star, _multi, _predict_dx, _materialize_dx, _predict_jac, _predict_hvp)
 int ensure_dx_tables(const obhip_model &m, obhip_terms &t);  // predict_dx.cpp; after t.prepare(t.pred_md.cap, ...)
 // Before any of their launches: the device view of the model capped at the terms' levels (rebuilt when
 // the model or its state changed), the term tables packed against its column layout and, with_dx, the
@@ -920,6 +925,15 @@ int launch_predict_dx(const obhip_model &m, obhip_terms &t, const double *d_thet
 bool predict_jac_supports(const obhip_terms &t);
 int launch_predict_jac(const obhip_model &m, obhip_terms &t, const double *d_Theta, uint64_t q, const double *d_x,
                        uint64_t n, double *d_mean, double *d_jac, const double *d_W, uint64_t ldw, double *d_out);
+// kernels_predict_hvp.hip / predict_hvp.cpp: Hessian-vector and Jacobian-vector product of the
+// multi-response predictor (any q >= 1); the fused kernel's domain and its LDS for NQB blocks of 16 responses
+constexpr int kHvpRows = 32;  // rows of a tile
+size_t predict_hvp_lds(uint64_t Mu, uint64_t d, int nqb, bool hbm);
+bool predict_hvp_supports(const obhip_terms &t);
+int ensure_d2_tables(const obhip_model &m, obhip_terms &t);  // after ensure_dx_stage
+int launch_predict_hvp(const obhip_model &m, obhip_terms &t, const double *d_Theta, uint64_t q, const double *d_x,
+                       uint64_t n, const double *d_W, uint64_t ldw, const double *d_V, double *d_mean, double *d_vjp,
+                       double *d_jvp, double *d_hvp);
 // kernels_materialize_dx.hip / grad_obs.cpp: the derivative design matrix as rows of the normal equations
 struct DxStage {
   const double *x = nullptr;        // device, column-major with leading dimension ldx, n rows from x on

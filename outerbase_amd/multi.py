@@ -152,6 +152,52 @@ class MultiFit:
              dw.data_ptr(), n, None, out.data_ptr())
         return out.cpu().numpy().T
 
+    def hvp(self, xnew, cot, V):
+        """(hvp n x d, jvp n x q) of the de-standardised means for one direction per row (the rows of V):
+        hvp[i, l] = sum_j cot[i, j] sum_m V[i, m] d2 mean_ij / d x_il d x_im and jvp[i, j] =
+        sum_l V[i, l] d mean_ij / d x_il, raw units.  cot (n x q) is scaled by y_sca per response as in
+        vjp and sent through obhip_predict_hvp_multi_dev; no Jacobian and no Hessian is formed."""
+        import torch
+        xnew = np.asarray(xnew, dtype=np.float64)
+        if xnew.ndim != 2 or xnew.shape[1] != self.om.d:
+            raise ValueError("xnew must be n x d")
+        cot, V = np.asarray(cot, dtype=np.float64), np.asarray(V, dtype=np.float64)
+        n, q, d = xnew.shape[0], self.q, self.om.d
+        if cot.shape != (n, q):
+            raise ValueError("cot must be n x q")
+        if V.shape != (n, d):
+            raise ValueError("V must be n x d")
+        if n == 0:
+            return np.zeros((0, d)), np.zeros((0, q))
+        dev, dx, dth = self._dev_inputs(xnew)
+        sca = torch.from_numpy(self.y_sca).to(dev)
+        dw = torch.from_numpy(np.ascontiguousarray(cot.T)).to(dev) * sca[:, None]
+        dv = torch.from_numpy(np.ascontiguousarray(V.T)).to(dev)
+        hv = torch.empty((d, n), dtype=torch.float64, device=dev)
+        jv = torch.empty((q, n), dtype=torch.float64, device=dev)
+        call("obhip_predict_hvp_multi_dev", self.om._h, self._t._h, dth.data_ptr(), q, dx.data_ptr(), n,
+             dw.data_ptr(), n, dv.data_ptr(), None, None, jv.data_ptr(), hv.data_ptr())
+        return hv.cpu().numpy().T, (jv * sca[:, None]).cpu().numpy().T
+
+    def predict_hess(self, xnew, response=0):
+        """The Hessian of one response's de-standardised mean, hess[i, l, m] = d2 mean_i / d x_il d x_im
+        (n x d x d): d hvp calls with unit directions, each evaluating the basis again -- for the few
+        rows of an optimiser or a Laplace approximation, not for 1e6 rows."""
+        xnew = np.asarray(xnew, dtype=np.float64)
+        if xnew.ndim != 2 or xnew.shape[1] != self.om.d:
+            raise ValueError("xnew must be n x d")
+        if not 0 <= int(response) < self.q:
+            raise ValueError("response must be in 0 .. q - 1")
+        n, d = xnew.shape[0], self.om.d
+        cot = np.zeros((n, self.q))
+        cot[:, int(response)] = 1.0
+        hess = np.empty((n, d, d))
+        for m in range(d):
+            V = np.zeros((n, d))
+            V[:, m] = 1.0
+            hess[:, :, m] = self.hvp(xnew, cot, V)[0]
+        return hess
+
     def sobol(self, nodes, weights=None):
         """Sobol indices of every response under the product measure of nodes / weights
         (sensitivity.input_moments), in raw units: SobolResult with mean = y_cent + y_sca mu, the variances

@@ -820,6 +820,54 @@ def predict_vjp(om, terms, Theta, xnew, W):
     return mean.cpu().numpy().T, out.cpu().numpy().T
 
 
+def predict_hvp(om, terms, Theta, xnew, V, W=None):
+    """(hvp, jvp) of q responses with the coefficients Theta (p x q) at the rows xnew (n x d), for one
+    direction per row (the rows of V, n x d): jvp[i, j] = sum_l V[i, l] d mean_ij / d x_il (n x q) and,
+    with the weights W (n x q), hvp[i, l] = sum_j W[i, j] sum_m V[i, m] d2 mean_ij / d x_il d x_im
+    (n x d; None without W).  One fused kernel; neither the Jacobian nor a Hessian is formed
+    (obhip_predict_hvp_multi_dev)."""
+    t = _terms_of(om, terms)
+    x, Theta = _check_multi(om, t, Theta, xnew)
+    V = np.asarray(V, dtype=np.float64)
+    n, q, d = x.shape[0], Theta.shape[1], om.d
+    if V.shape != (n, d):
+        raise ValueError("V must be n x d")
+    if W is not None:
+        W = np.asarray(W, dtype=np.float64)
+        if W.shape != (n, q):
+            raise ValueError("W must be n x q")
+    if n == 0:
+        return (None if W is None else np.zeros((0, d))), np.zeros((0, q))
+    x, Theta, V = np.asfortranarray(x), np.asfortranarray(Theta), np.asfortranarray(V)
+    W = None if W is None else np.asfortranarray(W)
+    jvp = np.empty((q, n))
+    hvp = None if W is None else np.empty((d, n))
+    call("obhip_predict_hvp_multi", om._h, t._h, ptr(Theta), q, ptr(x), n, n, ptr(W), n, ptr(V), n, None, None,
+         ptr(jvp), ptr(hvp))
+    return (None if hvp is None else hvp.T), jvp.T
+
+
+def predict_hess(om, terms, theta, xnew):
+    """The Hessian of the mean of one response with the coefficients theta (p) at the rows xnew:
+    hess[i, l, m] = d2 mean_i / d x_il d x_im (n x d x d).  Column m comes from one predict_hvp call
+    with the unit direction e_m, so the cost is d calls, each of which evaluates the basis again:
+    meant for the few rows of an optimiser, not for 1e6 of them (there, ask for the products)."""
+    theta = _f64(theta)
+    x = np.asarray(xnew, dtype=np.float64)
+    if theta.ndim != 1:
+        raise ValueError("theta must have one entry per term")
+    if x.ndim != 2 or x.shape[1] != om.d:
+        raise ValueError("xnew must be n x d")
+    n, d = x.shape[0], om.d
+    hess = np.empty((n, d, d))
+    ones = np.ones((n, 1))
+    for m in range(d):
+        V = np.zeros((n, d))
+        V[:, m] = 1.0
+        hess[:, :, m] = predict_hvp(om, terms, theta[:, None], x, V, ones)[0]
+    return hess
+
+
 def term_dim_views(om, terms):
     """per dimension the indices of the terms that have it at a level > 0, in term order: the lists
     the gradient kernel sums over (obhip_terms_dimview; host only)"""

@@ -3,8 +3,9 @@
 A multi-output emulator is used for calibration and optimisation over its inputs: a scalar loss of
 all q outputs is differentiated by x.  TorchEmulator wraps a MultiFit so that it can sit inside a
 torch.optim loop: forward is obhip_predict_multi_dev, backward the vector-Jacobian product
-obhip_predict_vjp_multi_dev (include/obhip.h), both on the current stream; the n x d x q Jacobian
-is never formed.  All arithmetic is in libobhip; torch holds the memory and the graph.
+obhip_predict_vjp_multi_dev, the backward of that the Hessian-vector and Jacobian-vector product
+obhip_predict_hvp_multi_dev (include/obhip.h), all on the current stream; neither the n x d x q
+Jacobian nor a Hessian is formed.  All arithmetic is in libobhip; torch holds the memory and the graph.
 """
 import ctypes as C
 
@@ -32,24 +33,65 @@ else:
                 call("obhip_predict_multi_dev", emu._om._h, emu._t._h, emu.theta.data_ptr(), q, xc.data_ptr(), n,
                      mean.data_ptr(), None, emu._sigma, None)
             ctx.emu, ctx.xc = emu, xc
+            ctx.save_for_backward(x)
             return (mean * emu.y_sca[:, None] + emu.y_cent[:, None]).t()
 
         @staticmethod
-        @torch.autograd.function.once_differentiable
         def backward(ctx, grad_output):
-            emu, xc = ctx.emu, ctx.xc
+            x, = ctx.saved_tensors
+            return _PredictVjp.apply(grad_output, x, ctx.xc, ctx.emu), None
+
+    class _PredictVjp(torch.autograd.Function):
+        """the backward of _Predict as a function of (grad_output, x): out = sum_j grad_output_ij y_sca_j
+        d mean_ij / d x (obhip_predict_vjp_multi_dev; xc is x column-major, as the forward left it).
+        Its own backward is _PredictHvp."""
+
+        @staticmethod
+        def forward(ctx, grad_output, x, xc, emu):
             d, n = xc.shape
             out = torch.zeros((d, n), dtype=torch.float64, device=xc.device)
+            w = None
             if n > 0:
                 w = (grad_output.detach().to(torch.float64) * emu.y_sca[None, :]).t().contiguous()   # n x q column-major
                 call("obhip_set_stream", C.c_void_p(torch.cuda.current_stream().cuda_stream))
                 call("obhip_predict_vjp_multi_dev", emu._om._h, emu._t._h, emu.theta.data_ptr(), emu.q, xc.data_ptr(),
                      n, w.data_ptr(), n, None, out.data_ptr())
-            return out.t(), None
+            ctx.emu, ctx.xc, ctx.w = emu, xc, w
+            ctx.save_for_backward(grad_output, x)
+            return out.t()
+
+        @staticmethod
+        def backward(ctx, u):
+            grad_output, x = ctx.saved_tensors
+            gy, gx = _PredictHvp.apply(u, grad_output, x, ctx.xc, ctx.w, ctx.emu)
+            return gy, gx, None, None
+
+    class _PredictHvp(torch.autograd.Function):
+        """the backward of _PredictVjp for the cotangent u (n x d) of its output: one
+        obhip_predict_hvp_multi_dev call with the direction u gives the Hessian-vector product (for x)
+        and jvp . y_sca (for grad_output).  The library has no third derivative: backward raises."""
+
+        @staticmethod
+        def forward(ctx, u, grad_output, x, xc, w, emu):
+            d, n = xc.shape
+            hv = torch.zeros((d, n), dtype=torch.float64, device=xc.device)
+            jv = torch.zeros((emu.q, n), dtype=torch.float64, device=xc.device)
+            if n > 0:
+                v = _colmajor(u.to(torch.float64))
+                call("obhip_set_stream", C.c_void_p(torch.cuda.current_stream().cuda_stream))
+                call("obhip_predict_hvp_multi_dev", emu._om._h, emu._t._h, emu.theta.data_ptr(), emu.q, xc.data_ptr(),
+                     n, w.data_ptr(), n, v.data_ptr(), None, None, jv.data_ptr(), hv.data_ptr())
+            return (jv * emu.y_sca[:, None]).t(), hv.t()
+
+        @staticmethod
+        def backward(ctx, *grads):
+            raise RuntimeError("TorchEmulator is twice differentiable by x: a third derivative was asked for "
+                               "(the library has no third input derivatives of the predictor)")
 
     class TorchEmulator(torch.nn.Module):
         """forward(x): (n, d) float64 tensor on the current GPU -> (n, q) de-standardised means, differentiable
-        by x (once: no double backward).  Theta, y_cent and y_sca are device buffers uploaded once."""
+        by x twice (the second derivative through obhip_predict_hvp_multi_dev; a third raises).  Theta, y_cent
+        and y_sca are device buffers uploaded once."""
 
         def __init__(self, fit):
             super().__init__()
