@@ -370,7 +370,7 @@ __device__ __forceinline__ void tl_waitn(double (&b)[12]) {
 // TAIL > 0: the last TAIL factors of a unit are NOT multiplied in but handed over one by one,
 //   template <int RR, int UNIT, int S, bool LEAD> void use_tail(v, buf)
 // with v the product of the WE - TAIL leading factors (LEAD false: there are none, v = 1) and
-// buf[S .. S + TAIL) the others (the gradient passes of kernels_grad.hip: a term's factor in one
+// buf[S .. S + TAIL) the others (the gradient pass k_tmm_d3 of kernels_grad_d3.hip: a term's factor in one
 // dimension and that dimension's delta columns)
 template <int WE, int W, int NU, int ROWS, int INFLIGHT = 12, int U0 = 0, int ROW0 = 0, int TAIL = 0>
 struct TlPipe {

@@ -2,9 +2,9 @@
 // contractions a likelihood needs of d B / d hyp -- w^T d(B a)/dhyp (loglik_gauss.cpp:120-127,
 // modandbase.cpp:663-760 matmul_gradhyp) and sum_i d(B^2)_ik/dhyp (diaghessgradhyp,
 // loglik_gauss.cpp:158-161; basematsq_gradhyp modandbase.cpp:588-590) -- in one sweep per group of
-// dimensions.  The groups' tables are built in kernels_grad.hip (build_d3_groups), the dense part
-// every term has is k_tmm_ge0 there.  (Its own translation unit: the instantiations compile for two
-// minutes.)
+// dimensions.  The groups' tables are built in grad_views.cpp (build_d3_groups), the dense part
+// every term has is k_tmm_ge0 in kernels_grad_dense.hip.  (Its own translation unit: the
+// instantiations compile for two minutes.)
 #include <hip/hip_runtime.h>
 
 #include "obhip_internal.h"

@@ -315,24 +315,12 @@ struct obhip_terms {
   obhip::DevBuf<uint32_t> sh_shape;   // nstars / 64
   obhip::DevBuf<uint32_t> sh_left_term;  // nleft (at least one element)
   obhip::DevBuf<uint16_t> sh_left_cols;  // nleft x W
-  // per hyper-parameter views for the gradient products (kernels_grad.hip)
-  std::vector<std::unique_ptr<obhip_terms>> ge_views;
-  // the same restricted to the terms that HAVE the hyper-parameter's dimension, with
-  // their indices (transposed gradient products: the other terms come from one dense pass)
-  std::vector<std::unique_ptr<obhip_terms>> ge_sviews;
-  std::vector<std::vector<uint32_t>> ge_sidx;
-  std::vector<uint64_t> ge_views_sig;  // hypmatch of the model the views were built for
-  std::vector<uint64_t> ge_full_sig;   // the same for ge_views
-  // restricted likewise, the dimension's factor replaced by the delta column (products B a)
-  std::vector<std::unique_ptr<obhip_terms>> ge_dviews;
-  // all ge_sviews concatenated (one B^T a pass for every hyper-parameter), offsets per h
+  // a few restricted views concatenated (one B^T pass for all of them), offsets per hyper-parameter
   struct GeGroup {
-    std::unique_ptr<obhip_terms> v;  // the ge_sviews of `hyps`, concatenated
+    std::unique_ptr<obhip_terms> v;  // the views of `hyps`, concatenated
     std::vector<uint64_t> hyps, off; // off[j]: first term of hyps[j] in v (off.size() = hyps.size() + 1)
   };
-  std::vector<GeGroup> ge_sgroups;
-  std::vector<GeGroup> ge_dgroups;  // the ge_dviews likewise (w^T d(B a)/dhyp as B_delta^T w)
-  // the fused gradient passes (k_tmm_d3, kernels_grad.hip): per launch the terms that have one of a
+  // the fused gradient passes (k_tmm_d3, kernels_grad_d3.hip): per launch the terms that have one of a
   // few dimensions, each with that dimension's own factor moved to the END of its column list and
   // followed by the delta columns (level of the term) of up to two of the dimension's
   // hyper-parameters -- tables written by hand into v (no levels), keyed by the level caps
@@ -340,11 +328,32 @@ struct obhip_terms {
     std::unique_ptr<obhip_terms> v;
     int nh = 0;                       // delta columns per view-term (1 or 2)
     std::vector<uint64_t> hyp0, off;  // member j: hyper-parameters hyp0[j] .. hyp0[j] + nh - 1,
-                                      // view-terms [off[j], off[j + 1]) = the terms ge_sidx[hyp0[j]]
+                                      // view-terms [off[j], off[j + 1]) = the terms sidx[hyp0[j]]
   };
-  std::vector<GeD3> ge_d3;
-  std::vector<int64_t> ge_d3_cap;     // key of the column layout ge_d3 was built for (build_d3_groups)
-  bool ge_d3_ok = false;              // false: some view does not fit the kernel -> older passes
+  // per hyper-parameter views of these terms for the gradient products (grad_views.cpp), with their keys
+  struct GradCache {
+    // full views: dimension hypmatch[h] dropped, the gradient block at level t + 1 (grad_view)
+    std::vector<std::unique_ptr<obhip_terms>> full;
+    std::vector<uint64_t> full_sig;  // hypmatch of the model they were built for
+    // restricted to the terms that HAVE the hyper-parameter's dimension (sidx[h]), its factor replaced
+    // by the gradient column (sviews: transposed products, the other terms come from one dense pass)
+    // or by the delta column (dviews: products B a); groups of each kind concatenated
+    std::vector<std::unique_ptr<obhip_terms>> sviews, dviews;
+    std::vector<std::vector<uint32_t>> sidx;
+    std::vector<GeGroup> sgroups, dgroups;
+    std::vector<uint64_t> sig;       // hypmatch of the model they were built for
+    // the k_tmm_d3 groups, written from sidx
+    std::vector<GeD3> d3;
+    std::vector<int64_t> d3_key;     // column layout they were built for (build_d3_groups)
+    bool d3_ok = false;              // false: some view does not fit the kernel
+    // empty restricted views for nh hyper-parameters laid out as `s`; the d3 tables go with them
+    void reset_views(const std::vector<uint64_t> &s, uint64_t nh) {
+      sig = s;
+      sviews.clear(), sviews.resize(nh), dviews.clear(), dviews.resize(nh);
+      sidx.assign(nh, {}), sgroups.clear(), dgroups.clear();
+      d3.clear(), d3_key.clear(), d3_ok = false;
+    }
+  } ge;
   // device view of the model capped at maxlev, for the fused predictor
   obhip::ModelDev pred_md;
   const obhip_model *pred_model = nullptr;
@@ -686,11 +695,27 @@ int launch_sample_colext(const double *d_path, uint64_t ld, uint64_t nr, uint64_
 int launch_sample_pick(const double *part_key, const int64_t *part_idx, uint64_t nparts, uint64_t stride, int qc,
                        double sgn, int64_t *d_index, double *d_value);
 
-// kernels_grad.hip
-int ensure_gradbasis(obhip_basis &b);
-int ensure_gradbasis_sq(obhip_basis &b);
+// kernels_grad_basis.hip
+int ensure_gradbasis(obhip_basis &b);     // b.grad = the gradient basis of b for the model's current state
+int ensure_gradbasis_sq(obhip_basis &b);  // ... and b.grad->gbsq, its squared store
+// grad_views.cpp: the views cached in t.ge, rebuilt when b's model lays its hyper-parameters out differently
+// full view of hyper-parameter h (every term; level 0 picks up the gradient column too)
 obhip_terms *grad_view(obhip_terms &t, const obhip_basis &b, uint64_t h);
-// device-level forms (inputs and n-sized results in HBM) for the likelihood classes
+// view of the terms that have h's dimension, its factor replaced by the gradient column (delta: the delta
+// column); *idx = their term indices; null when no term has the dimension
+obhip_terms *grad_view_restricted(obhip_terms &t, const obhip_basis &b, uint64_t h, bool delta,
+                                  const std::vector<uint32_t> **idx);
+// those views concatenated a few hyper-parameters at a time, at most 128 used columns per group
+std::vector<obhip_terms::GeGroup> &grad_view_groups(obhip_terms &t, const obhip_basis &b, bool delta);
+// t.ge.d3 = the k_tmm_d3 groups for b.grad's column layout; false: a view does not fit, or OBHIP_GRAD_D3=0
+bool build_d3_groups(obhip_terms &t, const obhip_basis &b);
+// kernels_grad_dense.hip: d_out (device, p x nhyp column-major) = sum_i a_i ge[h, 0]_i B_ik (squared: of
+// the squared stores), enqueued on the current stream; t prepared for b, b.grad built
+bool tmm_ge0_supports(const obhip_terms &t);  // at most 8 column slots and the tile within the LDS
+int launch_tmm_ge0(obhip_basis &b, obhip_terms &t, bool squared, const double *d_a, double *d_out);
+// (from the materialised design matrix; squared: b.grad->gbsq built)
+int launch_bt_times_ge0(obhip_basis &b, obhip_terms &t, bool squared, const double *d_a, double *d_out);
+// kernels_grad.hip: device-level forms (inputs and n-sized results in HBM) for the likelihood classes
 int grad_mm_dev(obhip_basis &b, obhip_terms &t, bool squared, const double *a_host, const double *d_a,
                 double *d_M, DevBuf<double> &dge);
 int grad_mm_dot_dev(obhip_basis &b, obhip_terms &t, const double *a_host, const double *d_M,
@@ -698,7 +723,7 @@ int grad_mm_dot_dev(obhip_basis &b, obhip_terms &t, const double *a_host, const 
 // staging class of a column of a k_tmm_d3 tile, in bits 28-29 of its entry in the group's ucol list
 constexpr uint32_t kD3Delta = 1u << 28, kD3Own = 2u << 28, kD3ColMask = (1u << 28) - 1;
 constexpr int kD3Pre = 20;  // k_tmm_d3: prefetch registers per thread => at most 8 * 20 columns per group
-// one group of obhip_terms::ge_d3 (kernels_grad_d3.hip): d_out (device, [2 nh][v.p]) = u1 of the
+// one group of obhip_terms::ge.d3 (kernels_grad_d3.hip): d_out (device, [2 nh][v.p]) = u1 of the
 // group's first hyper-parameter, of its second, u2 likewise; mode bit 0: u1, bit 1: u2
 int launch_tmm_d3(obhip_basis &b, const obhip_terms::GeD3 &g, int mode, const double *d_w1, const double *d_w2,
                   double *d_out);

@@ -1,5 +1,6 @@
-"""The fused hyper-gradient passes (k_tmm_d3, csrc/kernels_grad.hip) against the oracle and against
-the per-hyper-parameter passes they replace (OBHIP_GRAD_D3=0, read per call).
+"""The fused hyper-gradient passes (k_tmm_d3, csrc/kernels_grad_d3.hip) against the oracle and against
+the per-hyper-parameter passes they replace (OBHIP_GRAD_D3=0, read per call), and the four plans of
+the transposed products (GradPlan, csrc/kernels_grad.hip) each against the oracle.
 
 What is contracted: matmul_gradhyp / tmatmul_gradhyp / sqcolsums_gradhyp (prodmmge_, tprodmmge_:
 /root/reference/src/linalg.cpp:219-276, 395-471; modandbase.cpp:798-879) and, through them, the
@@ -172,6 +173,75 @@ def test_views_too_wide_for_the_fused_kernel_take_the_older_passes():
     bd = ob.outerbase(om_d, x)
     assert relerr(bd.tmatmul_gradhyp(terms, v), O.ob_tmm_gradhyp(bo, terms, v)[1]) < 1e-9
     assert relerr(bd.sqcolsums_gradhyp(terms), O.ob_sqcolsums_gradhyp(bo, terms)) < 1e-9
+
+
+# The four plans of the transposed products (GradPlan, csrc/kernels_grad.hip): how each is reached and
+# how many launches of the scopes tmm_d3 / tmm_gradhyp_dense it makes (True: some, False: none).
+# "wide" terms have a term of nine factors, beyond the 8 column slots of k_tmm_ge0 and k_tmm_d3.
+PLANS = {
+    "fused": ("narrow", {}, True, True),
+    "ge0_views": ("narrow", {"OBHIP_GRAD_D3": "0"}, False, True),
+    "bmat_views": ("wide", {}, False, True),
+    # (no room is found for the design matrix of a basis that has none yet: gram_panel_supports)
+    "full_views": ("wide", {"OBHIP_GRAM_CHUNK_ROWS": "128"}, False, False),
+}
+PLAN_KINDS = ["mat25", "mat25pow"] * 5   # groups of one and of two hyper-parameters per dimension
+_plan_refs = {}
+
+
+def _plan_reference(width):
+    """Inputs and the oracle's four contractions for one of the two term sets, computed once."""
+    if width not in _plan_refs:
+        import ob_oracle as O
+        rng = np.random.default_rng(17 + len(width))
+        p, n = 120, 333                            # n ragged against the 64-row tile
+        om_o, _ = make_pair(PLAN_KINDS, knots_for(PLAN_KINDS, 10))
+        # Levels up to 4 with up to five factors, up to 3 with nine (as in the nine-factor test above):
+        # what the float64 oracle itself resolves.  Against tests/extended_ref.py on these inputs it
+        # is off by at most 1.8e-10 (narrow) and 5.4e-11 (wide) in the four results, but by 1.4e-9 in
+        # matmul_gradhyp with nine factors of levels up to 4, more than the 1e-9 asked of the device.
+        terms = random_terms(rng, p, len(PLAN_KINDS), *((3, 9) if width == "wide" else (4, 5)))
+        if width == "wide":
+            terms[1, :9] = 1                       # one term with nine factors for certain
+        assert (np.count_nonzero(terms, axis=1).max() > 8) == (width == "wide")
+        x = sample_x(rng, n, PLAN_KINDS)
+        a, v = rng.standard_normal(p), rng.standard_normal(n)
+        bo = O.OuterBase(om_o, x, dograd=True)
+        mm = O.ob_mm_gradhyp(bo, terms, a)[1]
+        want = dict(mm=mm, dot=mm.T @ v, tmm=O.ob_tmm_gradhyp(bo, terms, v)[1],
+                    sqcolsums=O.ob_sqcolsums_gradhyp(bo, terms))
+        _plan_refs[width] = (terms, x, a, v, want)
+    return _plan_refs[width]
+
+
+@pytest.mark.parametrize("plan", list(PLANS))
+def test_every_plan_of_the_transposed_products_matches_the_oracle(plan, monkeypatch):
+    """matmul_gradhyp, matmul_gradhyp_dot, tmatmul_gradhyp and sqcolsums_gradhyp under each of the four
+    plans, against the oracle at the 1e-9 this file uses below level 8, and which plan ran from the
+    profile scopes of the fused pass and of the dense pass."""
+    import outerbase_amd as ob
+    from outerbase_amd import _lib
+    width, env, want_d3, want_dense = PLANS[plan]
+    terms, x, a, v, want = _plan_reference(width)
+    for key, val in env.items():
+        monkeypatch.setenv(key, val)
+    _, om_d = make_pair(PLAN_KINDS, knots_for(PLAN_KINDS, 10))
+    bd = ob.outerbase(om_d, x)
+    _lib.call("obhip_profile_reset")
+    _lib.call("obhip_profile_enable", 1)
+    got = dict(mm=bd.matmul_gradhyp(terms, a), dot=bd.matmul_gradhyp_dot(terms, a, v),
+               tmm=bd.tmatmul_gradhyp(terms, v), sqcolsums=bd.sqcolsums_gradhyp(terms))
+    launches = {}
+    for scope in (b"tmm_d3", b"tmm_gradhyp_dense"):
+        cnt, ms = C.c_uint64(0), C.c_double(0)
+        _lib.call("obhip_profile_get", scope, C.byref(cnt), C.byref(ms))
+        launches[scope] = cnt.value
+    _lib.call("obhip_profile_enable", 0)
+    print(plan, launches, {q: relerr(got[q], want[q]) for q in want})
+    assert (launches[b"tmm_d3"] > 0) == want_d3 and (launches[b"tmm_gradhyp_dense"] > 0) == want_dense, launches
+    for q in want:
+        assert np.shape(got[q]) == np.shape(want[q]), q
+        assert relerr(got[q], want[q]) < 1e-9, (plan, q)
 
 
 def test_one_terms_handle_on_bases_of_two_models():

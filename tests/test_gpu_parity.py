@@ -584,7 +584,7 @@ def test_gradient_basis_tables_and_knot_loop_against_extended_precision(kind, mo
 def test_gradhyp_with_more_hyperparameters_than_one_pass_holds(kinds, nhyp):
     """More hyper-parameters than one 16-block of the dense pass holds, and the shapes at which the
     last few are contracted in groups of four on the 4 x 4 x 4 matrix instruction (k_tmm_ge0_db,
-    csrc/kernels_grad.hip): matmul / tmatmul / sqcolsums _gradhyp against the oracle."""
+    csrc/kernels_grad_dense.hip): matmul / tmatmul / sqcolsums _gradhyp against the oracle."""
     import ob_oracle as O
     import outerbase_amd as ob
     rng = np.random.default_rng(26)
