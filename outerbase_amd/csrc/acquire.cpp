@@ -101,7 +101,7 @@ extern "C" int obhip_acquire_dev(const obhip_posterior *post, const double *d_th
     OB_TRY(Linv.alloc(pp * pp));
     OB_HIP(hipMemsetAsync(Linv.p, 0, pp * pp * sizeof(double), st));
     OB_TRY(launch_transpose(post->f.X.p, pp, Linv.p, pp, p));
-    OB_TRY(launch_atb(2, Linv.p, pp, pp, Linv.p, pp, pp, pp, false, S.p, pp));
+    OB_TRY(launch_atb(kAtbStore, Linv.p, pp, pp, Linv.p, pp, pp, pp, false, S.p, pp));
     OB_HIP(hipStreamSynchronize(st));  // Linv is a local
   }
   OB_TRY(launch_predict(om, t, d_theta, d_xcand, m, mu.p, nullptr, 0.0, nullptr));

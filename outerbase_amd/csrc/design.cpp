@@ -93,14 +93,14 @@ int row_forms_dev(const obhip_model &m, obhip_terms &t, const double *d_Q, bool 
     const double *B = Bcm.p, *Y = Ycm.p;
     double *out = d_out + r0;
     if (norms) {
-      OB_TRY(launch_atb(fixed_order ? 3 : 2, Bcm.p, npad, npad, d_Q, pp, pp, pp, true, Ycm.p, pp));  // Z = B X, npad x pp
+      OB_TRY(launch_atb(fixed_order ? kAtbStoreFixed : kAtbStore, Bcm.p, npad, npad, d_Q, pp, pp, pp, true, Ycm.p, pp));  // Z = B X, npad x pp
       OB_TRY(vmap(nr, [=] __device__(uint64_t i) {
         double s = 0.0;
         for (uint64_t k = 0; k < p; ++k) s = fma(Y[i * pp + k], Y[i * pp + k], s);
         out[i] = s;
       }));
     } else {
-      OB_TRY(launch_atb(fixed_order ? 3 : 2, d_Q, pp, pp, Bcm.p, npad, npad, pp, false, Ycm.p, npad));  // Y = Q B^T, pp x npad
+      OB_TRY(launch_atb(fixed_order ? kAtbStoreFixed : kAtbStore, d_Q, pp, pp, Bcm.p, npad, npad, pp, false, Ycm.p, npad));  // Y = Q B^T, pp x npad
       OB_TRY(vmap(nr, [=] __device__(uint64_t i) {
         double s = 0.0;
         for (uint64_t k = 0; k < p; ++k) s = fma(B[k * npad + i], Y[k * npad + i], s);
@@ -180,7 +180,7 @@ extern "C" int obhip_design_select_dev(const obhip_posterior *post, const double
     OB_TRY(Linv.alloc(pp * pp));
     OB_HIP(hipMemsetAsync(Linv.p, 0, pp * pp * sizeof(double), st));
     OB_TRY(launch_transpose(post->f.X.p, pp, Linv.p, pp, p));
-    OB_TRY(launch_atb(2, Linv.p, pp, pp, Linv.p, pp, pp, pp, false, S.p, pp));
+    OB_TRY(launch_atb(kAtbStore, Linv.p, pp, pp, Linv.p, pp, pp, pp, false, S.p, pp));
     OB_HIP(hipStreamSynchronize(st));  // Linv is a local
   }
   if (imse) {
@@ -198,8 +198,8 @@ extern "C" int obhip_design_select_dev(const obhip_posterior *post, const double
       const uint64_t a = i / pp, b = i % pp;
       Mpp[i] = (a < p && b < p) ? Mc[a * p + b] : 0.0;
     }));
-    OB_TRY(launch_atb(2, Mp.p, pp, pp, S.p, pp, pp, pp, false, W.p, pp));  // M S
-    OB_TRY(launch_atb(2, W.p, pp, pp, S.p, pp, pp, pp, false, T.p, pp));   // (M S)^T S = S M S
+    OB_TRY(launch_atb(kAtbStore, Mp.p, pp, pp, S.p, pp, pp, pp, false, W.p, pp));  // M S
+    OB_TRY(launch_atb(kAtbStore, W.p, pp, pp, S.p, pp, pp, pp, false, T.p, pp));   // (M S)^T S = S M S
     OB_TRY(row_forms_dev(om, t, T.p, false, p, pp, d_xcand, m, num.p));
     // tr(M S_0) = sum_kl M_kl S_kl
     OB_TRY(vsum<1>(pp * pp, [=] __device__(uint64_t i, double *acc) { acc[0] += Mpp[i] * Sc[i]; }, trace.p, part.p));

@@ -72,11 +72,10 @@ int grad_batch_normal_eq(obhip_basis &holder, const obhip_model &m, obhip_terms 
   const uint64_t ntiles = (n + kTileRows - 1) / kTileRows;
   size_t free_b = 0, total_b = 0;
   OB_HIP(hipMemGetInfo(&free_b, &total_b));
-  const size_t tile_bytes = (size_t)t.p_pad * kTileRows * L * sizeof(double);
-  uint64_t ctiles = std::min<size_t>(free_b / 4, (size_t)16 << 30) / tile_bytes;
-  if (const char *e = getenv("OBHIP_GRAM_CHUNK_ROWS")) ctiles = (uint64_t)atoll(e) / kTileRows;  // tests
-  ctiles = std::min(std::max<uint64_t>(ctiles, 1), ntiles);
-  if ((size_t)ctiles * tile_bytes > free_b)
+  const char *forced = getenv("OBHIP_GRAM_CHUNK_ROWS");  // tests
+  const uint64_t ctiles = gram_chunk_tiles(free_b, (uint64_t)t.p_pad * kTileRows * L * sizeof(double), ntiles,
+                                           forced ? std::max<uint64_t>(1, (uint64_t)atoll(forced)) : 0);
+  if (!ctiles)
     return fail(OBHIP_ERR_HIP, "not enough free HBM for even one row chunk of the derivative design matrix");
   const uint64_t blk_rows = ctiles * kTileRows;
   DevBuf<double> staged, ypart, part;
@@ -105,7 +104,7 @@ int grad_batch_normal_eq(obhip_basis &holder, const obhip_model &m, obhip_terms 
     // the level per dimension`, level 0 included (its function in dimension l is rho_l instead of 1), so
     // an entry of D_l^T D_l depends on the per-dimension unordered level pairs only -- gram_dedup.hip's
     // premise; and so does a sum of such matrices over l.
-    OB_TRY(gram_of_staged_rows(holder, staged.p, nt * L, t, sink, t0 != 0, t0 + nt >= ntiles));
+    OB_TRY(gram_of_staged(holder, staged.p, nt * L, t, sink, t0 != 0, t0 + nt >= ntiles));
   }
   return 0;
 }

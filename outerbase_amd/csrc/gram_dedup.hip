@@ -34,7 +34,7 @@ namespace obhip {
 
 namespace {
 
-constexpr int kGT = 128;
+constexpr int kGT = kGramTile;
 constexpr uint32_t kTileEntries = kGT * kGT;
 constexpr uint64_t kNoKey = ~0ull;  // padding, and the lower half of diagonal tiles
 // entries of all tile pairs above which the analysis is not run (p = 8192: 34 million; its
@@ -152,7 +152,7 @@ int analyse(obhip_terms &t, GramDedup &dd) {
   for (int dist = 0; dist < nb; ++dist)
     for (int I = 0; I + dist < nb; ++I) {
       order.push_back((uint32_t)I | (uint32_t)(I + dist) << 16);
-      slot_of_rank.push_back(I * nb - I * (I - 1) / 2 + dist);
+      slot_of_rank.push_back(pair_slot(nb, I, I + dist));
     }
   std::vector<uint16_t> lev16((size_t)p * d);
   for (size_t k = 0; k < lev16.size(); ++k) {
@@ -231,7 +231,7 @@ int gram_dedup_get(obhip_terms &t, const GramDedup **out) {
   if (!dd.tried || dd.hashbits != hashbits) {
     dd.nskip = 0;
     dd.sig = 0;
-    dd.cont_known = false;
+    dd.dealing = GramDedup::Dealing();
     dd.analysis_ms = 0.0;
     dd.tried = true;
     dd.hashbits = hashbits;

@@ -32,14 +32,14 @@
 //   per-wave 32-term LDS transpose, then 256-byte row segments to HBM.  (Terms of more than 8
 //   factors; the default copy is k_materialize_tl in kernels_prod.hip.)
 // k_atb_dma2: tile pair (I, J) of 128 x 128 terms and a run of row tiles per task, tasks in
-//   an XCD-aware table (build_task_order); 4 waves with 64 x 64 wave tiles (64 accumulators),
+//   an XCD-aware table (gram_plan.h: build_task_order, and the row split and dealing gram_of_staged
+//   takes from gram_choose_split / gram_choose_dealing); 4 waves with 64 x 64 wave tiles (64 accumulators),
 //   operands from two LDS panel buffers [16 rows][272], row-split partials reduced by
 //   k_gram_reduce (kernels_gram.hip).  The same body serves C = A^T Bm for two operands
-//   (launch_atb: row norms for predr_std, stored products for the marginal adjustment).
+//   (launch_atb with atb_rect_table: row norms for predr_std, stored products for the marginal adjustment).
 #include <algorithm>
 #include <map>
 #include <mutex>
-#include <tuple>
 
 #include <memory>
 #include "obhip_internal.h"
@@ -49,7 +49,7 @@ namespace obhip {
 
 namespace {
 
-constexpr int kGT = 128;            // output tile edge (terms)
+constexpr int kGT = kGramTile;      // output tile edge (terms)
 constexpr int kCR = 16;             // rows per chunk
 constexpr int kTP = 2 * 128 + 16;   // LDS panel row pitch (doubles), see k_gram_mfma4
 constexpr int kTB = 65;             // transpose buffer pitch
@@ -171,11 +171,7 @@ __device__ __forceinline__ void lds_rd_h1(const uint32_t (&baddr)[4], double (&b
 // For the last two the k range of column tile J ends at (J + 1) * 128 when `tri` says Bm is
 // upper triangular.  DBG: one block reports its s_memtime / s_memrealtime span (clock and
 // matrix-pipe cycles per chunk under load, OBHIP_GRAM_DBG=1); production carries none of it.
-constexpr int kAtbGram = 0, kAtbNorm = 1, kAtbStore = 2, kAtbStoreFixed = 3;  // 3: kAtbStore, one order of k
-__host__ __device__ inline uint64_t atb_task(uint64_t I, uint64_t J, uint64_t y, uint64_t type = 0) {
-  return I | (J << 24) | (y << 48) | (type << 62);
-}
-constexpr uint64_t kAtbNoTask = ~0ull;
+// (the modes are declared in obhip_internal.h, the task encoding in gram_plan.h)
 // What the four waves of a block do with the 256 staged columns [panel I | panel J] of a chunk:
 // per wave one byte = A operand's 64-column group (2 bits) | B operand's (2 bits) << 2 |
 // quadrant row << 4 | quadrant column << 5 | output tile (0: (I, I), 1: (J, J), 2: (I, J)) << 6.
@@ -399,158 +395,6 @@ k_atb_dma2(const double *__restrict__ A, uint64_t ldA, const double *__restrict_
   }
 }
 
-// Workgroups go to the 8 XCDs round-robin by linear id, so blocks x, x + 8, x + 16, ... share
-// one 4-MB L2, and an XCD keeps 64 of them resident (32 CUs x 2).  The work is cut into units
-// of (8 x 8 square of the tile-pair triangle, row split): the 64 blocks of a unit read 16
-// panel column blocks over the same rows, so a panel row fetched by one block is an L2 hit
-// for the others.  Every XCD gets whole units, one after the other (diagonal squares hold
-// 36 pairs; the next unit fills the slots they leave), and all XCDs the same number of blocks
-// (padding tasks exit at once).  At p = 4096: 10 squares x 32 splits = 320 units, 2112 blocks
-// per XCD = 33 rounds of 64.  (The first version dealt every XCD a 66-pair run of the sorted
-// pair list per split: runs straddle squares and touch 16-24 column blocks.)
-//
-// When the units do not pack into the 64 slots of an XCD -- one 34-block square per split at
-// p = 1024: two units are 68 blocks, and the four that do not fit wait for a whole second round --
-// the units are dealt CONTINUOUSLY instead (`continuous`): the task list in unit order is cut
-// into 8 equal runs, a unit may straddle two XCDs (its panels are then fetched by both).
-// gram_xcd_blocks tells the row-split choice what either dealing gives an XCD.
-//
-// Tile pairs that hold repeats of other entries of G only (`skip`, one byte per slot of the pair
-// triangle, gram_dedup.hip; may be null) get no task: their squares are smaller units, and their
-// slots of the partial-tile workspace stay unwritten.
-constexpr int kXcd = 8, kSq = 8;
-struct GramUnit {
-  int bi, bj, y, size;
-};
-inline bool pair_skipped(const uint8_t *skip, int nb, int i, int j) {
-  return skip && skip[i * nb - i * (i - 1) / 2 + (j - i)];
-}
-void gram_units(int nb, int nsplit, bool diag4, const uint8_t *skip, std::vector<GramUnit> &units) {
-  const int nsq = (nb + kSq - 1) / kSq;
-  for (int y = 0; y < nsplit; ++y)
-    for (int bi = 0; bi < nsq; ++bi)
-      for (int bj = bi; bj < nsq; ++bj) {
-        int size = 0;
-        for (int i = bi * kSq; i < std::min(nb, (bi + 1) * kSq); ++i)
-          for (int j = std::max(i, bj * kSq); j < std::min(nb, (bj + 1) * kSq); ++j)
-            if (!(i == j && diag4 && i / 4 * 4 + 3 < nb && i % 4 == 3) && !pair_skipped(skip, nb, i, j)) ++size;
-        if (size) units.push_back({bi, bj, y, size});
-      }
-}
-// blocks of the busiest XCD
-uint64_t gram_xcd_blocks(int nb, int nsplit, bool diag4, bool continuous) {
-  std::vector<GramUnit> units;
-  gram_units(nb, 1, diag4, nullptr, units);  // (every split has the same units)
-  uint64_t per_split = 0;
-  for (const GramUnit &u : units) per_split += (uint64_t)u.size;
-  if (continuous) return (per_split * (uint64_t)nsplit + kXcd - 1) / kXcd;
-  std::vector<int> sizes;
-  for (int y = 0; y < nsplit; ++y)
-    for (const GramUnit &u : units) sizes.push_back(u.size);
-  std::stable_sort(sizes.begin(), sizes.end(), [](int a, int b) { return a > b; });
-  uint64_t load[kXcd] = {0};
-  for (int s : sizes) {
-    int k = 0;
-    for (int q = 1; q < kXcd; ++q)
-      if (load[q] < load[k]) k = q;
-    load[k] += (uint64_t)s;
-  }
-  return *std::max_element(load, load + kXcd);
-}
-void build_task_order(int nb, int nsplit, bool diag4, bool continuous, const uint8_t *skip,
-                      std::vector<uint64_t> &tab) {
-  typedef GramUnit Unit;
-  std::vector<Unit> units;
-  gram_units(nb, nsplit, diag4, skip, units);
-  // the tasks of a unit in its order
-  auto unit_tasks = [&](const Unit &u, std::vector<uint64_t> &out) {
-    for (int i = u.bi * kSq; i < std::min(nb, (u.bi + 1) * kSq); ++i)
-      for (int j = std::max(i, u.bj * kSq); j < std::min(nb, (u.bj + 1) * kSq); ++j) {
-        if (i == j && diag4) {
-          // four consecutive diagonal tiles as three blocks (atb_wave_code); squares are 8 wide,
-          // so a group never straddles two of them (its three blocks may still go to different
-          // XCDs where the top-up below takes single tasks of a diagonal square: they write
-          // disjoint wave tiles)
-          const int g0 = i / 4 * 4;
-          if (g0 + 3 < nb) {
-            if (i - g0 < 3) out.push_back(atb_task(i, i + 1, u.y, 1 + (i - g0)));
-            continue;
-          }
-        }
-        if (pair_skipped(skip, nb, i, j)) continue;
-        out.push_back(atb_task(i, j, u.y));
-      }
-  };
-  std::vector<std::vector<uint64_t>> seq(kXcd);
-  // whole runs of tasks, the largest first, each to the XCD with the fewest blocks so far (stable:
-  // the order of equal-sized runs keeps squares of one split together)
-  auto deal = [&](std::vector<std::vector<uint64_t>> &runs) {
-    std::stable_sort(runs.begin(), runs.end(),
-                     [](const std::vector<uint64_t> &a, const std::vector<uint64_t> &b) { return a.size() > b.size(); });
-    for (const auto &r : runs) {
-      int k = 0;
-      for (int q = 1; q < kXcd; ++q)
-        if (seq[q].size() < seq[k].size()) k = q;
-      seq[k].insert(seq[k].end(), r.begin(), r.end());
-    }
-  };
-  if (continuous) {  // the task list in unit order cut into 8 equal runs
-    std::vector<uint64_t> all;
-    for (const Unit &u : units) unit_tasks(u, all);
-    const uint64_t run = (all.size() + kXcd - 1) / kXcd;
-    for (size_t m = 0; m < all.size(); ++m) seq[m / run].push_back(all[m]);
-  } else if (skip) {
-    // An off-diagonal square that lost pairs no longer fills the 64 slots of its XCD: the next
-    // unit's first blocks would start beside it and its remaining ones a round later, and sharers
-    // of a panel that do not start together miss the L2 together.  Such a
-    // square is topped up to 64 with tasks of the split's diagonal squares -- those of its own row
-    // or column band first, whose panels it stages anyway -- and what is left of the diagonal
-    // squares goes out in runs of 64.
-    constexpr size_t kFull = (size_t)kSq * kSq;
-    std::vector<std::vector<uint64_t>> runs;
-    const int nsq = (nb + kSq - 1) / kSq;
-    size_t u0 = 0;
-    while (u0 < units.size()) {
-      size_t u1 = u0;
-      while (u1 < units.size() && units[u1].y == units[u0].y) ++u1;
-      std::vector<std::vector<uint64_t>> diag((size_t)nsq);
-      for (size_t m = u0; m < u1; ++m)
-        if (units[m].bi == units[m].bj) unit_tasks(units[m], diag[(size_t)units[m].bi]);
-      for (size_t m = u0; m < u1; ++m) {
-        const Unit &u = units[m];
-        if (u.bi == u.bj) continue;
-        std::vector<uint64_t> r;
-        unit_tasks(u, r);
-        for (int pass = 0; pass < 2 && r.size() < kFull; ++pass)
-          for (int sq = 0; sq < nsq && r.size() < kFull; ++sq) {
-            if ((pass == 0) != (sq == u.bi || sq == u.bj)) continue;
-            std::vector<uint64_t> &pool = diag[(size_t)sq];
-            while (!pool.empty() && r.size() < kFull) {
-              r.push_back(pool.back());
-              pool.pop_back();
-            }
-          }
-        runs.push_back(std::move(r));
-      }
-      std::vector<uint64_t> rest;
-      for (auto &pool : diag) rest.insert(rest.end(), pool.begin(), pool.end());
-      for (size_t m = 0; m < rest.size(); m += kFull)
-        runs.emplace_back(rest.begin() + m, rest.begin() + std::min(rest.size(), m + kFull));
-      u0 = u1;
-    }
-    deal(runs);
-  } else {
-    std::vector<std::vector<uint64_t>> runs(units.size());
-    for (size_t m = 0; m < units.size(); ++m) unit_tasks(units[m], runs[m]);
-    deal(runs);
-  }
-  size_t len = 0;
-  for (auto &q : seq) len = std::max(len, q.size());
-  tab.assign(len * kXcd, kAtbNoTask);
-  for (int k = 0; k < kXcd; ++k)
-    for (size_t m = 0; m < seq[k].size(); ++m) tab[m * kXcd + k] = seq[k][m];
-}
-
 template <int W2>
 int run_materialize(const obhip_basis &b, obhip_terms &t, double *d_B) {
   const size_t lds = (t.Mu * kTileRows + 4 * 32 * kTB) * sizeof(double);
@@ -618,167 +462,108 @@ int materialize_any(const obhip_basis &b, obhip_terms &t, double *d_B, GramFuse 
   }
 }
 
-// partial tiles of B^T B over the ntiles row tiles of d_B, reduced into d_G
-int gram_of_staged(obhip_basis &b, const double *d_B, uint64_t ntiles, obhip_terms &t,
-                   const GramSink &sink, bool accumulate, bool last) {
-  // OBHIP_GRAM_DBG=1: print one block's s_memtime / s_memrealtime span
-  const bool dbg = getenv("OBHIP_GRAM_DBG") && atoi(getenv("OBHIP_GRAM_DBG")) != 0;
-  const int nb = (int)((t.p + kGT - 1) / kGT);
-  const int npairs = nb * (nb + 1) / 2;
-  // Row split: two blocks per CU at a time and all blocks (nearly) equally long, so the launch
-  // takes ceil(blocks / slots) rounds of tiles-per-split each; pick the split that minimises
-  // that product (528 pairs x 32 splits = 33 x 512 exactly on MI355X).
-  const int ncu = device_cus(b.device);
-  const bool diag4 = !(getenv("OBHIP_GRAM_DIAG4") && atoi(getenv("OBHIP_GRAM_DIAG4")) == 0);
-  // blocks per row split: four consecutive diagonal tiles take three blocks (atb_wave_code)
-  // ... and tile pairs that only repeat entries of other pairs none (gram_dedup.hip; analysed on the
+// one launch of k_atb_dma2<MODE, DBG, FIXED>, a block per entry of the task table
+template <int MODE, bool DBG, bool FIXED = false>
+int run_atb(const double *A, uint64_t ldA, const double *Bm, uint64_t ldB, int nb, int npairs, uint64_t ntiles,
+            uint64_t split_base, int tri, const DevBuf<uint64_t> &tasks, double *out, uint64_t ldo,
+            unsigned long long *dbgout) {
+  const size_t lds = (size_t)2 * kCR * kTP * sizeof(double);
+  OB_TRY(ensure_dyn_lds((const void *)k_atb_dma2<MODE, DBG, FIXED>, lds));
+  hipLaunchKernelGGL((k_atb_dma2<MODE, DBG, FIXED>), dim3((unsigned)tasks.n), dim3(256), lds, cur_stream(), A, ldA,
+                     Bm, ldB, nb, npairs, ntiles, split_base, tri, tasks.p, out, ldo, dbgout);
+  OB_HIP(hipGetLastError());
+  return 0;
+}
+
+// The environment switches of the Gram launch, read on every call (tests set them in-process).
+struct GramSwitches {
+  // =1: print one block's s_memtime / s_memrealtime span
+  bool dbg = getenv("OBHIP_GRAM_DBG") && atoi(getenv("OBHIP_GRAM_DBG")) != 0;
+  // =0: one block per diagonal tile
+  bool diag4 = !(getenv("OBHIP_GRAM_DIAG4") && atoi(getenv("OBHIP_GRAM_DIAG4")) == 0);
+  const char *nsplit = getenv("OBHIP_GRAM_NSPLIT");          // the row split, 1 .. gram_max_split (null: the plan's)
+  const char *continuous = getenv("OBHIP_GRAM_CONTINUOUS");  // 0 / 1, the dealing (null: the plan's)
+};
+
+// gram_choose_split of a shape (the choice depends on the shape only: priced once per shape, not once per fit)
+GramPlan split_of_shape(const GramShape &shape) {
+  static std::mutex mu;
+  static std::map<GramKey, GramPlan> cache;
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = cache.find(GramKey{shape});
+  if (it == cache.end()) it = cache.emplace(GramKey{shape}, gram_choose_split(shape)).first;
+  return it->second;
+}
+
+int print_gram_dbg(const unsigned long long *dbgout) {
+  unsigned long long h[17];
+  OB_HIP(hipMemcpy(h, dbgout, sizeof(h), hipMemcpyDeviceToHost));
+  fprintf(stderr, "[gram dbg] middle-round block: first chunk %.2f us, loop %.2f us, stores %.2f us; the block one round "
+                  "on starts %.2f us after this one ended (its first chunk %.2f us)\n",
+          0.01 * (double)(h[10] - h[9]), 0.01 * (double)(h[11] - h[10]), 0.01 * (double)(h[12] - h[11]),
+          0.01 * (double)((long long)h[13] - (long long)h[12]), 0.01 * (double)(h[14] - h[13]));
+  fprintf(stderr, "[gram dbg] clock of a block of the first / middle / last round: %.0f / %.0f / %.0f MHz\n",
+          h[4] ? 100.0 * h[3] / h[4] : 0.0, h[1] ? 100.0 * h[0] / h[1] : 0.0, h[7] ? 100.0 * h[6] / h[7] : 0.0);
+  fprintf(stderr, "[gram dbg] one block: %llu shader-clock ticks in %llu x 10 ns -> %.0f MHz, %.0f ticks "
+          "per 16-row chunk (8192 = matrix pipe saturated by two blocks)\n",
+          h[0], h[1], h[1] ? 100.0 * h[0] / h[1] : 0.0, h[2] ? (double)h[0] / h[2] : 0.0);
+  return 0;
+}
+
+}  // namespace
+
+// partial tiles of B^T B over the ntiles row tiles of d_B, reduced into the sink:
+// switches -> dedup -> plan -> table -> launch -> reduce -> fill
+int gram_of_staged(obhip_basis &b, const double *d_B, uint64_t ntiles, obhip_terms &t, const GramSink &sink,
+                   bool accumulate, bool last) {
+  const GramSwitches sw{};
+  // tile pairs that only repeat entries of other pairs get no task (gram_dedup.hip; analysed on the
   // term set's first Gram)
   const GramDedup *dd = nullptr;
   OB_TRY(gram_dedup_get(t, &dd));
   const uint8_t *skip = dd ? dd->skip.data() : nullptr;
-  const uint64_t skip_sig = dd ? dd->sig : 0;
-  const uint64_t bps = (uint64_t)npairs - (diag4 ? (uint64_t)(nb / 4) : 0) - (dd ? (uint64_t)dd->nskip : 0);
-  const uint64_t slots = 2 * (uint64_t)ncu;
-  uint64_t nsplit = 1;
-  const uint64_t max_split = std::max<uint64_t>(
-      1, std::min<uint64_t>({64, ntiles / 8, (4ull << 30) / ((uint64_t)npairs * kGT * kGT * 8)}));
-  // (the splits differ by at most one tile and the longer ones are few and dealt out first,
-  // so a round costs the average length; one tile charged for a block's first chunk, its
-  // partial-tile store and the hand-over of the slot: ~7 us measured, OBHIP_GRAM_DBG)
-  // A last round that fills at most half of the slots leaves its blocks alone on their CUs,
-  // where they run ~1.7x as fast (0.6 of a round); and every split costs k_gram_reduce one
-  // more partial of every tile pair to read (128 KB at ~4 TB/s = 0.0022 of the 14.6 us a block
-  // takes per row tile).  Both measured at p = 4096 (16 vs 32 splits at 125 000 rows: equal
-  // Gram times, half the reduction).
-  // The rounds are those of the busiest XCD (64 of the slots each): the task table hands the XCDs
-  // whole units (build_task_order), and when those do not pack into 64 slots -- p = 1024: one
-  // 34-block unit per split, two of them = 68 -- a whole round is spent on the overhang (measured:
-  // 2.56 ms where the model without XCDs promised 1.5).  Both dealings are priced, the continuous
-  // one 3 % dearer for the panels its straddling units fetch twice.
-  double bestc = 1e300;
-  bool continuous = false;
-  const uint64_t xslots = slots / kXcd;
-  // (the choice depends on the shape only: priced once per shape, not once per fit)
-  static std::mutex split_mu;
-  static std::map<std::tuple<int, uint64_t, uint64_t, uint64_t, bool>, std::pair<uint64_t, bool>> split_cache;
-  const auto split_key = std::make_tuple(nb, ntiles, max_split, slots, diag4);
-  bool cached = false;
-  {
-    std::lock_guard<std::mutex> lk(split_mu);
-    auto it = split_cache.find(split_key);
-    if (it != split_cache.end()) {
-      nsplit = it->second.first;
-      continuous = it->second.second;
-      cached = true;
+  const GramShape shape = {(int)((t.p + kGT - 1) / kGT), ntiles, 2 * (uint64_t)device_cus(b.device), sw.diag4};
+  const int nb = shape.nb, npairs = (int)gram_npairs(nb);
+  // the plan: the split as if no pair were skipped (gram_choose_split says why), the dealing for the mask
+  // at that split, kept with the analysis; a forced value replaces either
+  GramPlan plan = split_of_shape(shape);
+  if (sw.nsplit) plan.nsplit = std::max<uint64_t>(1, std::min<uint64_t>(gram_max_split(shape), atoi(sw.nsplit)));
+  if (skip) {
+    GramDedup::Dealing &d = t.dedup.dealing;
+    const GramKey key = {shape, plan.nsplit, dd->sig};
+    if (!(d.key == key)) {
+      d.continuous = gram_choose_dealing(shape, plan.nsplit, skip);
+      d.key = key;
     }
+    plan.continuous = d.continuous;
   }
-  // The split is chosen WITHOUT the skipped pairs, as if every pair had its task: the entries of the
-  // computed pairs are then the same sums in the same order whether or not others are skipped (bit
-  // for bit the run with OBHIP_GRAM_DEDUP=0).  Only the dealing to the XCDs, which changes no sum,
-  // is priced on the tasks that are left -- on the table build_task_order deals for the mask (its
-  // topped-up runs are not the units gram_xcd_blocks models), once per term set and shape.
-  const uint64_t bps_all = bps + (dd ? (uint64_t)dd->nskip : 0);
-  auto price = [&](uint64_t ns, int mode, const uint8_t *mask, uint64_t blocks) {
-    uint64_t per;
-    if (mask) {
-      std::vector<uint64_t> tab;
-      build_task_order(nb, (int)ns, diag4, mode == 1, mask, tab);
-      per = tab.size() / kXcd;  // the longest XCD sequence
-    } else {
-      per = gram_xcd_blocks(nb, (int)ns, diag4, mode == 1);
-    }
-    const uint64_t full = per / xslots, tail = per % xslots;
-    const double rounds = (double)full + (tail == 0 ? 0.0 : (2 * tail <= xslots ? 0.6 : 1.0));
-    const double cost = rounds * ((double)ntiles / (double)ns + 1.0) + 0.0022 * (double)blocks;
-    return mode == 1 ? cost * 1.03 : cost;
-  };
-  for (uint64_t ns = 1; !cached && ns <= max_split; ++ns) {
-    for (int mode = 0; mode < 2; ++mode) {
-      const double cost = price(ns, mode, nullptr, ns * bps_all);
-      if (cost < bestc - 1e-9) {
-        bestc = cost;
-        nsplit = ns;
-        continuous = mode == 1;
-      }
-    }
-  }
-  if (!cached) {
-    std::lock_guard<std::mutex> lk(split_mu);
-    split_cache[split_key] = std::make_pair(nsplit, continuous);
-  }
-  if (const char *e = getenv("OBHIP_GRAM_NSPLIT")) nsplit = std::max<uint64_t>(1, std::min<uint64_t>(max_split, atoi(e)));
-  if (skip) {  // the dealing for this mask at this split: kept with the analysis
-    GramDedup &d = t.dedup;
-    const auto key = std::make_tuple(ntiles, nsplit, slots, diag4);
-    if (!d.cont_known || d.cont_key != key) {
-      d.cont = price(nsplit, 1, skip, nsplit * bps) < price(nsplit, 0, skip, nsplit * bps) - 1e-9;
-      d.cont_key = key;
-      d.cont_known = true;
-    }
-    continuous = d.cont;
-  }
-  if (const char *e = getenv("OBHIP_GRAM_CONTINUOUS")) continuous = atoi(e) != 0;
-  double *part = nullptr;
-  OB_TRY(b.workspace((size_t)nsplit * npairs * kGT * kGT * sizeof(double) + 256, (void **)&part));
-  unsigned long long *dbgout =
-      dbg ? (unsigned long long *)(part + (size_t)nsplit * npairs * kGT * kGT) : nullptr;
-  if (b.gram_pairs_nb != nb || b.gram_pairs_ns != (int)nsplit || b.gram_pairs_diag4 != diag4 ||
-      b.gram_pairs_cont != continuous || b.gram_pairs_skip != skip_sig) {
+  if (sw.continuous) plan.continuous = atoi(sw.continuous) != 0;
+  // the table: built and uploaded when anything it depends on has changed
+  obhip_basis::GramTable &tb = b.gram_table;
+  const GramKey tkey = {{nb, 0, 0, sw.diag4}, plan.nsplit, dd ? dd->sig : 0, plan.continuous ? 1 : 0};
+  if (!(tb.key == tkey)) {
     std::vector<uint64_t> tab;
-    build_task_order(nb, (int)nsplit, diag4, continuous, skip, tab);
-    b.gram_pairs_nb = -1;  // (not the old table's key should the upload fail)
-    b.gram_pairs_skip = skip_sig;
-    b.gram_pairs_diag4 = diag4;
-    b.gram_pairs_cont = continuous;
-    OB_TRY(b.gram_pairs.upload(tab.data(), tab.size()));
-    b.gram_pairs_nb = nb;
-    b.gram_pairs_ns = (int)nsplit;
+    build_task_order(nb, (int)plan.nsplit, sw.diag4, plan.continuous, skip, tab);
+    tb.key = GramKey();  // (not the old table's key should the upload fail)
+    OB_TRY(tb.tab.upload(tab.data(), tab.size()));
+    tb.key = tkey;
   }
-  const unsigned nblocks = (unsigned)b.gram_pairs.n;
-  const size_t lds = (size_t)2 * kCR * kTP * sizeof(double);
-  {
+  const size_t part_n = (size_t)plan.nsplit * npairs * kGT * kGT;
+  double *part = nullptr;
+  OB_TRY(b.workspace(part_n * sizeof(double) + 256, (void **)&part));
+  unsigned long long *dbgout = sw.dbg ? (unsigned long long *)(part + part_n) : nullptr;
+  OB_TRY(pick_bool(sw.dbg, [&](auto DBG) {
     ProfScope ps("gram");
-    if (dbg) {
-      OB_TRY(ensure_dyn_lds((const void *)k_atb_dma2<kAtbGram, true>, lds));
-      hipLaunchKernelGGL((k_atb_dma2<kAtbGram, true>), dim3(nblocks), dim3(256), lds, cur_stream(), d_B,
-                         t.p_pad, d_B, t.p_pad, nb, npairs, ntiles, ntiles / nsplit, (int)(ntiles % nsplit), b.gram_pairs.p, part,
-                         (uint64_t)0, dbgout);
-    } else {
-      OB_TRY(ensure_dyn_lds((const void *)k_atb_dma2<kAtbGram, false>, lds));
-      hipLaunchKernelGGL((k_atb_dma2<kAtbGram, false>), dim3(nblocks), dim3(256), lds, cur_stream(),
-                         d_B, t.p_pad, d_B, t.p_pad, nb, npairs, ntiles, ntiles / nsplit, (int)(ntiles % nsplit), b.gram_pairs.p, part,
-                         (uint64_t)0, nullptr);
-    }
-    OB_HIP(hipGetLastError());
-  }
-  if (dbgout) {
-    unsigned long long h[17];
-    OB_HIP(hipMemcpy(h, dbgout, sizeof(h), hipMemcpyDeviceToHost));
-    fprintf(stderr, "[gram dbg] middle-round block: first chunk %.2f us, loop %.2f us, stores %.2f us; the block one round "
-                    "on starts %.2f us after this one ended (its first chunk %.2f us)\n",
-            0.01 * (double)(h[10] - h[9]), 0.01 * (double)(h[11] - h[10]), 0.01 * (double)(h[12] - h[11]),
-            0.01 * (double)((long long)h[13] - (long long)h[12]), 0.01 * (double)(h[14] - h[13]));
-    fprintf(stderr, "[gram dbg] clock of a block of the first / middle / last round: %.0f / %.0f / %.0f MHz\n",
-            h[4] ? 100.0 * h[3] / h[4] : 0.0, h[1] ? 100.0 * h[0] / h[1] : 0.0, h[7] ? 100.0 * h[6] / h[7] : 0.0);
-    fprintf(stderr,
-            "[gram dbg] one block: %llu shader-clock ticks in %llu x 10 ns -> %.0f MHz, %.0f ticks "
-            "per 16-row chunk (8192 = matrix pipe saturated by two blocks)\n",
-            h[0], h[1], h[1] ? 100.0 * h[0] / h[1] : 0.0, h[2] ? (double)h[0] / h[2] : 0.0);
-  }
-  OB_TRY(launch_gram_reduce(part, npairs, (int)nsplit, nb, (int)t.p, sink, accumulate, last,
+    return run_atb<kAtbGram, DBG()>(d_B, t.p_pad, d_B, t.p_pad, nb, npairs, ntiles, ntiles / plan.nsplit,
+                                    (int)(ntiles % plan.nsplit), tb.tab, part, 0, dbgout);
+  }));
+  if (dbgout) OB_TRY(print_gram_dbg(dbgout));
+  OB_TRY(launch_gram_reduce(part, npairs, (int)plan.nsplit, nb, (int)t.p, sink, accumulate, last,
                             dd ? dd->skip_dev.p : nullptr));
   // the skipped pairs' entries from their sources in the sink: after every reduction (of a row
   // chunk too: the sources then hold the sums so far, the copies likewise), formed values when the
   // reduction formed the Hessian
   return dd ? launch_gram_fill(*dd, (int)t.p, sink) : 0;
-}
-
-}  // namespace
-
-// for rows the caller staged itself (grad_obs.cpp: the derivative design matrix)
-int gram_of_staged_rows(obhip_basis &holder, const double *d_B, uint64_t ntiles, obhip_terms &t, const GramSink &sink,
-                        bool accumulate, bool last) {
-  return gram_of_staged(holder, d_B, ntiles, t, sink, accumulate, last);
 }
 
 // d_B: n_pad x p_pad doubles, row-major (= column-major p_pad x n_pad); padding rows are 0
@@ -815,12 +600,10 @@ int launch_gram_panel(const obhip_basis &bc, obhip_terms &t, const GramSink &sin
   // 16 GB, at least 64 tiles so that the launch still fills the GPU).
   size_t free_b = 0, total_b = 0;
   OB_HIP(hipMemGetInfo(&free_b, &total_b));
-  const size_t row_bytes = (size_t)t.p_pad * kTileRows * sizeof(double);
-  uint64_t ctiles = std::min<size_t>(free_b / 4, (size_t)16 << 30) / row_bytes;
-  if (const char *e = getenv("OBHIP_GRAM_CHUNK_ROWS")) ctiles = (uint64_t)atoll(e) / kTileRows;
-  ctiles = std::max<uint64_t>(ctiles, 1);
-  ctiles = std::min(ctiles, ntiles);
-  if ((size_t)ctiles * row_bytes > free_b)
+  const char *forced = getenv("OBHIP_GRAM_CHUNK_ROWS");
+  const uint64_t ctiles = gram_chunk_tiles(free_b, (uint64_t)t.p_pad * kTileRows * sizeof(double), ntiles,
+                                           forced ? std::max<uint64_t>(1, (uint64_t)atoll(forced)) : 0);
+  if (!ctiles)
     return fail(OBHIP_ERR_HIP, "not enough free HBM for even one row chunk of the design matrix");
   b.bmat_terms = 0;  // the buffer no longer holds the whole matrix of any terms
   if (b.bmat.n < (size_t)ctiles * kTileRows * t.p_pad) OB_TRY(b.bmat.alloc((size_t)ctiles * kTileRows * t.p_pad));
@@ -846,6 +629,7 @@ int launch_gram_panel(const obhip_basis &bc, obhip_terms &t, const GramSink &sin
 // (row tile, column tile) like the Gram's.
 int launch_atb(int mode, const double *A, uint64_t ldA, uint64_t M, const double *Bm, uint64_t ldB,
                uint64_t N, uint64_t K, bool tri, double *out, uint64_t ldo) {
+  if (mode < kAtbNorm || mode > kAtbStoreFixed) return fail(OBHIP_ERR_INVALID, "launch_atb: unknown mode");
   if (M % kGT || N % kGT || K % kTileRows)
     return fail(OBHIP_ERR_INVALID, "launch_atb: sizes must be padded to the tile");
   const uint64_t mt = M / kGT, nt = N / kGT;
@@ -885,22 +669,7 @@ int launch_atb(int mode, const double *A, uint64_t ldA, uint64_t M, const double
     }
     Tab &slot = cache[key];
     if (!slot) {
-      // units of up to 8 x 8 tiles, column-tile squares of equal k range together, dealt to the
-      // XCD with the fewest blocks so far
-      std::vector<std::vector<uint64_t>> seq(kXcd);
-      for (uint64_t bj = 0; bj * kSq < nt; ++bj)
-        for (uint64_t bi = 0; bi * kSq < mt; ++bi) {
-          int k = 0;
-          for (int q = 1; q < kXcd; ++q)
-            if (seq[q].size() < seq[k].size()) k = q;
-          for (uint64_t i = bi * kSq; i < std::min(mt, (bi + 1) * kSq); ++i)
-            for (uint64_t j = bj * kSq; j < std::min(nt, (bj + 1) * kSq); ++j) seq[k].push_back(atb_task(i, j, 0));
-        }
-      size_t len = 0;
-      for (auto &q : seq) len = std::max(len, q.size());
-      std::vector<uint64_t> tab(len * kXcd, kAtbNoTask);
-      for (int k = 0; k < kXcd; ++k)
-        for (size_t m = 0; m < seq[k].size(); ++m) tab[m * kXcd + k] = seq[k][m];
+      const std::vector<uint64_t> tab = atb_rect_table(mt, nt);
       slot = std::make_shared<DevBuf<uint64_t>>();  // freed by its last holder, after eviction
       const int rc = slot->upload(tab.data(), tab.size());
       if (rc) {
@@ -917,30 +686,12 @@ int launch_atb(int mode, const double *A, uint64_t ldA, uint64_t M, const double
     victim.reset();
     if (victim_dev != dev) (void)hipSetDevice(dev);
   }
-  DevBuf<uint64_t> &dtab = *dtabp;
-  const size_t ntasks = dtab.n;
-  const size_t lds = (size_t)2 * kCR * kTP * sizeof(double);
-  const uint64_t ktiles = K / kTileRows;
-  if (mode == kAtbNorm) {
-    OB_TRY(ensure_dyn_lds((const void *)k_atb_dma2<kAtbNorm, false>, lds));
-    hipLaunchKernelGGL((k_atb_dma2<kAtbNorm, false>), dim3((unsigned)ntasks), dim3(256), lds,
-                       cur_stream(), A, ldA, Bm, ldB, 0, 0, ktiles, ktiles, tri ? 1 : 0, dtab.p, out,
-                       ldo, nullptr);
-  } else if (mode == kAtbStore) {
-    OB_TRY(ensure_dyn_lds((const void *)k_atb_dma2<kAtbStore, false>, lds));
-    hipLaunchKernelGGL((k_atb_dma2<kAtbStore, false>), dim3((unsigned)ntasks), dim3(256), lds,
-                       cur_stream(), A, ldA, Bm, ldB, 0, 0, ktiles, ktiles, tri ? 1 : 0, dtab.p, out,
-                       ldo, nullptr);
-  } else if (mode == kAtbStoreFixed) {
-    OB_TRY(ensure_dyn_lds((const void *)k_atb_dma2<kAtbStore, false, true>, lds));
-    hipLaunchKernelGGL((k_atb_dma2<kAtbStore, false, true>), dim3((unsigned)ntasks), dim3(256), lds,
-                       cur_stream(), A, ldA, Bm, ldB, 0, 0, ktiles, ktiles, tri ? 1 : 0, dtab.p, out,
-                       ldo, nullptr);
-  } else {
-    return fail(OBHIP_ERR_INVALID, "launch_atb: unknown mode");
-  }
-  OB_HIP(hipGetLastError());
-  return 0;
+  // (listed last to first: the kernels then stand in the code object in the order of their modes)
+  return pick_or<kAtbStoreFixed, kAtbStore, kAtbNorm>(mode, 0, [&](auto M) {
+    constexpr int m = M();  // (kAtbStoreFixed is kAtbStore's body with FIXED)
+    return run_atb<m == kAtbNorm ? kAtbNorm : kAtbStore, false, m == kAtbStoreFixed>(
+        A, ldA, Bm, ldB, 0, 0, K / kTileRows, K / kTileRows, tri ? 1 : 0, *dtabp, out, ldo, nullptr);
+  });
 }
 
 }  // namespace obhip

@@ -19,6 +19,7 @@
 
 #include "../../include/obhip.h"
 #include "launch_plan.h"
+#include "gram_plan.h"
 
 namespace obhip {
 
@@ -282,8 +283,10 @@ struct GramDedup {
   int nb = 0, npairs = 0, nskip = 0;
   double analysis_ms = 0.0;    // host wall time of the analysis, uploads and read-back included
   uint64_t sig = 0;            // serial number of the analysis (non-zero): key of the task tables built on the mask
-  bool cont_known = false, cont = false;  // dealing chosen for the mask (continuous or whole runs) at the shape
-  std::tuple<uint64_t, uint64_t, uint64_t, bool> cont_key;  // (row tiles, row splits, block slots, diag4)
+  struct Dealing {             // dealing chosen for the mask (continuous or whole runs) ...
+    GramKey key;               // ... at this shape and split (no shape: none chosen yet)
+    bool continuous = false;
+  } dealing;
   std::vector<uint8_t> skip;   // per tile pair (row-major slot in the upper triangle): 1 = no task
   DevBuf<uint8_t> skip_dev;    // the same on the device
   DevBuf<uint32_t> pairs;      // nskip skipped tile pairs, I | J << 16
@@ -449,10 +452,10 @@ struct obhip_basis {
   obhip::DevBuf<double> bmat;   // row-major design matrix [n_pad][p_pad], staging of the
                                 // materialised-B Gram kernel (allocated on first use)
   uint64_t bmat_terms = 0;      // uid of the terms bmat currently holds (0: none)
-  obhip::DevBuf<uint64_t> gram_pairs;  // XCD-aware (tile pair, row split) task order of that kernel
-  int gram_pairs_nb = -1, gram_pairs_ns = -1;
-  bool gram_pairs_diag4 = false, gram_pairs_cont = false;
-  uint64_t gram_pairs_skip = 0;  // GramDedup::sig of the mask the order was built with (0: none)
+  struct GramTable {            // XCD-aware (tile pair, row split) task order of that kernel ...
+    obhip::GramKey key;         // ... and what it was built for (no shape: no table)
+    obhip::DevBuf<uint64_t> tab;
+  } gram_table;
   std::unique_ptr<obhip_gradbasis> grad;  // built on first *_gradhyp call, dropped on rebuild
   int device = 0;
   int workspace(size_t bytes, void **out) {
@@ -471,6 +474,7 @@ struct obhip_basis {
 namespace obhip {
 
 constexpr int kTileRows = 64;
+static_assert(kTileRows == kGramRowTile, "gram_plan.h sizes row chunks in these tiles");
 // LDS of a workgroup on gfx950: what the fused kernels size their tiles against
 constexpr size_t kLdsBudget = 160 * 1024;
 // the largest tile the term-per-lane and star kernels were measured to run with: what their
@@ -572,9 +576,15 @@ int get_gram_backend();
 int launch_materialize_rows(const obhip_basis &b, obhip_terms &t, double *d_B, GramFuse *fuse = nullptr);
 int ensure_bmat(obhip_basis &b, obhip_terms &t, GramFuse *fuse = nullptr);  // b.bmat = design matrix of (b, t)
 bool gram_panel_supports(const obhip_basis &b, const obhip_terms &t);
-// C = A^T Bm on the matrix cores (kernels_gram_panel.hip): mode 1 = row norms of C into
-// out[J * ldo + i] per 128-column tile J, mode 2 = C stored row-major with ldo, mode 3 = mode 2 with every entry
-// summed over k in one order wherever it stands (mode 2 rotates a tile's start by its indices)
+// partial tiles of B^T B over the ntiles x 64 rows staged at d_B (pitch p_pad), reduced into the sink; holder
+// lends its device, workspace and task table (grad_obs.cpp stages rows of its own)
+int gram_of_staged(obhip_basis &holder, const double *d_B, uint64_t ntiles, obhip_terms &t, const GramSink &sink,
+                   bool accumulate, bool last);
+// C = A^T Bm on the matrix cores (kernels_gram_panel.hip): kAtbNorm = row norms of C into
+// out[J * ldo + i] per 128-column tile J, kAtbStore = C stored row-major with ldo, kAtbStoreFixed = the same with
+// every entry summed over k in one order wherever it stands (kAtbStore rotates a tile's start by its indices);
+// kAtbGram is gram_of_staged's own
+constexpr int kAtbGram = 0, kAtbNorm = 1, kAtbStore = 2, kAtbStoreFixed = 3;
 int launch_atb(int mode, const double *A, uint64_t ldA, uint64_t M, const double *Bm, uint64_t ldB,
                uint64_t N, uint64_t K, bool tri, double *out, uint64_t ldo);
 // kernels_trtri.hip: X (pp x pp, zeroed) = L^-T in its upper triangle; transpose of an n x n block
@@ -612,7 +622,7 @@ struct BasisGuard {
   ~BasisGuard() { obhip_basis_destroy(b); }
 };
 // design.cpp: b_i^T Q b_i (norms false) or || X^T b_i ||^2 (norms true) at the n rows of d_x, a stored product
-// and one ascending sum per row.  fixed_order: the stored product by launch_atb's mode 3, and only then do
+// and one ascending sum per row.  fixed_order: the stored product by launch_atb's kAtbStoreFixed, and only then do
 // bit-identical rows get bit-identical results wherever they stand (without it: when their 128-row tiles of a
 // chunk have the same index mod 8 -- what obhip_design_select has always returned)
 int row_forms_dev(const obhip_model &m, obhip_terms &t, const double *d_Q, bool norms, uint64_t p, uint64_t pp,
@@ -989,9 +999,6 @@ int launch_dx_colsum(const double *d_part, uint64_t nsplit, uint64_t pitch, uint
 int grad_batch_normal_eq(obhip_basis &holder, const obhip_model &m, obhip_terms &t, const double *d_x, uint64_t n,
                          const uint32_t *dims, const double *weights, uint64_t L, const double *d_dY, uint64_t lddy,
                          uint64_t q, double *d_tri, double *d_R);
-// kernels_gram_panel.hip: gram_of_staged for a caller that stages its own rows (ntiles x 64 rows, pitch p_pad)
-int gram_of_staged_rows(obhip_basis &holder, const double *d_B, uint64_t ntiles, obhip_terms &t, const GramSink &sink,
-                        bool accumulate, bool last);
 // kernels_acc.hip: the streaming fit's batch moments, folds and right-hand sides (normal_acc.cpp)
 // dst +/- src over the triangle and R only (a batch of gradient rows has no B^T 1 and no moments)
 int launch_acc_fold_grad(uint64_t p, uint64_t q, double *d_dst, const double *d_src, double sign);

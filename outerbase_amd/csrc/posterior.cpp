@@ -79,7 +79,7 @@ int post_var_dev(const obhip_model &m, obhip_terms &t, const PostFactor &f, cons
     OB_TRY(launch_getmat(*b, t, Bcm.p, npad));  // B^T: term-major, rows contiguous
     {
       ProfScope ps("predict_std_gemm");
-      OB_TRY(launch_atb(1, Bcm.p, npad, npad, f.X.p, pp, pp, pp, true, part.p, npad));
+      OB_TRY(launch_atb(kAtbNorm, Bcm.p, npad, npad, f.X.p, pp, pp, pp, true, part.p, npad));
     }
     const double *pt = part.p;
     double *out = d_var + r0;
@@ -153,7 +153,7 @@ extern "C" int obhip_margadj_full(const obhip_basis *bc, const obhip_terms *tc, 
   OB_TRY(Hinv.alloc(pp * pp));
   OB_HIP(hipMemsetAsync(Linv.p, 0, pp * pp * sizeof(double), cur_stream()));
   OB_TRY(launch_transpose(f.X.p, pp, Linv.p, pp, p));
-  OB_TRY(launch_atb(2, Linv.p, pp, pp, Linv.p, pp, pp, pp, false, Hinv.p, pp));
+  OB_TRY(launch_atb(kAtbStore, Linv.p, pp, pp, Linv.p, pp, pp, pp, false, Hinv.p, pp));
   std::vector<double> hinv(p);  // diag(inv(H))
   OB_HIP(hipMemcpy2DAsync(hinv.data(), sizeof(double), Hinv.p, (pp + 1) * sizeof(double),
                           sizeof(double), p, hipMemcpyDeviceToHost, cur_stream()));
@@ -165,7 +165,7 @@ extern "C" int obhip_margadj_full(const obhip_basis *bc, const obhip_terms *tc, 
   OB_TRY(Ycm.alloc(pp * npad));
   OB_HIP(hipMemsetAsync(Bcm.p, 0, pp * npad * sizeof(double), cur_stream()));
   OB_TRY(launch_getmat(b, t, Bcm.p, npad));
-  OB_TRY(launch_atb(2, Hinv.p, pp, pp, Bcm.p, npad, npad, pp, false, Ycm.p, npad));
+  OB_TRY(launch_atb(kAtbStore, Hinv.p, pp, pp, Bcm.p, npad, npad, pp, false, Ycm.p, npad));
   OB_TRY(dscal.alloc(nh + 1 + 4096));
   double *part = dscal.p + nh + 1;
   // tr(inv(H) B^T B) and tr(inv(H) B^T Bge_l): rows k < p, the n real columns of each
