@@ -1281,6 +1281,58 @@ int obhip_product_loglik(const obhip_model *m, const obhip_terms *t, const doubl
                          uint64_t ldxa, const double *y, const double *obsvar, const double *xb,
                          uint64_t nb, uint64_t ldxb, const double *coeffvar, double sigma, double *out);
 
+/* ---- gradient by xb on the product (no reference counterpart) ---------------------------------
+ * The derivatives of the pair's mean and variance, and of the two likelihood sums, by the inputs of
+ * block B: what an optimiser or an HMC / MALA sampler over the candidate rows of xb needs per step.
+ * One response.  Notation of the section above and of obhip_predict_grad_dev; l runs over the L =
+ * ndims_b dimensions of B, in the order of dims_b.  For B row j
+ *     rho_jl = R'_l0 / R_l0        r'_{l,t} = (R'_lt - r_lt R'_l0) / R_l0
+ *     E_jkl  = V_jk without dimension l's factor (a product, never a quotient)
+ * and with S_ij = sum_k theta_k U_ik V_jk, Q_ij = sum_k c_k U_ik^2 V_jk^2, s = sA_i sB_j
+ *     m'_ijl = d mean_ij / d xb_jl = s (rho_jl S_ij + D_ijl)
+ *              D_ijl = sum_{k: t_kl > 0} theta_k U_ik E_jkl r'_{l,t_kl}(xb_j)
+ *     v'_ijl = d var_ij / d xb_jl = 2 s^2 (rho_jl Q_ij + F_ijl)
+ *              F_ijl = sum_{k: t_kl > 0} c_k U_ik^2 V_jk E_jkl r'_{l,t_kl}(xb_j)
+ *     d chi2_j / d xb_jl   = sum_i ( -2 r_ij / v_ij m'_ijl - r_ij^2 / v_ij^2 v'_ijl )
+ *     d logdet_j / d xb_jl = sum_i v'_ijl / v_ij
+ * (v' = 0 without d_coeffvar).  D and F run over the VIEW of l only -- the terms that contain
+ * dimension l -- as matrix products on the matrix cores after the dense pass: all L gradients cost
+ * about view_terms / p more passes, view_terms = sum_l |view_l|, not L more.  Term sets whose tiles
+ * (the B tile now with its derivative columns and L columns of rho) do not fit the kernel's LDS, and
+ * OBHIP_FORCE_GENERIC, are expanded in bounded row chunks and go through obhip_predict_grad_dev.
+ * Refusals as in the section above.  Fixed summation order, no atomics: two calls give the same bits. */
+/* host only: obhip_product_layout's mu_a and mu_b, view_terms, and whether the fused gradient kernel
+ * takes the split */
+int obhip_product_grad_layout(const obhip_terms *t, const uint32_t *dims_b, uint64_t ndims_b,
+                              uint64_t *mu_a, uint64_t *mu_b, uint64_t *view_terms, int *fused);
+/* d_dmean[(l nb + j) lda + i] = m'_ijl; d_dvar (same shape; may be NULL, needs d_coeffvar) = v'_ijl.
+ * The mean-only call gives the bits of the d_dmean of the call with the variance. */
+int obhip_predict_product_grad_dev(const obhip_model *m, const obhip_terms *t, const double *d_theta,
+                                   const uint32_t *dims_b, uint64_t ndims_b, const double *d_xa,
+                                   uint64_t na, const double *d_xb, uint64_t nb, double *d_dmean,
+                                   uint64_t lda, const double *d_coeffvar, double sigma,
+                                   double *d_dvar);
+/* obhip_product_loglik_dev with the gradients: d_out is nb x (2 + 2 L), column-major,
+ * [chi2, logdet, d chi2 / d xb_0 .., d logdet / d xb_0 ..].  On the fused route the first two
+ * columns carry the bits of obhip_product_loglik_dev (the same contraction).  A bad d_obsvar:
+ * OBHIP_ERR_NUMERIC, d_out untouched. */
+int obhip_product_loglik_grad_dev(const obhip_model *m, const obhip_terms *t, const double *d_theta,
+                                  const uint32_t *dims_b, uint64_t ndims_b, const double *d_xa,
+                                  uint64_t na, const double *d_y, const double *d_obsvar,
+                                  const double *d_xb, uint64_t nb, const double *d_coeffvar,
+                                  double sigma, double *d_out);
+/* host-buffer forms, as above: dmean, dvar with leading dimension lda, out nb x (2 + 2 L) */
+int obhip_predict_product_grad(const obhip_model *m, const obhip_terms *t, const double *theta,
+                               const uint32_t *dims_b, uint64_t ndims_b, const double *xa, uint64_t na,
+                               uint64_t ldxa, const double *xb, uint64_t nb, uint64_t ldxb,
+                               double *dmean, uint64_t lda, const double *coeffvar, double sigma,
+                               double *dvar);
+int obhip_product_loglik_grad(const obhip_model *m, const obhip_terms *t, const double *theta,
+                              const uint32_t *dims_b, uint64_t ndims_b, const double *xa, uint64_t na,
+                              uint64_t ldxa, const double *y, const double *obsvar, const double *xb,
+                              uint64_t nb, uint64_t ldxb, const double *coeffvar, double sigma,
+                              double *out);
+
 /* ---- synthetic workload of BASELINE.md section 3 (benchmark input) ------ */
 /* rows [row0, row0+n) of the counter-based SplitMix64 stream; d_x is n x d
  * column-major, d_y n (raw, not standardised).  kinds: d entries. */

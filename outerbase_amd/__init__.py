@@ -18,8 +18,9 @@ from .glm import GlmFit, fit_glm
 from .sensitivity import (InputMoments, Sobol2Result, SobolResult, input_moments, interaction_effects, main_effects,
                           sobol, sobol2, uniform_nodes)
 from .design import AcquireResult, DesignResult, Posterior, ThompsonResult
-from .torch_emulator import TorchEmulator
-from .product import CalibrationLoglik, predict_product, product_layout, product_loglik
+from .torch_emulator import TorchCalibration, TorchEmulator
+from .product import (CalibrationLoglik, predict_product, predict_product_grad, product_grad_layout, product_layout,
+                      product_loglik, product_loglik_grad)
 from .driver import HotPath, MultiHotPath
 from .stream import (CVResult, NewtonAccumulator, cv_folds, cv_newton_multi, design_dx,
                      fit_newton_grad)
@@ -39,4 +40,5 @@ __all__ = [
     "InputMoments", "SobolResult", "input_moments", "uniform_nodes", "sobol", "main_effects",
     "Sobol2Result", "sobol2", "interaction_effects",
     "predict_product", "product_loglik", "product_layout", "CalibrationLoglik",
+    "predict_product_grad", "product_loglik_grad", "product_grad_layout", "TorchCalibration",
 ]

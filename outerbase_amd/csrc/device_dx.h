@@ -213,6 +213,30 @@ __device__ __forceinline__ void build_tile_side(const DimDesc *__restrict__ dims
   part[wave * kTileRows + store.lane] = sc;
 }
 
+// build_tile_side with the derivatives by the side's inputs (kernels_product_dx.hip): behind the side's Mu
+// value columns the derivative column of every used column >= 1 and behind those one column of rho per entry
+// of side[], in that order (StoreTile::der, ::rho with l = the entry's index).  The value columns and the row
+// scale are those of build_tile_side's formulas through build_dim_dx_any, as build_tile<DX = true> has them.
+template <int WAVES, int PITCH>
+__device__ __forceinline__ void build_tile_side_dx(const DimDesc *__restrict__ dims, const double *__restrict__ ka,
+                                                   const double *__restrict__ kb, const double *__restrict__ kc,
+                                                   const double *__restrict__ rot, const double *__restrict__ tab,
+                                                   const double *__restrict__ dtab, const int *__restrict__ side,
+                                                   int nside, const double *__restrict__ x, uint64_t ldx, uint64_t row,
+                                                   bool valid, int wave, int slot, const StoreTile<PITCH> &store,
+                                                   double *part) {
+  double sc = 1.0;
+  for (int s = slot; s < nside; s += WAVES) {
+    const DimDesc D = dims[side[s]];
+    const double xv = valid ? x[(uint64_t)s * ldx + row] : 0.5;
+    double rho;
+    sc *= build_dim_dx_any(D, ka, kb, kc, rot, tab, dtab, xv, store, rho);
+    store.rho(s, rho);
+  }
+  if (wave == 0) store.tile[store.lane] = 1.0;  // used column 0 = all ones
+  part[wave * kTileRows + store.lane] = sc;
+}
+
 // the row scale of this lane's row: the waves' shares multiplied in wave order
 template <int WAVES>
 __device__ __forceinline__ double tile_scale(const double *part, int lane) {

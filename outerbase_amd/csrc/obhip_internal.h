@@ -409,6 +409,17 @@ struct obhip_terms {
     obhip::DevBuf<int32_t> cpos_a, cpos_b;   // compact column -> the side's used column or -1 (Mc each)
     obhip::DevBuf<uint16_t> cols_a, cols_b;  // p x wa, p x wb: right-aligned, padded with column 0
   } product;
+  // gradient by xb on the product (product.cpp, kernels_product_dx.hip): per dimension of dims_b the view of
+  // the terms that have it, against the tables of `product` for the same split and caps.  An entry is
+  // wa / 2 words of the term's A columns, wb / 2 words of its OTHER B columns (own slot = the ones column),
+  // its own used B column and its term index.
+  struct ProductGrad {
+    std::vector<uint32_t> dims_b;      // key, as in Product
+    std::vector<int64_t> cap;
+    std::vector<uint32_t> voff_h;      // |B| + 1: first entry of every B dimension
+    obhip::DevBuf<uint32_t> voff;      // the same on the device
+    obhip::DevBuf<uint32_t> vw;        // entries x (wa / 2 + wb / 2 + 2) words
+  } product_grad;
   int prepare(const std::vector<int64_t> &cap, const std::vector<obhip::DimDesc> &dims);
 };
 
@@ -802,6 +813,36 @@ int launch_product_lik_rows(const double *d_mean, const double *d_var, double e2
 int launch_product_sum_tiles(const double *d_part, uint64_t tiles_a, uint64_t nb, double *d_out);
 // *bad_out != 0: an entry of d_v (n) is negative or not finite (waits for the device)
 int launch_check_nonneg(const double *d_v, uint64_t n, int *bad_out);
+// kernels_product_dx.hip: the gradient by xb on the product (include/obhip.h, "gradient by xb"; DESIGN.md
+// section 28).  One response; L = |dims_b|.
+struct ProductGradCall {
+  const double *theta = nullptr;     // p
+  const double *xa = nullptr, *xb = nullptr;
+  uint64_t na = 0, nb = 0;
+  const double *coeffvar = nullptr;  // p or null: no variance part
+  double sigma = 0.0;
+  double *dmean = nullptr;           // store epilogue: dmean[(l nb + j) lda + i] ...
+  uint64_t lda = 0;
+  double *dvar = nullptr;            // ... and dvar likewise (needs coeffvar)
+  const double *y = nullptr, *obsvar = nullptr;  // likelihood epilogue (dmean == nullptr): ...
+  double *part = nullptr;            // ... part[(w tiles_a + A tile) nb + j], w < 2 + 2 L: chi2, logdet,
+                                     // d chi2 / d xb_l (w = 2 + l), d logdet / d xb_l (w = 2 + L + l)
+};
+size_t product_grad_lds(uint64_t mu_a, uint64_t mu_b, uint64_t nb_dims, uint64_t wa, uint64_t wb);
+// the gradient kernel's domain: the A tile, the B tile with its derivative and rho columns and the staging
+// within kLdsBudget, column lists of even width
+bool product_grad_supports(uint64_t mu_a, uint64_t mu_b, uint64_t nb_dims, uint64_t wa, uint64_t wb);
+// t.product, t.product_grad, t.pred_md and t.dx.dtab are prepared for the split (product.cpp)
+int launch_product_grad(const obhip_model &m, obhip_terms &t, const ProductGradCall &c);
+// the row route's reduction: the likelihood terms and their gradients of a chunk of expanded rows (d_grad,
+// d_gradvar: rows x d as obhip_predict_grad_dev writes them; d_var, d_gradvar null: e2sigma, no variance part)
+// per A tile in the fused kernel's order, into the partials of ProductGradCall::part
+int launch_product_lik_grad_rows(const obhip_terms &t, const double *d_mean, const double *d_var, double e2sigma,
+                                 const double *d_grad, const double *d_gradvar, const double *d_y,
+                                 const double *d_obsvar, uint64_t na, uint64_t nb, uint64_t i0, uint64_t ni,
+                                 uint64_t j0, uint64_t nj, double *d_part);
+// d_out[w nb + j], w < ncols = the partials of the A tiles added in ascending order
+int launch_product_sum_tile_cols(const double *d_part, uint64_t tiles_a, uint64_t nb, uint64_t ncols, double *d_out);
 // kernels_glm.hip: the row pass between two Newton steps of the GLM fit (glm.cpp) and the response scale
 // of its predictor.  eta_i = (eta ? eta[i] : o ? o[i] : 0) + (deta ? alpha deta[i] : 0); scale, scale_w and
 // u have n rounded up to a multiple of 64 entries; scale_w == nullptr: a trial pass, only the sums

@@ -258,7 +258,8 @@ class MultiFit:
             return mean
         return mean, v.cpu().numpy().T[:, :, None] * (self.y_sca * self.y_sca)[None, None, :]
 
-    def calibration_loglik(self, x_field, y_field, t_cand, dims_t, obs_var=None, response=0, emulator_var=True):
+    def calibration_loglik(self, x_field, y_field, t_cand, dims_t, obs_var=None, response=0, emulator_var=True,
+                           grad=False):
         """Gaussian log-likelihood of the field data y_field (na, raw units) observed at the settings x_field
         (na x the dimensions not in dims_t) for every candidate t_cand[j] (nb x len(dims_t)) of the
         dimensions dims_t, under the emulator of one response:
@@ -266,9 +267,27 @@ class MultiFit:
             loglik_j = -(chi2_j + logdet_j) / 2 - (na / 2) log 2 pi,  chi2 = sum_i r^2 / v,  logdet = sum_i log v.
         obs_var: na variances in raw units (or one for all rows; None: 0).  Returns a CalibrationLoglik with
         loglik, chi2, logdet (nb each).  The sums are formed on the device tile by tile
-        (obhip_product_loglik_dev); the na x nb matrices are never written."""
+        (obhip_product_loglik_dev); the na x nb matrices are never written.
+        grad=True: the result also has grad (nb x len(dims_t)), d loglik_j / d t_cand[j] = -(d chi2_j +
+        d logdet_j) / 2 in raw units, from the same pass (obhip_product_loglik_grad_dev); the constant
+        2 na log y_sca of logdet has no gradient."""
         from . import product
         x_field, t_cand, _ = product.check_blocks(self.om.d, x_field, t_cand, dims_t)
+        y, ov = self._field_data(x_field, y_field, obs_var, response)
+        na = x_field.shape[0]
+        args = (self.om, self._t, self.coeff[:, response], x_field, y, t_cand, dims_t)
+        kw = dict(obsvar=ov, coeffvar=1.0 / self.diagH if emulator_var else None, sigma=self.sigma)
+        g = None
+        if grad:
+            chi2, logdet, dchi2, dlogdet = product.product_loglik_grad(*args, **kw)
+            g = -0.5 * (dchi2 + dlogdet)
+        else:
+            chi2, logdet = product.product_loglik(*args, **kw)
+        logdet = logdet + 2.0 * na * math.log(self.y_sca[response])
+        return product.CalibrationLoglik(-0.5 * (chi2 + logdet) - 0.5 * na * math.log(2.0 * math.pi), chi2, logdet, g)
+
+    def _field_data(self, x_field, y_field, obs_var, response):
+        """calibration_loglik's checks: (standardised y, standardised obs_var or None) of one response"""
         if not (isinstance(response, (int, np.integer)) and 0 <= response < self.q):
             raise ValueError("response must be in 0 .. q - 1")
         y = np.asarray(y_field, dtype=np.float64)
@@ -283,11 +302,7 @@ class MultiFit:
             if ov.shape != (na,):
                 raise ValueError("obs_var must be a number or have one entry per row of x_field")
             ov = ov / (sca * sca)
-        chi2, logdet = product.product_loglik(self.om, self._t, self.coeff[:, response], x_field, (y - cent) / sca,
-                                              t_cand, dims_t, obsvar=ov,
-                                              coeffvar=1.0 / self.diagH if emulator_var else None, sigma=self.sigma)
-        logdet = logdet + 2.0 * na * math.log(sca)
-        return product.CalibrationLoglik(-0.5 * (chi2 + logdet) - 0.5 * na * math.log(2.0 * math.pi), chi2, logdet)
+        return (y - cent) / sca, ov
 
     def torch(self):
         """a differentiable torch module of the de-standardised predictor (torch_emulator.TorchEmulator)"""

@@ -106,23 +106,96 @@ def predict_product(om, terms, Theta, xa, xb, dims_b, coeffvar=None, sigma=None)
 
 
 class CalibrationLoglik:
-    """loglik, chi2 = sum_i r_ij^2 / v_ij and logdet = sum_i log v_ij per candidate j, in raw units"""
+    """loglik, chi2 = sum_i r_ij^2 / v_ij and logdet = sum_i log v_ij per candidate j, in raw units; from
+    calibration_loglik(..., grad=True) also grad (nb x L) = d loglik_j / d t_j"""
 
-    def __init__(self, loglik, chi2, logdet):
+    def __init__(self, loglik, chi2, logdet, grad=None):
         self.loglik, self.chi2, self.logdet = loglik, chi2, logdet
+        if grad is not None:
+            self.grad = grad
 
 
-def product_loglik(om, terms, theta, xa, y, xb, dims_b, obsvar=None, coeffvar=None, sigma=None):
-    """(chi2, logdet), nb each, of the standardised field data y (na) at the settings xa for every candidate
-    row of xb: r = y - mean, v = var + obsvar (var = e^{2 sigma} without coeffvar) -- obhip_product_loglik_dev"""
+def product_grad_layout(om, terms, dims_b):
+    """(mu_a, mu_b, view_terms, fused): product_layout's used columns, the (term, dimension of dims_b) pairs
+    with a factor -- the inner dimensions of the gradient's view products, summed -- and whether the fused
+    gradient kernel takes the split (obhip_product_grad_layout; host only)"""
+    t = obmod._terms_of(om, terms)
+    db = check_dims_b(om.d, dims_b)
+    ma, mb, vt, fu = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_int(0)
+    call("obhip_product_grad_layout", t._h, db.ctypes.data, db.size, C.byref(ma), C.byref(mb), C.byref(vt), C.byref(fu))
+    return ma.value, mb.value, vt.value, bool(fu.value)
+
+
+def predict_product_grad(om, terms, theta, xa, xb, dims_b, coeffvar=None, sigma=None):
+    """dmean (na, nb, L): the derivative of the mean of the coefficient vector theta (p) at every pair
+    (xa[i], xb[j]) by xb[j, l]; with coeffvar (p) also the derivative of predict_product's variance, returned as
+    (dmean, dvar).  Standardised units -- obhip_predict_product_grad_dev."""
     import torch
     t = obmod._terms_of(om, terms)
     xa, xb, db = check_blocks(om.d, xa, xb, dims_b)
     theta = np.asarray(theta, dtype=np.float64)
     if theta.shape != (t.p,):
         raise ValueError("theta must have p entries")
+    if coeffvar is not None:
+        coeffvar = np.asarray(coeffvar, dtype=np.float64)
+        if coeffvar.shape != (t.p,):
+            raise ValueError("coeffvar must have p entries")
+    if sigma is None:
+        sigma = math.log(0.01)
+    na, nb, L = xa.shape[0], xb.shape[0], db.size
+    if na == 0 or nb == 0:
+        z = np.zeros((na, nb, L))
+        return z if coeffvar is None else (z, z.copy())
+    dev = _device()
+    vec = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    dth, dcv = vec(theta), vec(coeffvar)
+    dxa, dxb = _cols(xa, dev), _cols(xb, dev)
+    dmean = torch.empty((L, nb, na), dtype=torch.float64, device=dev)
+    dvar = None if dcv is None else torch.empty((L, nb, na), dtype=torch.float64, device=dev)
+    call("obhip_predict_product_grad_dev", om._h, t._h, dth.data_ptr(), db.ctypes.data, db.size, dxa.data_ptr(), na,
+         dxb.data_ptr(), nb, dmean.data_ptr(), na, None if dcv is None else dcv.data_ptr(), float(sigma),
+         None if dvar is None else dvar.data_ptr())
+    dmean = dmean.permute(2, 1, 0).cpu().numpy()
+    return dmean if dvar is None else (dmean, dvar.permute(2, 1, 0).cpu().numpy())
+
+
+def product_loglik_grad(om, terms, theta, xa, y, xb, dims_b, obsvar=None, coeffvar=None, sigma=None):
+    """(chi2, logdet, dchi2, dlogdet): product_loglik's sums (nb each; on the fused kernel the same bits) and
+    their derivatives by xb[j, l] (nb x L each) -- obhip_product_loglik_grad_dev"""
+    import torch
+    t = obmod._terms_of(om, terms)
+    xa, xb, db = check_blocks(om.d, xa, xb, dims_b)
+    theta, y, obsvar, coeffvar, sigma = _loglik_args(t, theta, xa, y, obsvar, coeffvar, sigma)
+    na, nb, L = xa.shape[0], xb.shape[0], db.size
+    if na == 0 or nb == 0:
+        return np.zeros(nb), np.zeros(nb), np.zeros((nb, L)), np.zeros((nb, L))
+    dev = _device()
+    vec = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    out = product_loglik_grad_dev(om, t, vec(theta), _cols(xa, dev), vec(y), vec(obsvar), _cols(xb, dev), db,
+                                  vec(coeffvar), sigma).cpu().numpy()
+    return out[0].copy(), out[1].copy(), out[2:2 + L].T.copy(), out[2 + L:].T.copy()
+
+
+def product_loglik_grad_dev(om, t, dth, dxa, dy, dov, dxb, db, dcv, sigma):
+    """the (2 + 2 L) x nb device tensor of obhip_product_loglik_grad_dev from device tensors (dxa, dxb
+    column-major: |A| x na, L x nb); nothing passes through the host"""
+    import torch
+    na, nb = dxa.shape[1], dxb.shape[1]
+    out = torch.empty((2 + 2 * db.size, nb), dtype=torch.float64, device=dxb.device)
+    call("obhip_set_stream", C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    call("obhip_product_loglik_grad_dev", om._h, t._h, dth.data_ptr(), db.ctypes.data, db.size, dxa.data_ptr(), na,
+         dy.data_ptr(), None if dov is None else dov.data_ptr(), dxb.data_ptr(), nb,
+         None if dcv is None else dcv.data_ptr(), float(sigma), out.data_ptr())
+    return out
+
+
+def _loglik_args(t, theta, xa, y, obsvar, coeffvar, sigma):
+    """the checks of product_loglik on everything but the blocks"""
+    theta = np.asarray(theta, dtype=np.float64)
+    if theta.shape != (t.p,):
+        raise ValueError("theta must have p entries")
     y = np.asarray(y, dtype=np.float64)
-    na, nb = xa.shape[0], xb.shape[0]
+    na = xa.shape[0]
     if y.shape != (na,):
         raise ValueError("y must have one entry per row of xa")
     if not np.all(np.isfinite(y)):
@@ -137,8 +210,17 @@ def product_loglik(om, terms, theta, xa, y, xb, dims_b, obsvar=None, coeffvar=No
         coeffvar = np.asarray(coeffvar, dtype=np.float64)
         if coeffvar.shape != (t.p,):
             raise ValueError("coeffvar must have p entries")
-    if sigma is None:
-        sigma = math.log(0.01)
+    return theta, y, obsvar, coeffvar, math.log(0.01) if sigma is None else float(sigma)
+
+
+def product_loglik(om, terms, theta, xa, y, xb, dims_b, obsvar=None, coeffvar=None, sigma=None):
+    """(chi2, logdet), nb each, of the standardised field data y (na) at the settings xa for every candidate
+    row of xb: r = y - mean, v = var + obsvar (var = e^{2 sigma} without coeffvar) -- obhip_product_loglik_dev"""
+    import torch
+    t = obmod._terms_of(om, terms)
+    xa, xb, db = check_blocks(om.d, xa, xb, dims_b)
+    theta, y, obsvar, coeffvar, sigma = _loglik_args(t, theta, xa, y, obsvar, coeffvar, sigma)
+    na, nb = xa.shape[0], xb.shape[0]
     if na == 0 or nb == 0:
         return np.zeros(nb), np.zeros(nb)
     dev = _device()

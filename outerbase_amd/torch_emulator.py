@@ -17,6 +17,10 @@ if torch is None:  # host-only use of the package: the name exists, building one
     class TorchEmulator:
         def __init__(self, *args, **kwargs):
             raise ImportError("TorchEmulator needs torch")
+
+    class TorchCalibration:
+        def __init__(self, *args, **kwargs):
+            raise ImportError("TorchCalibration needs torch")
 else:
     def _colmajor(a):
         """the (rows, cols) tensor a as a contiguous (cols, rows) tensor: column-major storage of a"""
@@ -110,3 +114,60 @@ else:
             if x.device != self.theta.device:
                 raise ValueError("x is on another device than the emulator")
             return _Predict.apply(x, self)
+
+    class _CalibrationLoglik(torch.autograd.Function):
+        """loglik (nb) of the candidates t (nb x L) and, saved for backward, its gradient (nb x L): one
+        obhip_product_loglik_grad_dev call.  backward is cot[:, None] * grad; the gradient itself is not
+        differentiable (the library has no second derivatives on the product)."""
+
+        @staticmethod
+        def forward(ctx, t, cal):
+            from . import product
+            nb, L = t.shape
+            if nb == 0:
+                ctx.save_for_backward(torch.zeros_like(t))
+                return torch.zeros((0,), dtype=torch.float64, device=t.device)
+            out = product.product_loglik_grad_dev(cal._om, cal._t, cal.theta, cal.xa, cal.y, cal.obsvar, _colmajor(t),
+                                                  cal._db, cal.coeffvar, cal._sigma)
+            ctx.save_for_backward((-0.5 * (out[2:2 + L] + out[2 + L:])).t().contiguous())
+            return -0.5 * (out[0] + out[1]) + cal._shift
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, cot):
+            grad, = ctx.saved_tensors
+            return cot[:, None] * grad, None
+
+    class TorchCalibration(torch.nn.Module):
+        """The calibration log-likelihood of MultiFit.calibration_loglik as a torch module: forward(t) takes
+        the candidates t (nb x len(dims_t), float64 on the GPU) and returns loglik (nb), differentiable by t
+        once (backward = cot[:, None] * d loglik / d t, from the same obhip_product_loglik_grad_dev call), so
+        that nb chains or starting points move in one torch.optim loop.  The field data are uploaded once;
+        nothing passes through the host in forward or backward."""
+
+        def __init__(self, fit, x_field, y_field, dims_t, obs_var=None, response=0, emulator_var=True):
+            super().__init__()
+            from . import product
+            # (a one-row stand-in for the candidates: the checks of the blocks need only their width)
+            x_field, _, self._db = product.check_blocks(fit.om.d, x_field, np.zeros((1, np.size(dims_t))), dims_t)
+            y, ov = fit._field_data(x_field, y_field, obs_var, response)
+            y, ov = product._loglik_args(fit._t, fit.coeff[:, response], x_field, y, ov, None, fit.sigma)[1:3]
+            self._om, self._t, self._sigma = fit.om, fit._t, float(fit.sigma)
+            self.L, na = int(self._db.size), x_field.shape[0]
+            self._shift = -0.5 * (2.0 * na * float(np.log(fit.y_sca[response])) + na * float(np.log(2.0 * np.pi)))
+            dev = torch.device("cuda", torch.cuda.current_device())
+            up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+            self.register_buffer("theta", up(fit.coeff[:, response]))
+            self.register_buffer("xa", up(x_field.T).reshape(x_field.shape[1], na))   # column-major
+            self.register_buffer("y", up(y))
+            self.register_buffer("obsvar", up(ov))
+            self.register_buffer("coeffvar", up(1.0 / fit.diagH) if emulator_var else None)
+
+        def forward(self, t):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64:
+                raise TypeError("TorchCalibration takes a float64 tensor on the GPU")
+            if t.dim() != 2 or t.shape[1] != self.L:
+                raise ValueError("t must be nb x len(dims_t)")
+            if t.device != self.theta.device:
+                raise ValueError("t is on another device than the calibration")
+            return _CalibrationLoglik.apply(t, self)
