@@ -719,6 +719,32 @@ int obhip_interaction_effect_dev(const obhip_model *m, const obhip_terms *t, uin
 /* host-buffer form: out q x 2 n_pairs, G (may be NULL) q x n_G */
 int obhip_sobol2(const obhip_terms *t, const double *Theta, uint64_t q, const double *mean_tab,
                  const double *cov_tab, double *out, double *G);
+/* One number per input that sums to V: the Shapley effect Sh_l = sum_{u contains l} V_u / |u| (Owen 2014), V_u the
+ * variance of the ANOVA term of the subset u.  Players are groups of dimensions, a partition of 0 .. d-1 into P
+ * groups; per term pair (k, k'), with c_i = C_i[t,t'], mm_i = m_i[t] m_i[t'], A_i = c_i + mm_i, a player g has
+ *   mm_g = prod_{i in g} mm_i,   c_g = prod_{i in g} A_i - prod_{i in g} mm_i   (by D <- c_i PA + mm_i D,
+ *                                                                                PA <- PA A_i: no cancellation)
+ *   Sh_g = sum_{k,k'} theta_k theta_k' c_g int_0^1 prod_{h != g} (mm_h + s c_h) ds,   sum_g Sh_g = V
+ * The integrand is a polynomial of degree P - 1 in s: the Gauss-Legendre rule of ceil(P / 2) nodes on [0,1] is
+ * exact, its weights are positive and nothing is divided.  The limits are those of obhip_sobol_dev and at most 40
+ * players (more dimensions than that must be grouped), refused with a message before any device call; fixed
+ * summation order, no atomics: the same bits on every call. */
+/* Host only: the Gauss-Legendre rule of G nodes on [0,1], 1 <= G <= 128 (OBHIP_ERR_INVALID otherwise), nodes
+ * ascending, weights summing to 1; computed in long double and rounded once. */
+int obhip_gauss_legendre01(uint64_t G, double *nodes, double *weights);
+/* groups: d player ids on the host, exactly 0 .. P-1 with every id used, or NULL: dimension l is player l.
+ * *n_players = P, *n_nodes = ceil(P / 2) (either may be NULL); P > 40 is OBHIP_ERR_INVALID. */
+int obhip_shapley_layout(const obhip_terms *t, const int32_t *groups, uint64_t *n_players,
+                         uint64_t *n_nodes);
+int obhip_shapley_workspace_bytes(uint64_t p, uint64_t d, uint64_t q, uint64_t *bytes);
+/* d_Theta and the tables as obhip_sobol_dev takes them (every C_l symmetric).  d_out: q x P row-major, in
+ * variance units, player g at column g.  d_ws: obhip_shapley_workspace_bytes(p, d, q). */
+int obhip_shapley_dev(const obhip_terms *t, const int32_t *groups, const double *d_Theta, uint64_t q,
+                      const double *d_mean_tab, const double *d_cov_tab, double *d_out, void *d_ws,
+                      uint64_t ws_bytes);
+/* host-buffer form: out q x P */
+int obhip_shapley(const obhip_terms *t, const int32_t *groups, const double *Theta, uint64_t q,
+                  const double *mean_tab, const double *cov_tab, double *out);
 
 /* ---- streaming Newton fit: rows come and go, one pass over each (no reference counterpart) ----
  * obfit (R/fitting.R:40-120) and every fit entry above take all rows at once and form the whole

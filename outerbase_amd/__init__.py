@@ -15,8 +15,8 @@ from .obmod import (covf, covf_mat25, covf_mat25ang, covf_mat25pow, gethyp, getp
 from .fitting import BFGS_lpdf, BFGS_std, obfit, obpred, obpred_grad
 from .multi import MultiFit, fit_newton_multi
 from .glm import GlmFit, fit_glm
-from .sensitivity import (InputMoments, Sobol2Result, SobolResult, input_moments, interaction_effects, main_effects,
-                          sobol, sobol2, uniform_nodes)
+from .sensitivity import (InputMoments, ShapleyResult, Sobol2Result, SobolResult, input_moments, interaction_effects,
+                          main_effects, shapley, sobol, sobol2, uniform_nodes)
 from .design import AcquireResult, DesignResult, Posterior, ThompsonResult
 from .torch_emulator import TorchCalibration, TorchEmulator
 from .product import (CalibrationLoglik, predict_product, predict_product_grad, product_grad_layout, product_layout,
@@ -38,7 +38,7 @@ __all__ = [
     "GlmFit", "fit_glm",
     "Posterior", "DesignResult", "ThompsonResult", "AcquireResult",
     "InputMoments", "SobolResult", "input_moments", "uniform_nodes", "sobol", "main_effects",
-    "Sobol2Result", "sobol2", "interaction_effects",
+    "Sobol2Result", "sobol2", "interaction_effects", "ShapleyResult", "shapley",
     "predict_product", "product_loglik", "product_layout", "CalibrationLoglik",
     "predict_product_grad", "product_loglik_grad", "product_grad_layout", "TorchCalibration",
 ]

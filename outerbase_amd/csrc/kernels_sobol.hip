@@ -33,6 +33,7 @@
 //   L_i x L_j contraction with G_ij of every response.
 #include "obhip_internal.h"
 #include "device_common.h"
+#include "sobol_device.h"
 
 namespace obhip {
 
@@ -78,12 +79,6 @@ __device__ __forceinline__ int cov_offset(const DimDesc *__restrict__ dims, int 
   int o = 0;
   for (int i = 0; i < l; ++i) o += dims[i].ncol * dims[i].ncol;
   return o;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 // part[k] = sum over the block of acc[k]: butterfly per wave, the waves in order

@@ -897,6 +897,29 @@ int launch_sobol2_pairs(const uint8_t *d_lev, const int *d_meta, const int *d_pa
 int launch_interaction_effect(const obhip_model &m, obhip_terms &t, uint64_t di, uint64_t dj, const double *d_Gij,
                               uint64_t n_G, uint64_t q, const double *d_grid_i, uint64_t Gi, const double *d_grid_j,
                               uint64_t Gj, double *d_out);
+// kernels_shapley.hip: Shapley effects of players (groups of dimensions), DESIGN.md section 29
+constexpr int kShapMaxPlayers = 40;                   // = the register slots of the widest instantiation
+constexpr int kShapMaxNodes = kShapMaxPlayers / 2;    // Gauss-Legendre nodes: ceil(P / 2)
+inline int shapley_slots(uint64_t d) { return d <= 8 ? 8 : d <= 24 ? 24 : 40; }  // NS: register slots per pair
+inline int shapley_rc(uint64_t d) { return d <= 24 ? 2 : 1; }                     // responses per chunk at that NS
+// What the pair kernel sweeps, passed by value (kernel arguments: scalar loads).  The dimensions in sweep order
+// `perm`, every player's dimensions contiguous; slot s < ns holds a run of that order, all of one player: its last
+// dimension regdim[s], whose row offset is in a register of the lane, behind nmem (a byte per slot, four to a
+// word) dimensions that are read per pair.  Bit s of lastmask: the player ends at slot s and its effect is
+// accumulated there; slot[g]: that slot.
+struct ShapPlan {
+  double node[kShapMaxNodes], wt[kShapMaxNodes];
+  unsigned long long lastmask;
+  uint32_t nmem[kShapMaxPlayers / 4];
+  int ns, nnode, nplayers;
+  uint8_t perm[256], regdim[kShapMaxPlayers], slot[kShapMaxPlayers];
+};
+size_t shapley_pairs_lds(uint64_t d, uint64_t n_cov);               // dynamic LDS of k_shapley_pairs
+uint64_t shapley_part_doubles(uint64_t p, uint64_t d, uint64_t q);  // partials of its pair sum
+// d_out: q x nplayers row-major
+int launch_shapley_pairs(const ShapPlan &plan, const uint8_t *d_lev, const int *d_meta, uint64_t p, uint64_t d,
+                         uint64_t q, uint64_t n_cov, const double *d_Theta, const double *d_mtab, const double *d_ctab,
+                         double *d_part, double *d_out);
 // ---- runtime value -> template argument -----------------------------------------------------------
 // pick_or<1, 2, 4, 8>(ng, miss, [&](auto NG) { ... NG() ... }): the lambda is called with the
 // std::integral_constant of the listed value that v equals and its result returned; `miss` when v

@@ -1,7 +1,11 @@
 // Variance-based sensitivity of the fitted mean: the entry points (include/obhip.h, "variance-based
-// sensitivity").  No reference counterpart.  The kernels and their launches are in kernels_sobol.hip.
+// sensitivity").  No reference counterpart.  The kernels and their launches are in kernels_sobol.hip and
+// kernels_shapley.hip.
 // Every check that can refuse a call runs before the first device call.
 #include "obhip_internal.h"
+
+#include <cfloat>
+#include <cmath>
 
 using namespace obhip;
 
@@ -82,6 +86,62 @@ int ensure_sobol_pairs(obhip_terms &t) {
       go += ((int)t.maxlev[i] + 1) * ((int)t.maxlev[j] + 1);
     }
   return t.sobol_pairs.upload(pr.data(), pr.size());
+}
+
+// The players of a call and the sweep the pair kernel makes over them (ShapPlan, obhip_internal.h); refuses ids
+// that are not exactly 0 .. P-1 and more players than the kernel has slots.  groups == NULL: player l = dimension l.
+int shapley_plan(const char *who, const obhip_terms &t, const int32_t *groups, ShapPlan &plan) {
+  const uint64_t d = t.d;
+  std::vector<int> gid(d);
+  uint64_t P = 0;
+  for (uint64_t l = 0; l < d; ++l) {
+    gid[l] = groups ? groups[l] : (int)l;
+    if (gid[l] < 0 || (uint64_t)gid[l] >= d)
+      return fail(OBHIP_ERR_INVALID, std::string(who) + ": player id of dimension " + std::to_string(l) +
+                                         " outside 0 .. d-1");
+    P = std::max<uint64_t>(P, (uint64_t)gid[l] + 1);
+  }
+  std::vector<int> count(P, 0);
+  for (uint64_t l = 0; l < d; ++l) ++count[gid[l]];
+  for (uint64_t g = 0; g < P; ++g)
+    if (!count[g])
+      return fail(OBHIP_ERR_INVALID, std::string(who) + ": player ids must be 0 .. P-1 without a gap; " +
+                                         std::to_string(g) + " is not used");
+  if (P > (uint64_t)kShapMaxPlayers)
+    return fail(OBHIP_ERR_INVALID, std::string(who) + ": " + std::to_string(P) + " players, at most " +
+                                       std::to_string(kShapMaxPlayers) + " (group the dimensions)");
+  plan = ShapPlan{};
+  plan.nplayers = (int)P;
+  plan.nnode = (int)((P + 1) / 2);
+  OB_TRY(obhip_gauss_legendre01((uint64_t)plan.nnode, plan.node, plan.wt));
+  // the sweep order: by player, a player's dimensions ascending
+  uint64_t pos = 0;
+  std::vector<uint8_t> is_last(d, 0);
+  for (uint64_t g = 0; g < P; ++g) {
+    for (uint64_t l = 0; l < d; ++l)
+      if ((uint64_t)gid[l] == g) plan.perm[pos++] = (uint8_t)l;
+    is_last[pos - 1] = 1;
+  }
+  // d <= NS: every dimension has a slot.  Beyond, the first d - NS dimensions that do not end a player are read
+  // per pair, in front of the next slot (there are d - P >= d - NS of them)
+  const uint64_t ns = std::min<uint64_t>(d, (uint64_t)shapley_slots(d));
+  uint64_t nomem = d - ns, s = 0, run = 0;
+  for (pos = 0; pos < d; ++pos) {
+    if (nomem && !is_last[pos]) {
+      --nomem, ++run;
+      continue;
+    }
+    plan.regdim[s] = plan.perm[pos];
+    plan.nmem[s / 4] |= (uint32_t)run << (8 * (s % 4));
+    run = 0;
+    if (is_last[pos]) {
+      plan.lastmask |= 1ull << s;
+      plan.slot[gid[plan.perm[pos]]] = (uint8_t)s;
+    }
+    ++s;
+  }
+  plan.ns = (int)ns;
+  return 0;
 }
 
 }  // namespace
@@ -188,6 +248,78 @@ int obhip_sobol2_dev(const obhip_terms *t, const double *d_Theta, uint64_t q, co
                               pl.gmax, d_Theta, d_mean_tab, d_cov_tab, d_out, d_G));
   return launch_sobol2_pairs(tt.sobol_lev.p, tt.sobol_meta.p, tt.sobol_pairs.p, t->p, t->d, q, lay.n_cov, d_Theta,
                              d_mean_tab, d_cov_tab, (double *)d_ws, d_out);
+}
+
+int obhip_gauss_legendre01(uint64_t G, double *nodes, double *weights) {
+  if (G == 0 || G > 128 || !nodes || !weights)
+    return fail(OBHIP_ERR_INVALID, "gauss_legendre01: 1 to 128 nodes, and somewhere to put them");
+  // Newton on Q_G(s) = (-1)^G P_G(2 s - 1) for the nodes below 1/2, the others by symmetry.  The recurrence runs
+  // on the differences D_k = Q_k - Q_{k-1}, (k + 1) D_{k+1} = k D_k - 2 (2 k + 1) s Q_k, which takes s itself and
+  // never forms 2 s - 1: a node near 0 keeps its relative accuracy.  w = 1 / (s (1 - s) Q_G'(s)^2).
+  const long double pi = 3.141592653589793238462643383279502884L;
+  for (uint64_t i = 0; i < (G + 1) / 2; ++i) {
+    const long double th = pi * ((long double)i + 0.75L) / ((long double)G + 0.5L), sh = sinl(0.5L * th);
+    long double s = sh * sh, dq = 0.0L;
+    if (2 * i + 1 == G) s = 0.5L;
+    for (int it = 0; it < 100; ++it) {
+      long double q = 1.0L, dk = 0.0L, ddk = 0.0L;
+      dq = 0.0L;
+      for (uint64_t k = 0; k < G; ++k) {
+        const long double kk = (long double)k;
+        const long double dn = (kk * dk - 2.0L * (2.0L * kk + 1.0L) * s * q) / (kk + 1.0L);
+        const long double ddn = (kk * ddk - 2.0L * (2.0L * kk + 1.0L) * (q + s * dq)) / (kk + 1.0L);
+        q += dn, dq += ddn, dk = dn, ddk = ddn;
+      }
+      if (2 * i + 1 == G) break;                         // (the middle node of an odd rule is 1/2 itself)
+      const long double step = q / dq;
+      s -= step;
+      if (fabsl(step) <= 4.0L * LDBL_EPSILON * s) break;
+    }
+    const long double w = 1.0L / (s * (1.0L - s) * dq * dq);
+    nodes[i] = (double)s, weights[i] = (double)w;
+    nodes[G - 1 - i] = (double)(1.0L - s), weights[G - 1 - i] = (double)w;
+  }
+  return 0;
+}
+
+int obhip_shapley_layout(const obhip_terms *t, const int32_t *groups, uint64_t *n_players, uint64_t *n_nodes) {
+  if (!t) return fail(OBHIP_ERR_INVALID, "shapley_layout: null terms");
+  Layout lay;
+  OB_TRY(sobol_layout("shapley_layout", *t, lay));
+  ShapPlan plan;
+  OB_TRY(shapley_plan("shapley_layout", *t, groups, plan));
+  if (n_players) *n_players = (uint64_t)plan.nplayers;
+  if (n_nodes) *n_nodes = (uint64_t)plan.nnode;
+  return 0;
+}
+
+int obhip_shapley_workspace_bytes(uint64_t p, uint64_t d, uint64_t q, uint64_t *bytes) {
+  if (!bytes || p == 0 || d == 0 || d > 255 || q == 0 || q > kSobolMaxQ || p > (1ull << 24))
+    return fail(OBHIP_ERR_INVALID, "shapley_workspace_bytes: null bytes, or p, d, q out of range");
+  *bytes = align256(shapley_part_doubles(p, d, q) * sizeof(double));
+  return 0;
+}
+
+int obhip_shapley_dev(const obhip_terms *t, const int32_t *groups, const double *d_Theta, uint64_t q,
+                      const double *d_mean_tab, const double *d_cov_tab, double *d_out, void *d_ws, uint64_t ws_bytes) {
+  if (!t || !d_Theta || !d_mean_tab || !d_cov_tab || !d_out || !d_ws)
+    return fail(OBHIP_ERR_INVALID, "shapley_dev: null terms, Theta, tables, out or workspace");
+  if (q == 0 || q > kSobolMaxQ) return fail(OBHIP_ERR_INVALID, "shapley_dev: 1 to 65535 responses");
+  Layout lay;
+  OB_TRY(sobol_layout("shapley_dev", *t, lay));  // (tables that fit k_sobol_pairs fit k_shapley_pairs: two of three)
+  if (shapley_pairs_lds(t->d, lay.n_cov) > kLdsBudget)
+    return fail(OBHIP_ERR_INVALID, "shapley_dev: the tables of these terms do not fit the LDS of a workgroup");
+  ShapPlan plan;
+  OB_TRY(shapley_plan("shapley_dev", *t, groups, plan));
+  uint64_t need = 0;
+  OB_TRY(obhip_shapley_workspace_bytes(t->p, t->d, q, &need));
+  if (ws_bytes < need)
+    return fail(OBHIP_ERR_INVALID, "shapley_dev: workspace smaller than obhip_shapley_workspace_bytes");
+  OB_TRY(require_device());
+  obhip_terms &tt = *const_cast<obhip_terms *>(t);
+  OB_TRY(ensure_sobol_tables(tt));
+  return launch_shapley_pairs(plan, tt.sobol_lev.p, tt.sobol_meta.p, t->p, t->d, q, lay.n_cov, d_Theta, d_mean_tab,
+                              d_cov_tab, (double *)d_ws, d_out);
 }
 
 int obhip_interaction_effect_dev(const obhip_model *m, const obhip_terms *t, uint64_t dim_i, uint64_t dim_j,
@@ -300,6 +432,29 @@ int obhip_sobol2(const obhip_terms *t, const double *Theta, uint64_t q, const do
   OB_TRY(d2h(out, dout.p, q * 2 * pl.n_pairs * sizeof(double)));
   if (G) OB_TRY(d2h(G, dg.p, q * pl.n_G * sizeof(double)));
   return 0;
+}
+
+int obhip_shapley(const obhip_terms *t, const int32_t *groups, const double *Theta, uint64_t q, const double *mean_tab,
+                  const double *cov_tab, double *out) {
+  if (!t || !Theta || !mean_tab || !cov_tab || !out)
+    return fail(OBHIP_ERR_INVALID, "shapley: null terms, Theta, tables or out");
+  if (q == 0 || q > kSobolMaxQ) return fail(OBHIP_ERR_INVALID, "shapley: 1 to 65535 responses");
+  Layout lay;
+  OB_TRY(sobol_layout("shapley", *t, lay));
+  ShapPlan plan;
+  OB_TRY(shapley_plan("shapley", *t, groups, plan));
+  uint64_t wsb = 0;
+  OB_TRY(obhip_shapley_workspace_bytes(t->p, t->d, q, &wsb));
+  OB_TRY(require_device());
+  DevBuf<double> dth, dm, dc, dout;
+  DevBuf<char> ws;
+  OB_TRY(dth.upload(Theta, t->p * q));
+  OB_TRY(dm.upload(mean_tab, lay.n_mean));
+  OB_TRY(dc.upload(cov_tab, lay.n_cov));
+  OB_TRY(dout.alloc(q * (uint64_t)plan.nplayers));
+  OB_TRY(ws.alloc(wsb));
+  OB_TRY(obhip_shapley_dev(t, groups, dth.p, q, dm.p, dc.p, dout.p, ws.p, wsb));
+  return d2h(out, dout.p, q * (uint64_t)plan.nplayers * sizeof(double));
 }
 
 }  // extern "C"

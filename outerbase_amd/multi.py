@@ -233,6 +233,18 @@ class MultiFit:
         res._mats(self.om.d)
         return res
 
+    def shapley(self, nodes, weights=None, groups=None):
+        """Shapley effects of every response under the product measure of nodes / weights, in raw units:
+        ShapleyResult with the variances times y_sca^2 and the shares unchanged (sensitivity.shapley)."""
+        from . import sensitivity
+        sensitivity._check_groups(self.om.d, groups)
+        mom = sensitivity.input_moments(self.om, self._t, nodes, weights)
+        res = sensitivity.shapley(self.om, self._t, self.coeff, mom, groups)
+        s2 = self.y_sca * self.y_sca
+        res.effect_var = res.effect_var * s2[None, :]
+        res.var = res.var * s2
+        return res
+
     def interaction_effects(self, dim_i, dim_j, grid_i, grid_j, nodes, weights=None):
         """the interaction surface of every response on grid_i x grid_j (Gi x Gj x q), in raw units (times y_sca)"""
         from . import sensitivity

@@ -1,4 +1,4 @@
-"""Sobol indices and main effects of the fitted mean, in closed form.
+"""Sobol indices, Shapley effects and main effects of the fitted mean, in closed form.
 
 The fitted mean is a sum of products of one-dimensional functions, f(x) = sum_k theta_k prod_l
 psi_{l, t_kl}(x_l) with psi_l = getbase(l).  Under independent inputs with a discrete measure per
@@ -91,6 +91,33 @@ class Sobol2Result:
     def _mats(self, d):
         for name in ("second_var", "total_interaction_var", "second", "total_interaction"):
             setattr(self, name + "_mat", _pair_matrix(getattr(self, name), self.pairs, d))
+
+
+class ShapleyResult:
+    """players: the list of dimension lists; effect_var (P x q): the Shapley effect of every player in variance
+    units; var (q): their column sums, the variance of the fitted mean; effect = effect_var / var (NaN where
+    var == 0), shares that sum to 1."""
+
+    def __init__(self, out, players):
+        self.players = players
+        self.effect_var = np.ascontiguousarray(out.T)
+        self.var = self.effect_var.sum(axis=0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.effect = self.effect_var / np.where(self.var == 0.0, np.nan, self.var)
+
+
+def _check_groups(d, groups):
+    """-> (players: list of dimension lists, ids: d int32 player ids or None for the default)"""
+    if groups is None:
+        return [[l] for l in range(d)], None
+    players = [[int(l) for l in g] for g in groups]
+    flat = [l for g in players for l in g]
+    if any(len(g) == 0 for g in players) or sorted(flat) != list(range(d)):
+        raise ValueError("groups must be non-empty lists of dimension indices that partition range(d)")
+    ids = np.empty(d, dtype=np.int32)
+    for g, dims in enumerate(players):
+        ids[dims] = g
+    return players, ids
 
 
 def _check_nodes(om, nodes, weights):
@@ -238,3 +265,25 @@ def interaction_effects(om, terms, Theta, moments, dim_i, dim_j, grid_i, grid_j)
          dzj.data_ptr(), Gj, out.data_ptr())
     surf = out.cpu().numpy().transpose(1, 2, 0)
     return surf - mi[:, None, :] - mj[None, :, :] - mu[None, None, :]
+
+
+def shapley(om, terms, Theta, moments, groups=None):
+    """ShapleyResult of the responses Theta (p x q, or p) under the measure of `moments`: one effect per player,
+    summing to the variance.  groups: lists of dimension indices that partition range(d), each list one player;
+    None: every dimension its own player -- obhip_shapley_dev."""
+    t = obmod._terms_of(om, terms)
+    Theta = _check_theta(t, Theta)
+    players, ids = _check_groups(t.d, groups)
+    q, d = Theta.shape[1], t.d
+    gp = None if ids is None else ids.ctypes.data
+    P, wsb = C.c_uint64(0), C.c_uint64(0)
+    call("obhip_shapley_layout", t._h, gp, C.byref(P), None)
+    call("obhip_shapley_workspace_bytes", t.p, d, q, C.byref(wsb))
+    torch, dev = _device()
+    dth = torch.from_numpy(np.ascontiguousarray(Theta.T)).to(dev)
+    ws = torch.empty(wsb.value, dtype=torch.uint8, device=dev)
+    out = torch.empty((q, P.value), dtype=torch.float64, device=dev)
+    call("obhip_shapley_dev", t._h, gp, dth.data_ptr(), q, moments.mean_dev.data_ptr(), moments.cov_dev.data_ptr(),
+         out.data_ptr(), ws.data_ptr(), wsb.value)
+    torch.cuda.synchronize()
+    return ShapleyResult(out.cpu().numpy(), players)
