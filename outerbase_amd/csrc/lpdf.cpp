@@ -27,14 +27,17 @@ int h2d(void *dst, const void *src, size_t bytes) {  // src may be a temporary: 
   return 0;
 }
 
-// var(y) with the n - 1 denominator (arma::var, loglik_std.cpp:51)
+// var(y) with the n - 1 denominator (arma::var, loglik_std.cpp:51).  One row has no variance: NaN, as
+// Loglik::set_comm gives for one row over all ranks.  This knowingly differs from the reference, whose
+// arma::var of one element is 0 and whose para0 is then log(0) = -inf; neither value is a usable noise
+// level, and the object works once updatepara has given it one.
 double sample_var(const double *y, uint64_t n) {
   double m = 0;
   for (uint64_t i = 0; i < n; ++i) m += y[i];
   m /= (double)n;
   double s = 0;
   for (uint64_t i = 0; i < n; ++i) s += (y[i] - m) * (y[i] - m);
-  return n > 1 ? s / (double)(n - 1) : 0.0;
+  return n > 1 ? s / (double)(n - 1) : std::numeric_limits<double>::quiet_NaN();
 }
 
 }  // namespace
@@ -392,6 +395,8 @@ struct Loglik : obhip_lpdf {
   }
   virtual int set_comm(obhip_comm *c) {
     comm = c;
+    // what was summed under the old sharding (sqcs holds the sum over the ranks) is not the sum under this one
+    dhg_valid = sqcs_valid = false;
     // var(y) over ALL rows, two-pass like R's var() (para0 = log(0.01 var(y)) must be the same on
     // every rank): (sum y, n) summed -> mean, then sum (y - mean)^2 summed.  (The one-pass form
     // sum y^2 - n mean^2 of round 2 lost eps (mean / sd)^2 relative.)
@@ -923,13 +928,17 @@ struct LpdfVec : obhip_lpdf {
     if (!lik || !pr || lik->kind != OBHIP_LPDF_LOGLIK_STD)
       return fail(OBHIP_ERR_STATE, "full-Hessian marginal adjustment needs loglik_std + logpr_gauss");
     const uint64_t p = nterms;
-    std::vector<double> H(p * p), gh(nhyp()), gp(2);
+    const uint64_t nh = nhyp();
+    std::vector<double> H(p * p), rows(nh + 1), prior(nh + 1);
     OB_TRY(d2h(H.data(), hessv.p, p * p * sizeof(double)));
-    OB_TRY(obhip_margadj_full(lik->ob, lik->t, om, H.data(), lik->para[0], pr->para[0], &val_margadj,
-                              gh.data(), gp.data()));
-    gradhyp_margadj = gh;
+    OB_TRY(margadj_full_parts(lik->ob, lik->t, om, H.data(), lik->para[0], pr->para[0], &val_margadj, rows.data(),
+                              prior.data()));
+    // the traces run over the rows: with a row-sharded likelihood they are summed over the ranks (H already is)
+    OB_TRY(lik->sum_ranks(rows.data(), nh + 1));
+    gradhyp_margadj.resize(nh);
+    for (uint64_t h = 0; h < nh; ++h) gradhyp_margadj[h] = -0.5 * (2.0 * rows[h] - prior[h]);
     gradpara_margadj.assign(npara, 0.0);
-    for (int c = 0; c < 2; ++c) gradpara_margadj[parasrt[c]] = list[c] == lik ? gp[0] : gp[1];
+    for (int c = 0; c < 2; ++c) gradpara_margadj[parasrt[c]] = list[c] == lik ? rows[nh] : prior[nh];
     return 0;
   }
   int update(const double *c) override {  // fit.cpp:323-363

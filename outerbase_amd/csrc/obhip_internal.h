@@ -611,6 +611,12 @@ struct PostFactor {
 int post_factor_build(const double *d_H, uint64_t p, PostFactor &f, bool want_inverse);
 int post_var_dev(const obhip_model &m, obhip_terms &t, const PostFactor &f, const double *d_x,
                  uint64_t n, double e2sigma, double *d_var);
+// obhip_margadj_full in its two parts, so that a row-sharded likelihood can sum the first over its ranks:
+// rows[l] = e^{-2 sigma} tr(inv(H) B^T Bge_l) for l < nhyp and rows[nhyp] = e^{-2 sigma} tr(inv(H) B^T B) over
+// the rows of THIS basis, prior[l] = sum_k inv(H)_kk prec_k lvarge_kl and prior[nhyp] = sum_k inv(H)_kk prec_k
+// (both may be null: val only)
+int margadj_full_parts(const obhip_basis *b, const obhip_terms *t, const obhip_model *m, const double *H,
+                       double sigma, double rho, double *val, double *rows, double *prior);
 }  // namespace obhip
 // posterior.cpp: the device-resident posterior of one model and term set (include/obhip.h)
 struct obhip_posterior {

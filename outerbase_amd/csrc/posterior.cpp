@@ -127,12 +127,29 @@ extern "C" int obhip_predict_std(const obhip_model *m, const obhip_terms *tc, co
 extern "C" int obhip_margadj_full(const obhip_basis *bc, const obhip_terms *tc, const obhip_model *m,
                                   const double *H, double sigma, double rho, double *val,
                                   double *gradhyp, double *gradpara) {
+  if (!m) return fail(OBHIP_ERR_INVALID, "margadj_full: null argument");
+  const uint64_t nh = m->nhyp();
+  const bool grads = gradhyp || gradpara;
+  std::vector<double> rows(nh + 1), prior(nh + 1);
+  OB_TRY(margadj_full_parts(bc, tc, m, H, sigma, rho, val, grads ? rows.data() : nullptr,
+                            grads ? prior.data() : nullptr));
+  if (gradhyp)
+    for (uint64_t h = 0; h < nh; ++h) gradhyp[h] = -0.5 * (2.0 * rows[h] - prior[h]);
+  if (gradpara) {
+    gradpara[0] = rows[nh];   // -1/2 tr(inv(H) (-2 e^{-2 sigma} G)), loglik_std.cpp:199-203
+    gradpara[1] = prior[nh];  // -1/2 sum(-2 prec_k inv(H)_kk), logpr_gauss.cpp:181-186
+  }
+  return 0;
+}
+
+int obhip::margadj_full_parts(const obhip_basis *bc, const obhip_terms *tc, const obhip_model *m, const double *H,
+                              double sigma, double rho, double *val, double *rows, double *prior) {
   if (!bc || !tc || !m || !H || !val) return fail(OBHIP_ERR_INVALID, "margadj_full: null argument");
   if (bc->model != m) return fail(OBHIP_ERR_INVALID, "margadj_full: basis belongs to another model");
   obhip_basis &b = *const_cast<obhip_basis *>(bc);
   obhip_terms &t = *const_cast<obhip_terms *>(tc);
   const uint64_t p = t.p, d = m->d, nh = m->nhyp();
-  const bool grads = gradhyp || gradpara;
+  const bool grads = rows && prior;
   DevBuf<double> dH;
   OB_TRY(dH.upload(H, p * p));
   PostFactor f;
@@ -186,20 +203,18 @@ extern "C" int obhip_margadj_full(const obhip_basis *bc, const obhip_terms *tc, 
     for (uint64_t l = 0; l < d; ++l) sv += m->basisvar[m->knotptst[l] + t.lev[k * d + l]];
     prec[k] = 1.0 / (std::exp(sv) * std::exp(2.0 * rho));
   }
-  if (gradhyp)
-    for (uint64_t h = 0; h < nh; ++h) {
-      const uint64_t l = m->hypmatch[h];
-      double pr = 0;
-      for (uint64_t k = 0; k < p; ++k)
-        pr += hinv[k] * prec[k] * m->logbasisvar_gradhyp[m->gest[h] + t.lev[k * d + l]];
-      gradhyp[h] = -0.5 * (2.0 * e2 * q[h] - pr);
-    }
-  if (gradpara) {
-    gradpara[0] = e2 * q[nh];  // -1/2 tr(inv(H) (-2 e^{-2 sigma} G)), loglik_std.cpp:199-203
+  for (uint64_t h = 0; h < nh; ++h) {
+    const uint64_t l = m->hypmatch[h];
     double pr = 0;
-    for (uint64_t k = 0; k < p; ++k) pr += hinv[k] * prec[k];
-    gradpara[1] = pr;          // -1/2 sum(-2 prec_k inv(H)_kk), logpr_gauss.cpp:181-186
+    for (uint64_t k = 0; k < p; ++k)
+      pr += hinv[k] * prec[k] * m->logbasisvar_gradhyp[m->gest[h] + t.lev[k * d + l]];
+    rows[h] = e2 * q[h];
+    prior[h] = pr;
   }
+  rows[nh] = e2 * q[nh];
+  double pr = 0;
+  for (uint64_t k = 0; k < p; ++k) pr += hinv[k] * prec[k];
+  prior[nh] = pr;
   return 0;
 }
 
