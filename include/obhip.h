@@ -863,6 +863,55 @@ int obhip_normal_acc_add_grad_dev(obhip_normal_acc *acc, const double *d_x, uint
 int obhip_normal_acc_grad_info(const obhip_normal_acc *acc, uint64_t *grad_equations,
                                uint64_t *grad_batches);
 
+/* ---- Newton fit on the product of two input blocks (no reference counterpart) ----
+ * Training data on a full grid: the na nb pairs (row i of xa, row j of xb) of "product of two input
+ * blocks" below, one response value per pair.  A design-matrix entry of the pair separates,
+ * B[(i,j),k] = At[i,k] Bt[j,k] with At = diag(sA) U (na x p) and Bt = diag(sB) V (nb x p), and so do
+ * the normal equations:
+ *   B^T B = (At^T At) o (Bt^T Bt)   (Hadamard product),   B^T 1 = (At^T 1) o (Bt^T 1),
+ *   (B^T y)_k = sum_i At[i,k] (Y Bt)[i,k].
+ * The two side matrices are staged (one kernel per side; fused while the side's terms use at most 8
+ * factors and its tile fits 160 KB of LDS, from a pooled HBM tile per block beyond that and under
+ * OBHIP_FORCE_GENERIC), go through the Gram kernels of obhip_gram_dev as na + nb rows, and Y Bt is one
+ * matrix-core product with the long index j contracted in ascending row chunks.  Nothing of size
+ * na nb d or na nb p exists.  Y - c is formed by one subtraction per entry before anything is
+ * contracted; the batch moments are those of obhip_normal_acc_add_dev over the na nb values in the
+ * order i fast, j slow.  No atomics: two equal calls give the same bits.  Scratch: two packed
+ * triangles, the staged A side (64 ceil(na / 64) x p_pad doubles, whole), one staged chunk of the B
+ * side (at most a quarter of the free HBM and 16 GB; OBHIP_GRAM_CHUNK_ROWS sets the rows per chunk for
+ * tests), q copies of Y padded to multiples of (128, 64) and the product of one block of at most 8
+ * responses (128 ceil(na / 128) x p_pad doubles each).  When na is far larger than nb, name the
+ * complement as dims_b and swap the blocks: the B side is the one that is chunked.
+ * Every check runs before the first device call and a refused call leaves the state unchanged:
+ * OBHIP_ERR_INVALID for a null argument, a sign other than +1 / -1, dims_b not strictly ascending or
+ * out of range or with fewer than 1 or more than d - 1 entries, na = 0 or nb = 0 (a batch without
+ * rows cannot be told from a mistake here), lda < na, more than 2^31 rows in xa, 2^40 in xb or 2^48
+ * pairs, more than 65535 used basis columns on a side; OBHIP_ERR_STATE as obhip_normal_acc_add_dev.
+ * A batch is taken out with the dims_b it was added with: the accumulator does not remember the
+ * split, that is the caller's business. */
+/* sign = +1: add the na*nb observations of the grid (xa_i on the dimensions not in dims_b, xb_j on dims_b);
+ * sign = -1: take out a grid batch added before.  d_xa: column-major na x |A|, d_xb: column-major nb x |B|,
+ * dims_b (host) as obhip_predict_product_dev takes them (strictly ascending, 1..d-1 entries).
+ * d_Y_raw[(r*nb + j)*lda + i], lda >= na: the layout obhip_predict_product_dev writes its mean in; the
+ * padding lda - na is never read.  rows grows by na*nb and batches by 1; the shift of a fresh
+ * accumulator is Y_raw[r][0][0].  obhip_normal_acc_combine_dev, the `minus` of the solve and
+ * obhip_normal_acc_posterior_dev carry grid batches like any other rows.  No reference counterpart. */
+int obhip_normal_acc_add_product_dev(obhip_normal_acc *acc, const double *d_xa, uint64_t na,
+                                     const double *d_xb, uint64_t nb, const uint32_t *dims_b,
+                                     uint64_t ndims_b, const double *d_Y_raw, uint64_t lda, int sign);
+/* the staged side matrix itself: out[i*pitch + k] = s_i * prod of the term's factors on that side
+ * (side 0 = A at rows of xa, 1 = B at rows of xb; d_x column-major n x |side|), k < p, zeros up to
+ * pitch; d_out holds 64 ceil(n / 64) rows of pitch >= p doubles and the rows from n on are written as
+ * zeros: the layout the Gram kernels read.  n = 0 is a no-op.  For tests and callers that want the
+ * factors.  No reference counterpart. */
+int obhip_product_side_dev(const obhip_model *m, const obhip_terms *t, const uint32_t *dims_b,
+                           uint64_t ndims_b, int side, const double *d_x, uint64_t n,
+                           double *d_out, uint64_t pitch);
+/* host only: used columns of each side and whether the staging kernel keeps that side's tile in LDS
+ * (any pointer may be NULL).  No reference counterpart. */
+int obhip_product_fit_layout(const obhip_terms *t, const uint32_t *dims_b, uint64_t ndims_b,
+                             uint64_t *mu_a, uint64_t *mu_b, int *fused_a, int *fused_b);
+
 /* ---- predictor ---------------------------------------------------------- */
 /* predictor$update(x) + $mean() (+ $var() of pred_gauss):
  * loglik_gauss.cpp:214-227, loglik_std.cpp:239-248.  The basis at xnew is

@@ -19,8 +19,9 @@ from .sensitivity import (InputMoments, ShapleyResult, Sobol2Result, SobolResult
                           main_effects, shapley, sobol, sobol2, uniform_nodes)
 from .design import AcquireResult, DesignResult, Posterior, ThompsonResult
 from .torch_emulator import TorchCalibration, TorchEmulator
-from .product import (CalibrationLoglik, predict_product, predict_product_grad, product_grad_layout, product_layout,
-                      product_loglik, product_loglik_grad)
+from .product import (CalibrationLoglik, fit_newton_product, predict_product, predict_product_grad,
+                      product_fit_layout, product_grad_layout, product_layout, product_loglik, product_loglik_grad,
+                      product_side)
 from .driver import HotPath, MultiHotPath
 from .stream import (CVResult, NewtonAccumulator, cv_folds, cv_newton_multi, design_dx,
                      fit_newton_grad)
@@ -41,4 +42,5 @@ __all__ = [
     "Sobol2Result", "sobol2", "interaction_effects", "ShapleyResult", "shapley",
     "predict_product", "product_loglik", "product_layout", "CalibrationLoglik",
     "predict_product_grad", "product_loglik_grad", "product_grad_layout", "TorchCalibration",
+    "fit_newton_product", "product_side", "product_fit_layout",
 ]

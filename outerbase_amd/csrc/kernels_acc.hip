@@ -181,13 +181,21 @@ int launch_acc_batch_moments(const double *d_Y, uint64_t ldy, uint64_t n, uint64
 int launch_acc_fold(uint64_t p, uint64_t q, double *d_dst, const double *d_src, bool dst_empty, double sign) {
   ProfScope ps("acc_fold");
   hipStream_t st = cur_stream();
-  const uint64_t tri = p * (p + 1) / 2, nrb = p * (q + 1);
+  const uint64_t tri = p * (p + 1) / 2;
   const unsigned blocks = (unsigned)std::min<uint64_t>(8192, (tri / 2 + 255) / 256 + 1);
   hipLaunchKernelGGL(k_acc_fold, dim3(blocks), dim3(256), 0, st, d_dst, d_src, tri, sign);
-  hipLaunchKernelGGL(k_acc_fold_rhs, dim3((unsigned)((nrb + 255) / 256)), dim3(256), 0, st, d_dst + tri, d_src + tri, p,
-                     (int)q, (const double *)(d_dst + tri + nrb), d_src + tri + nrb, dst_empty ? 1 : 0, sign);
-  hipLaunchKernelGGL(k_acc_fold_mom, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, st, d_dst + tri + nrb,
-                     d_src + tri + nrb, (int)q, dst_empty ? 1 : 0, sign);
+  return launch_acc_fold_tail(p, q, d_dst + tri, d_src + tri, dst_empty, sign);
+}
+
+// [R | b1] and the moments alone (a grid batch folds its triangle from two factors: kernels_product_fit.hip)
+int launch_acc_fold_tail(uint64_t p, uint64_t q, double *d_dst_tail, const double *d_src_tail, bool dst_empty,
+                         double sign) {
+  hipStream_t st = cur_stream();
+  const uint64_t nrb = p * (q + 1);
+  hipLaunchKernelGGL(k_acc_fold_rhs, dim3((unsigned)((nrb + 255) / 256)), dim3(256), 0, st, d_dst_tail, d_src_tail, p,
+                     (int)q, (const double *)(d_dst_tail + nrb), d_src_tail + nrb, dst_empty ? 1 : 0, sign);
+  hipLaunchKernelGGL(k_acc_fold_mom, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, st, d_dst_tail + nrb,
+                     d_src_tail + nrb, (int)q, dst_empty ? 1 : 0, sign);
   OB_HIP(hipGetLastError());
   return 0;
 }

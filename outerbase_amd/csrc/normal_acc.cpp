@@ -6,6 +6,8 @@
 //   add / remove   the batch's Gram goes through launch_gram_to with a packed sink into scratch,
 //                  B^T [Y - c | 1] as fit_newton.cpp forms B^T Y (column 0 with the staging pass, the
 //                  others by bty_columns), then one fold with the sign;
+//   grid batch     the na nb pairs of two input blocks: the triangle from the Hadamard product of the two sides'
+//                  Grams, the rest as product_fit.cpp forms it;
 //   combine        the same fold of one accumulator into another;
 //   solve          H = e^{-2 sigma} (T - T_minus) + diag(prec) unpacked from the triangle(s), the
 //                  moments of the remaining rows and the right-hand sides standardised AFTER the sum,
@@ -32,8 +34,8 @@ struct obhip_normal_acc {
   uint64_t geq = 0, gbatches = 0;  // gradient equations (rows x differentiated dimensions) and their batches
   uint64_t version = 0;  // of the model when the first batch came in (rows > 0 or geq > 0)
   DevBuf<double> st;     // [tri][R p x q][b1 p][moments 4 q]
-  // lends the Gram of staged gradient rows its device, workspace and task-table cache; it never has rows
-  // of its own, and the staged buffer is never its bmat
+  // lends the Gram of staged rows (gradient rows, the sides of a grid batch) its device, workspace and task-table
+  // cache; it never has rows of its own, and the staged buffer is never its bmat
   std::unique_ptr<obhip_basis> gholder;
 };
 
@@ -74,6 +76,17 @@ int after_removal(obhip_normal_acc *a) {
     OB_HIP(hipMemsetAsync(a->st.p + head, 0, (a->st.n - head) * sizeof(double), cur_stream()));
     a->batches = 0;
   }
+  return 0;
+}
+
+// the basis that lends gram_of_staged its device, workspace and task-table cache
+int ensure_holder(obhip_normal_acc *a, const char *who) {
+  if (a->gholder) return 0;
+  a->gholder.reset(new (std::nothrow) obhip_basis());
+  if (!a->gholder) return fail(OBHIP_ERR_INVALID, std::string(who) + ": out of host memory");
+  a->gholder->model = a->model;
+  a->gholder->d = a->model->d;
+  (void)hipGetDevice(&a->gholder->device);
   return 0;
 }
 
@@ -199,13 +212,7 @@ int obhip_normal_acc_add_grad_dev(obhip_normal_acc *acc, const double *d_x, uint
     return fail(OBHIP_ERR_STATE, "normal_acc_add_grad_dev: removing " + std::to_string(eq) +
                                      " gradient equations from an accumulator that holds " + std::to_string(acc->geq));
   OB_TRY(require_device());
-  if (!acc->gholder) {
-    acc->gholder.reset(new (std::nothrow) obhip_basis());
-    if (!acc->gholder) return fail(OBHIP_ERR_INVALID, "normal_acc_add_grad_dev: out of host memory");
-    acc->gholder->model = acc->model;
-    acc->gholder->d = acc->model->d;
-    (void)hipGetDevice(&acc->gholder->device);
-  }
+  OB_TRY(ensure_holder(acc, "normal_acc_add_grad_dev"));
   const uint64_t p = acc->p, q = acc->q, tri = p * (p + 1) / 2;
   DevBuf<double> scratch;
   OB_TRY(scratch.alloc(tri + p * q));
@@ -221,6 +228,53 @@ int obhip_normal_acc_add_grad_dev(obhip_normal_acc *acc, const double *d_x, uint
   } else {
     acc->geq -= eq;
     acc->gbatches -= acc->gbatches > 0 ? 1 : 0;
+    OB_TRY(after_removal(acc));
+  }
+  return 0;
+}
+
+int obhip_normal_acc_add_product_dev(obhip_normal_acc *acc, const double *d_xa, uint64_t na, const double *d_xb,
+                                     uint64_t nb, const uint32_t *dims_b, uint64_t ndims_b, const double *d_Y_raw,
+                                     uint64_t lda, int sign) {
+  if (!acc || (sign != 1 && sign != -1))
+    return fail(OBHIP_ERR_INVALID, "normal_acc_add_product_dev: null accumulator, or a sign other than +1 / -1");
+  ProductSplit s;
+  OB_TRY(make_split("normal_acc_add_product_dev", *acc->terms, dims_b, ndims_b, s));
+  OB_TRY(check_side_columns("normal_acc_add_product_dev", s));
+  if (na == 0 || nb == 0) return fail(OBHIP_ERR_INVALID, "normal_acc_add_product_dev: a grid batch needs rows on both sides");
+  if (!d_xa || !d_xb || !d_Y_raw) return fail(OBHIP_ERR_INVALID, "normal_acc_add_product_dev: null xa, xb or Y");
+  if (lda < na) return fail(OBHIP_ERR_INVALID, "normal_acc_add_product_dev: lda below na");
+  if (na > (1ull << 31) || nb > (1ull << 40) || na * nb > (1ull << 48))
+    return fail(OBHIP_ERR_INVALID, "normal_acc_add_product_dev: more than 2^31 rows in xa, 2^40 in xb or 2^48 pairs");
+  OB_TRY(check_compat(acc->model, acc->terms));
+  OB_TRY(check_version(acc, "normal_acc_add_product_dev"));
+  const uint64_t n = na * nb;
+  if (sign < 0 && n > acc->rows)
+    return fail(OBHIP_ERR_STATE, "normal_acc_add_product_dev: removing " + std::to_string(n) +
+                                     " rows from an accumulator that holds " + std::to_string(acc->rows));
+  OB_TRY(require_device());
+  OB_TRY(ensure_holder(acc, "normal_acc_add_product_dev"));
+  const uint64_t p = acc->p, q = acc->q, tri = p * (p + 1) / 2, nrb = p * (q + 1);
+  const uint64_t tri2 = (tri + 1) & ~1ull;  // the second triangle on a 16-byte boundary as well
+  DevBuf<double> scratch;
+  OB_TRY(scratch.alloc(2 * tri2 + nrb + 4 * q));
+  const bool empty = acc->rows == 0;
+  double *s_ga = scratch.p, *s_gb = scratch.p + tri2, *s_tail = scratch.p + 2 * tri2;
+  OB_TRY(product_batch_normal_eq(*acc->gholder, *acc->model, *const_cast<obhip_terms *>(acc->terms), s, d_xa, na, d_xb, nb,
+                                 d_Y_raw, lda, q, empty, acc->st.p + tri + nrb, s_ga, s_gb, s_tail));
+  {
+    // B^T B = (At^T At) o (Bt^T Bt), folded from the two factors; [R | b1 | moments] as a row batch's
+    ProfScope ps("product_fit_fold");
+    OB_TRY(launch_acc_fold_hadamard(p, acc->st.p, s_ga, s_gb, (double)sign));
+    OB_TRY(launch_acc_fold_tail(p, q, acc->st.p + tri, s_tail, empty, (double)sign));
+  }
+  if (empty && acc->geq == 0) acc->version = acc->model->version;
+  if (sign > 0) {
+    acc->rows += n;
+    acc->batches += 1;
+  } else {
+    acc->rows -= n;
+    acc->batches -= acc->batches > 0 ? 1 : 0;
     OB_TRY(after_removal(acc));
   }
   return 0;

@@ -849,6 +849,67 @@ int launch_product_lik_grad_rows(const obhip_terms &t, const double *d_mean, con
                                  uint64_t j0, uint64_t nj, double *d_part);
 // d_out[w nb + j], w < ncols = the partials of the A tiles added in ascending order
 int launch_product_sum_tile_cols(const double *d_part, uint64_t tiles_a, uint64_t nb, uint64_t ncols, double *d_out);
+// product.cpp: the split of the dimensions and what follows from the levels alone (no device)
+struct ProductSplit {
+  std::vector<uint32_t> dims_b;
+  std::vector<int> side_a, side_b, dim_src;
+  std::vector<std::vector<char>> seen;  // per dimension: level used by some term
+  uint64_t mu_a = 1, mu_b = 1, wa = 2, wb = 2;
+  bool fused = false;
+};
+// dims_b: 1 to d - 1 entries, strictly ascending, each < d -- refused with OBHIP_ERR_INVALID otherwise
+int make_split(const char *who, const obhip_terms &t, const uint32_t *dims_b, uint64_t ndims_b, ProductSplit &s);
+// the device tables of the split (t.product), cached on the terms for the last split and column layout asked for
+int ensure_product_tables(const obhip_model &m, obhip_terms &t, const ProductSplit &s);
+// kernels_product_fit.hip / product_fit.cpp: the Newton fit on gridded data (include/obhip.h, "Newton fit on
+// the product of two input blocks").  One side's staged matrix:
+struct SideStage {
+  int side = 0;                     // 0: A (rows of xa), 1: B (rows of xb)
+  const double *x = nullptr;        // device, column-major with leading dimension ldx, n rows from x on
+  uint64_t ldx = 0, n = 0;
+  double *out = nullptr;            // out[i * pitch + k] = s_i prod of term k's factors on the side; rows n ..
+  uint64_t pitch = 0;               // 64 ceil(n / 64) and columns p .. pcols as zeros
+  uint64_t pcols = 0;
+  double *colpart = nullptr;        // optional: [ceil(n / 64)][pitch] column sums per tile
+};
+// the staging kernel keeps the side's tile in LDS: at most 8 factors per term on the side, tile within kLdsBudget
+bool materialize_side_supports(uint64_t mu, uint64_t w);
+// t.product and t.pred_md are prepared for the split (ensure_product_tables)
+int launch_materialize_side(const obhip_model &m, obhip_terms &t, const SideStage &s);
+// responses per GEMM of the right-hand sides: the product W2 of a block stays within 1 GB
+constexpr uint64_t kFitRespBlock = 8;
+inline uint64_t product_fit_resp_block(uint64_t na_pad, uint64_t p_pad, uint64_t q) {
+  return std::max<uint64_t>(1, std::min<uint64_t>(std::min(q, kFitRespBlock), (1ull << 27) / (na_pad * p_pad)));
+}
+// where Y[r][j][i] - c_r stands in the shifted copy: response blocks of rb, within a block [j][r][i] with i
+// padded to ldp and j to nbp rows (zeros), so that a block is the K x M operand of launch_atb with K = j
+__host__ __device__ inline uint64_t product_fit_ys_at(uint64_t r, uint64_t j, uint64_t i, uint64_t q, uint64_t rb,
+                                                     uint64_t nbp, uint64_t ldp) {
+  const uint64_t r0 = r / rb * rb, rc = (q - r0 < rb) ? q - r0 : rb;
+  return r0 * nbp * ldp + (j * rc + (r - r0)) * ldp + i;
+}
+// d_mom_batch[4 r] = the shift (the state's, or Y[r][0][0] for an empty state), d_Ys = Y - shift in the layout of
+// product_fit_ys_at, padding zeroed, then (mu, M2, n = na nb) per response in launch_acc_batch_moments' order
+// over the na nb values; the padding lda - na of Y is never read.  d_part: kSumBlocks q doubles
+int launch_product_fit_moments(const double *d_Y, uint64_t lda, uint64_t na, uint64_t nb, uint64_t q, uint64_t rb,
+                               uint64_t nbp, uint64_t ldp, bool empty, const double *d_mom_state, double *d_mom_batch,
+                               double *d_Ys, double *d_part);
+// d_part[(rr ns + s) pitch + k] = sum over the rows i of split s of A[i][k] W2[rr ldw + i][k] (rows ascending),
+// then d_R[(rr) p + k] (+)= the splits in ascending order; rc <= kFitRespBlock responses per pass over A
+uint64_t product_rhs_splits(uint64_t na);
+int launch_product_rhs_dot(const double *d_A, const double *d_W2, uint64_t pitch, uint64_t na, uint64_t ldw,
+                           uint64_t rc, uint64_t p, bool accumulate, double *d_part, double *d_R);
+// d_tri[e] += sign GA[e] GB[e] over the packed triangle, d_b1[k] = a1[k] b1[k]
+int launch_acc_fold_hadamard(uint64_t p, double *d_tri, const double *d_GA, const double *d_GB, double sign);
+int launch_hadamard(uint64_t p, const double *d_a, const double *d_b, double *d_out);
+// OBHIP_ERR_INVALID for a split with more than 65535 used columns on a side (the column lists are 16-bit)
+int check_side_columns(const char *who, const ProductSplit &s);
+// the normal equations of one grid batch: the two sides' Grams as packed triangles (d_GA, d_GB) and
+// [R | b1 | moments] in the accumulator's layout behind the triangle (d_tail); holder as grad_batch_normal_eq's
+int product_batch_normal_eq(obhip_basis &holder, const obhip_model &m, obhip_terms &t, const ProductSplit &s,
+                            const double *d_xa, uint64_t na, const double *d_xb, uint64_t nb, const double *d_Y,
+                            uint64_t lda, uint64_t q, bool empty, const double *d_mom_state, double *d_GA,
+                            double *d_GB, double *d_tail);
 // kernels_glm.hip: the row pass between two Newton steps of the GLM fit (glm.cpp) and the response scale
 // of its predictor.  eta_i = (eta ? eta[i] : o ? o[i] : 0) + (deta ? alpha deta[i] : 0); scale, scale_w and
 // u have n rounded up to a multiple of 64 entries; scale_w == nullptr: a trial pass, only the sums
@@ -1075,6 +1136,9 @@ int launch_acc_fold_grad(uint64_t p, uint64_t q, double *d_dst, const double *d_
 int launch_acc_batch_moments(const double *d_Y, uint64_t ldy, uint64_t n, uint64_t q, bool empty,
                              const double *d_mom_state, double *d_mom_batch, double *d_Ys, double *d_part);
 int launch_acc_fold(uint64_t p, uint64_t q, double *d_dst, const double *d_src, bool dst_empty, double sign);
+// launch_acc_fold behind the triangle: d_dst_tail / d_src_tail = [R | b1 | moments] of the two states
+int launch_acc_fold_tail(uint64_t p, uint64_t q, double *d_dst_tail, const double *d_src_tail, bool dst_empty,
+                         double sign);
 int launch_acc_rhs(uint64_t p, uint64_t q, const double *d_state, const double *d_minus, double e2, double *d_rhs,
                    double *d_meansd);
 int launch_cv_score(const double *d_mean, const double *d_Y, uint64_t n, uint64_t q, uint64_t ld,

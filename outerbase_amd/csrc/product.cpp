@@ -11,18 +11,9 @@
 
 using namespace obhip;
 
-namespace {
+namespace obhip {
 
-// the split of the dimensions and what follows from the levels alone (no device)
-struct Split {
-  std::vector<uint32_t> dims_b;
-  std::vector<int> side_a, side_b, dim_src;
-  std::vector<std::vector<char>> seen;  // per dimension: level used by some term
-  uint64_t mu_a = 1, mu_b = 1, wa = 2, wb = 2;
-  bool fused = false;
-};
-
-int make_split(const char *who, const obhip_terms &t, const uint32_t *dims_b, uint64_t ndims_b, Split &s) {
+int make_split(const char *who, const obhip_terms &t, const uint32_t *dims_b, uint64_t ndims_b, ProductSplit &s) {
   const uint64_t d = t.d, p = t.p;
   if (!dims_b || ndims_b < 1 || ndims_b + 1 > d)
     return fail(OBHIP_ERR_INVALID, std::string(who) + ": dims_b must name 1 to d - 1 dimensions");
@@ -65,9 +56,13 @@ int make_split(const char *who, const obhip_terms &t, const uint32_t *dims_b, ui
   return 0;
 }
 
+}  // namespace obhip
+
+namespace {
+
 // one side's tables against the column layout of t.pred_md: its used columns are numbered 1, 2, .. in the
 // order of the side's dimensions and, within a dimension, of the levels
-void side_tables(const obhip_terms &t, const Split &s, const std::vector<int> &side, uint64_t w,
+void side_tables(const obhip_terms &t, const ProductSplit &s, const std::vector<int> &side, uint64_t w,
                  std::vector<int32_t> &cpos, std::vector<uint16_t> &cols) {
   const std::vector<DimDesc> &dims = t.pred_md.dims_h;
   const uint64_t d = t.d, p = t.p;
@@ -94,8 +89,12 @@ void side_tables(const obhip_terms &t, const Split &s, const std::vector<int> &s
   }
 }
 
+}  // namespace
+
+namespace obhip {
+
 // the device tables of the split, cached on the terms for the last split and column layout asked for
-int ensure_product_tables(const obhip_model &m, obhip_terms &t, const Split &s) {
+int ensure_product_tables(const obhip_model &m, obhip_terms &t, const ProductSplit &s) {
   OB_TRY(prepare_predict(m, t, false));
   obhip_terms::Product &pr = t.product;
   if (pr.cols_a.p && pr.dims_b == s.dims_b && pr.cap == t.pred_md.cap) return 0;
@@ -116,7 +115,11 @@ int ensure_product_tables(const obhip_model &m, obhip_terms &t, const Split &s) 
   return 0;
 }
 
-bool take_fused(const Split &s) { return s.fused && !getenv("OBHIP_FORCE_GENERIC"); }
+}  // namespace obhip
+
+namespace {
+
+bool take_fused(const ProductSplit &s) { return s.fused && !getenv("OBHIP_FORCE_GENERIC"); }
 
 // The row route: the pairs in chunks (a range of A rows that is all of them or whole tiles, a range of B
 // rows) of at most kRowChunk doubles of scratch, written out as full-width rows for the row predictors.
@@ -161,7 +164,7 @@ int rows_predict(const obhip_model &m, obhip_terms &t, const ProductCall &c) {
   return 0;
 }
 
-int run_product(const obhip_model &m, obhip_terms &t, const Split &s, const ProductCall &c) {
+int run_product(const obhip_model &m, obhip_terms &t, const ProductSplit &s, const ProductCall &c) {
   OB_TRY(ensure_product_tables(m, t, s));
   return take_fused(s) ? launch_predict_product(m, t, c) : rows_predict(m, t, c);
 }
@@ -174,21 +177,21 @@ bool bad_obsvar(const double *v, uint64_t n) {
 
 // ---- gradient by xb ----------------------------------------------------------
 // sum_l |view_l|: the (term, B dimension) pairs with a factor, from the levels alone
-uint64_t view_terms_of(const obhip_terms &t, const Split &s) {
+uint64_t view_terms_of(const obhip_terms &t, const ProductSplit &s) {
   uint64_t n = 0;
   for (uint32_t l : s.dims_b)
     for (uint64_t k = 0; k < t.p; ++k) n += t.lev[k * t.d + l] > 0;
   return n;
 }
 
-bool grad_fused(const Split &s) {
+bool grad_fused(const ProductSplit &s) {
   return s.mu_a <= 65535 && s.mu_b <= 65535 && product_grad_supports(s.mu_a, s.mu_b, s.dims_b.size(), s.wa, s.wb);
 }
-bool take_grad_fused(const Split &s) { return grad_fused(s) && !getenv("OBHIP_FORCE_GENERIC"); }
+bool take_grad_fused(const ProductSplit &s) { return grad_fused(s) && !getenv("OBHIP_FORCE_GENERIC"); }
 
 // the tables of the split, the derivative interval tables and, for the fused kernel, the views of the B
 // dimensions, cached on the terms beside t.product for the last split and column layout asked for
-int ensure_product_grad_tables(const obhip_model &m, obhip_terms &t, const Split &s, bool fused) {
+int ensure_product_grad_tables(const obhip_model &m, obhip_terms &t, const ProductSplit &s, bool fused) {
   OB_TRY(ensure_product_tables(m, t, s));
   OB_TRY(ensure_dx_tables(m, t));
   if (!fused) return 0;
@@ -278,7 +281,7 @@ int rows_grad(const obhip_model &m, obhip_terms &t, const ProductGradCall &c) {
   return 0;
 }
 
-int run_product_grad(const obhip_model &m, obhip_terms &t, const Split &s, const ProductGradCall &c) {
+int run_product_grad(const obhip_model &m, obhip_terms &t, const ProductSplit &s, const ProductGradCall &c) {
   const bool fused = take_grad_fused(s);
   OB_TRY(ensure_product_grad_tables(m, t, s, fused));
   return fused ? launch_product_grad(m, t, c) : rows_grad(m, t, c);
@@ -291,7 +294,7 @@ extern "C" {
 int obhip_product_layout(const obhip_terms *t, const uint32_t *dims_b, uint64_t ndims_b, uint64_t *mu_a,
                          uint64_t *mu_b, int *fused) {
   if (!t) return fail(OBHIP_ERR_INVALID, "product_layout: null terms");
-  Split s;
+  ProductSplit s;
   OB_TRY(make_split("product_layout", *t, dims_b, ndims_b, s));
   if (mu_a) *mu_a = s.mu_a;
   if (mu_b) *mu_b = s.mu_b;
@@ -305,7 +308,7 @@ int obhip_predict_product_dev(const obhip_model *m, const obhip_terms *tc, const
                               const double *d_coeffvar, double sigma, double *d_var) {
   if (!m || !tc || !d_Theta || q == 0) return fail(OBHIP_ERR_INVALID, "predict_product_dev: null model, terms or Theta, or q = 0");
   OB_TRY(check_compat(m, tc));
-  Split s;
+  ProductSplit s;
   OB_TRY(make_split("predict_product_dev", *tc, dims_b, ndims_b, s));
   if (lda < na) return fail(OBHIP_ERR_INVALID, "predict_product_dev: lda below na");
   if (d_var && !d_coeffvar) return fail(OBHIP_ERR_INVALID, "predict_product_dev: d_var needs d_coeffvar");
@@ -324,7 +327,7 @@ int obhip_product_loglik_dev(const obhip_model *m, const obhip_terms *tc, const 
                              const double *d_coeffvar, double sigma, double *d_out) {
   if (!m || !tc || !d_theta) return fail(OBHIP_ERR_INVALID, "product_loglik_dev: null model, terms or theta");
   OB_TRY(check_compat(m, tc));
-  Split s;
+  ProductSplit s;
   OB_TRY(make_split("product_loglik_dev", *tc, dims_b, ndims_b, s));
   if (na == 0 || nb == 0) return 0;
   if (!d_xa || !d_xb || !d_y || !d_out) return fail(OBHIP_ERR_INVALID, "product_loglik_dev: null xa, xb, y or out");
@@ -350,7 +353,7 @@ int obhip_predict_product(const obhip_model *m, const obhip_terms *t, const doub
                           const double *coeffvar, double sigma, double *var) {
   if (!m || !t || !Theta || q == 0) return fail(OBHIP_ERR_INVALID, "predict_product: null model, terms or Theta, or q = 0");
   OB_TRY(check_compat(m, t));
-  Split s;
+  ProductSplit s;
   OB_TRY(make_split("predict_product", *t, dims_b, ndims_b, s));
   if (lda < na || ldxa < na || ldxb < nb) return fail(OBHIP_ERR_INVALID, "predict_product: leading dimension below the rows");
   if (var && !coeffvar) return fail(OBHIP_ERR_INVALID, "predict_product: var needs coeffvar");
@@ -384,7 +387,7 @@ int obhip_product_loglik(const obhip_model *m, const obhip_terms *t, const doubl
                          double sigma, double *out) {
   if (!m || !t || !theta) return fail(OBHIP_ERR_INVALID, "product_loglik: null model, terms or theta");
   OB_TRY(check_compat(m, t));
-  Split s;
+  ProductSplit s;
   OB_TRY(make_split("product_loglik", *t, dims_b, ndims_b, s));
   if (ldxa < na || ldxb < nb) return fail(OBHIP_ERR_INVALID, "product_loglik: leading dimension below the rows");
   if (na == 0 || nb == 0) return 0;
@@ -408,7 +411,7 @@ int obhip_product_loglik(const obhip_model *m, const obhip_terms *t, const doubl
 int obhip_product_grad_layout(const obhip_terms *t, const uint32_t *dims_b, uint64_t ndims_b, uint64_t *mu_a,
                               uint64_t *mu_b, uint64_t *view_terms, int *fused) {
   if (!t) return fail(OBHIP_ERR_INVALID, "product_grad_layout: null terms");
-  Split s;
+  ProductSplit s;
   OB_TRY(make_split("product_grad_layout", *t, dims_b, ndims_b, s));
   if (mu_a) *mu_a = s.mu_a;
   if (mu_b) *mu_b = s.mu_b;
@@ -423,7 +426,7 @@ int obhip_predict_product_grad_dev(const obhip_model *m, const obhip_terms *tc, 
                                    const double *d_coeffvar, double sigma, double *d_dvar) {
   if (!m || !tc || !d_theta) return fail(OBHIP_ERR_INVALID, "predict_product_grad_dev: null model, terms or theta");
   OB_TRY(check_compat(m, tc));
-  Split s;
+  ProductSplit s;
   OB_TRY(make_split("predict_product_grad_dev", *tc, dims_b, ndims_b, s));
   if (lda < na) return fail(OBHIP_ERR_INVALID, "predict_product_grad_dev: lda below na");
   if (d_dvar && !d_coeffvar) return fail(OBHIP_ERR_INVALID, "predict_product_grad_dev: d_dvar needs d_coeffvar");
@@ -442,7 +445,7 @@ int obhip_product_loglik_grad_dev(const obhip_model *m, const obhip_terms *tc, c
                                   const double *d_coeffvar, double sigma, double *d_out) {
   if (!m || !tc || !d_theta) return fail(OBHIP_ERR_INVALID, "product_loglik_grad_dev: null model, terms or theta");
   OB_TRY(check_compat(m, tc));
-  Split s;
+  ProductSplit s;
   OB_TRY(make_split("product_loglik_grad_dev", *tc, dims_b, ndims_b, s));
   if (na == 0 || nb == 0) return 0;
   if (!d_xa || !d_xb || !d_y || !d_out)
@@ -470,7 +473,7 @@ int obhip_predict_product_grad(const obhip_model *m, const obhip_terms *t, const
                                uint64_t lda, const double *coeffvar, double sigma, double *dvar) {
   if (!m || !t || !theta) return fail(OBHIP_ERR_INVALID, "predict_product_grad: null model, terms or theta");
   OB_TRY(check_compat(m, t));
-  Split s;
+  ProductSplit s;
   OB_TRY(make_split("predict_product_grad", *t, dims_b, ndims_b, s));
   if (lda < na || ldxa < na || ldxb < nb)
     return fail(OBHIP_ERR_INVALID, "predict_product_grad: leading dimension below the rows");
@@ -506,7 +509,7 @@ int obhip_product_loglik_grad(const obhip_model *m, const obhip_terms *t, const 
                               uint64_t ldxb, const double *coeffvar, double sigma, double *out) {
   if (!m || !t || !theta) return fail(OBHIP_ERR_INVALID, "product_loglik_grad: null model, terms or theta");
   OB_TRY(check_compat(m, t));
-  Split s;
+  ProductSplit s;
   OB_TRY(make_split("product_loglik_grad", *t, dims_b, ndims_b, s));
   if (ldxa < na || ldxb < nb) return fail(OBHIP_ERR_INVALID, "product_loglik_grad: leading dimension below the rows");
   if (na == 0 || nb == 0) return 0;

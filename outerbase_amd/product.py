@@ -15,6 +15,7 @@ import numpy as np
 
 from . import obmod
 from ._lib import call
+from .multi import DEFAULT_RHO
 
 
 def check_dims_b(d, dims_b):
@@ -48,6 +49,61 @@ def product_layout(om, terms, dims_b):
     ma, mb, fu = C.c_uint64(0), C.c_uint64(0), C.c_int(0)
     call("obhip_product_layout", t._h, db.ctypes.data, db.size, C.byref(ma), C.byref(mb), C.byref(fu))
     return ma.value, mb.value, bool(fu.value)
+
+
+def product_fit_layout(om, terms, dims_b):
+    """(mu_a, mu_b, fused_a, fused_b): the used basis columns of the two sides and whether the staging kernel of
+    the gridded fit keeps that side's tile in LDS (obhip_product_fit_layout; host only)"""
+    t = obmod._terms_of(om, terms)
+    db = check_dims_b(om.d, dims_b)
+    ma, mb, fa, fb = C.c_uint64(0), C.c_uint64(0), C.c_int(0), C.c_int(0)
+    call("obhip_product_fit_layout", t._h, db.ctypes.data, db.size, C.byref(ma), C.byref(mb), C.byref(fa), C.byref(fb))
+    return ma.value, mb.value, bool(fa.value), bool(fb.value)
+
+
+def product_side(om, terms, x, dims_b, side, padded=False):
+    """One side matrix of the gridded fit at the rows x: out[i, k] = s_i times the factors of term k on that
+    side (side 0: x is xa, n x (d - len(dims_b)); side 1: x is xb, n x len(dims_b)), an (n, p) array -- the
+    design-matrix entry of a pair is product_side(.., xa, .., 0)[i, k] * product_side(.., xb, .., 1)[j, k].
+    padded=True: the staged layout itself, rows up to a multiple of 64 and columns up to one of 256, all zeros
+    beyond (n, p) (obhip_product_side_dev)."""
+    import torch
+    t = obmod._terms_of(om, terms)
+    db = check_dims_b(om.d, dims_b)
+    if side not in (0, 1):
+        raise ValueError("side must be 0 (A) or 1 (B)")
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] != (db.size if side else om.d - db.size):
+        raise ValueError("x must be n x (the dimensions of the side)")
+    if not np.all(np.isfinite(x)):
+        raise ValueError("x must be finite")
+    n, p = x.shape[0], t.p
+    rows, pitch = ((n + 63) // 64 * 64, (p + 255) // 256 * 256)
+    if n == 0:
+        return np.zeros((0, pitch if padded else p))
+    dev = _device()
+    # filled with NaN: what the kernel does not write shows
+    out = torch.full((rows, pitch), float("nan"), dtype=torch.float64, device=dev)
+    call("obhip_product_side_dev", om._h, t._h, db.ctypes.data, db.size, int(side), _cols(x, dev).data_ptr(), n,
+         out.data_ptr(), pitch)
+    torch.cuda.synchronize()
+    out = out.cpu().numpy()
+    return out if padded else out[:n, :p].copy()
+
+
+def fit_newton_product(om, terms, xa, xb, Y, dims_b, sigma=None, rho=DEFAULT_RHO):
+    """The Newton fit of fit_newton_multi on the full grid xa x xb: Y[i, j] (na x nb, or na x nb x q) is the
+    response at the pair (xa[i], xb[j]) -- an accumulator filled once by NewtonAccumulator.add_product, so the
+    na nb full-width rows are never written.  -> MultiFit; fit.predict_product(xa, xb, dims_b) closes the loop."""
+    from .stream import NewtonAccumulator
+    Y = np.asarray(Y, dtype=np.float64)
+    if Y.ndim not in (2, 3):
+        raise ValueError("Y must be na x nb (x q)")
+    if Y.shape[0] * Y.shape[1] < 2:
+        raise ValueError("a fit needs two observations")
+    with NewtonAccumulator(om, terms, 1 if Y.ndim == 2 else Y.shape[2]) as acc:
+        acc.add_product(xa, xb, Y, dims_b)
+        return acc.fit(sigma=sigma, rho=rho)
 
 
 def _device():

@@ -189,6 +189,51 @@ class NewtonAccumulator:
         """Take out gradient rows that were added before (the same x, dY, dims and weights)."""
         return self._grad_batch(x, dY, dims, weights, -1)
 
+    # -- gridded data: the product of two input blocks ------------------------------------------
+    def _product_batch(self, xa, xb, Y, dims_b, sign):
+        from .product import check_blocks
+        xa, xb, db = check_blocks(self.om.d, xa, xb, dims_b)
+        na, nb = xa.shape[0], xb.shape[0]
+        Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim == 2:
+            Y = Y[:, :, None]
+        if Y.ndim != 3 or Y.shape != (na, nb, self.q):
+            raise ValueError("Y must be na x nb (x %d): one value per pair (and response)" % self.q)
+        if na == 0 or nb == 0:
+            raise ValueError("a grid batch needs rows on both sides")
+        if not (np.all(np.isfinite(xa)) and np.all(np.isfinite(xb))):
+            raise ValueError("xa and xb must be finite")
+        if not np.all(np.isfinite(Y)):
+            raise ValueError("Y must be finite")
+        self._need()
+        import torch
+        dev = _stream()
+        dxa = torch.from_numpy(np.ascontiguousarray(xa.T)).to(dev)
+        dxb = torch.from_numpy(np.ascontiguousarray(xb.T)).to(dev)
+        dY = torch.from_numpy(np.ascontiguousarray(Y.transpose(2, 1, 0))).to(dev)       # [response][j][i]
+        self._product_batch_dev(dxa, dxb, dY, na, nb, db, na, sign)
+        return self
+
+    def _product_batch_dev(self, dxa, dxb, dY, na, nb, db, lda, sign):
+        """dxa (|A|, na), dxb (|B|, nb), dY (q, nb, lda): device tensors; db: check_dims_b's uint32 array"""
+        import torch
+        self._need()
+        call("obhip_normal_acc_add_product_dev", self._h, dxa.data_ptr(), na, dxb.data_ptr(), nb, db.ctypes.data, db.size,
+             dY.data_ptr(), lda, sign)
+        torch.cuda.synchronize()
+
+    def add_product(self, xa, xb, Y, dims_b):
+        """Add the na nb observations of a full grid: Y[i, j] (na x nb, or na x nb x q: the shape of
+        predict_product's mean) is the response at the pair (xa[i], xb[j]), xb holding the dimensions dims_b and
+        xa all others (include/obhip.h, "Newton fit on the product of two input blocks").  The pairs are never
+        written out: the cost is the Gram of na + nb rows and one matrix product."""
+        return self._product_batch(xa, xb, Y, dims_b, +1)
+
+    def remove_product(self, xa, xb, Y, dims_b):
+        """Take out a grid batch that was added before (the same xa, xb, Y and dims_b: the accumulator does not
+        remember the split)."""
+        return self._product_batch(xa, xb, Y, dims_b, -1)
+
     def merge(self, other, sign=+1):
         """self += sign * other (another accumulator of the same model, terms and q)"""
         if not isinstance(other, NewtonAccumulator):
