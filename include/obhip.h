@@ -746,6 +746,53 @@ int obhip_shapley_dev(const obhip_terms *t, const int32_t *groups, const double 
 int obhip_shapley(const obhip_terms *t, const int32_t *groups, const double *Theta, uint64_t q,
                   const double *mean_tab, const double *cov_tab, double *out);
 
+/* ---- active subspaces and derivative-based sensitivity (no reference counterpart) ------------------
+ * C = E[grad f grad f^T] and gbar = E[grad f] of the fitted mean under the product measure above, in closed
+ * form: the diagonal of C holds the derivative-based global sensitivity measures (DGSM, nu_l = C_ll), its
+ * eigenvectors span the active subspace.  psi' = d psi / d x_l in raw input units, the raw (dcov/dx) . rotmat.
+ * Three more tables per dimension, all raw moments -- nothing is centred and nothing subtracted:
+ *   dm_l[t]   = sum_i w^_i psi'_{l,t}(z_il)                        packed like the mean table (sum L_l)
+ *   X_l[a,b]  = sum_i w^_i psi'_{l,a}(z_il) psi_{l,b}(z_il)          packed like the cov table (sum L_l^2), NOT symmetric
+ *   D_l[a,b]  = sum_i w^_i psi'_{l,a}(z_il) psi'_{l,b}(z_il)         packed like the cov table, exactly symmetric
+ * Per response, with t = t_kl, t' = t_k'l, s = t_km, s' = t_k'm and A_l = C_l + m_l m_l^T of the tables above:
+ *   gbar_l = sum_k theta_k dm_l[t] prod_{i != l} m_i[t_ki]                                   E[d f / d x_l]
+ *   C_ll   = sum_{k,k'} theta_k theta_k' D_l[t,t'] prod_{i != l} A_i[t_ki,t_k'i]              = nu_l
+ *   C_lm   = sum_{k,k'} theta_k theta_k' X_l[t,t'] X_m[s',s] prod_{i != l,m} A_i[t_ki,t_k'i]  l != m (X_m transposed)
+ * Exchanging k and k' maps the summand of C_lm onto that of C_ml: the pair sum runs over the upper triangle of
+ * term tiles and adds both orientations of every pair.  Fixed summation order, no atomics: the same bits on
+ * every call.  The limits are those of obhip_sobol_dev with three tables of sum L_l^2 entries in the LDS of a
+ * workgroup, refused with a message before any device call.  d = 1 is valid: one gbar and one C_00. */
+/* *n_mean = sum L_l, *n_cov = sum L_l^2, *n_out = d + d (d + 1) / 2 (each may be NULL) */
+int obhip_active_layout(const obhip_terms *t, uint64_t *n_mean, uint64_t *n_cov, uint64_t *n_out);
+/* The gradient tables of the measure; nodes, weights, errors and layout as obhip_dim_moments_dev (a bad weight
+ * or a column of weights without mass: OBHIP_ERR_NUMERIC).  d_dmean: sum L_l doubles; d_cross, d_dd: sum L_l^2
+ * doubles each, row-major per dimension.  Neither the basis nor its derivative is written to memory. */
+int obhip_dim_grad_moments_dev(const obhip_model *m, const obhip_terms *t, const double *d_nodes,
+                               uint64_t n, uint64_t ldx, const double *d_weights, uint64_t ldw,
+                               double *d_dmean, double *d_cross, double *d_dd);
+int obhip_active_workspace_bytes(uint64_t p, uint64_t d, uint64_t q, uint64_t *bytes);
+/* d_Theta and d_mean_tab / d_cov_tab as obhip_sobol_dev takes them (every C_l symmetric); d_dmean, d_cross,
+ * d_dd: the tables above (D_l symmetric; X_l as it is).  d_out: q x (d + d (d + 1) / 2) row-major, per response
+ * [gbar_0 .. gbar_{d-1}, C packed: the upper triangle with the diagonal, row-major -- C_00, C_01, .. C_0,d-1,
+ * C_11, ..].  d_ws: obhip_active_workspace_bytes(p, d, q). */
+int obhip_active_dev(const obhip_terms *t, const double *d_Theta, uint64_t q,
+                     const double *d_mean_tab, const double *d_cov_tab, const double *d_dmean,
+                     const double *d_cross, const double *d_dd, double *d_out, void *d_ws,
+                     uint64_t ws_bytes);
+/* host-buffer forms */
+int obhip_dim_grad_moments(const obhip_model *m, const obhip_terms *t, const double *nodes, uint64_t n,
+                           uint64_t ldx, const double *weights, uint64_t ldw, double *dmean,
+                           double *cross, double *dd);
+int obhip_active(const obhip_terms *t, const double *Theta, uint64_t q, const double *mean_tab,
+                 const double *cov_tab, const double *dmean, const double *cross, const double *dd,
+                 double *out);
+/* Host only: the eigen-decomposition of the symmetric n x n matrix A (column-major; the upper triangle is
+ * read), 1 <= n <= 4096 (OBHIP_ERR_INVALID otherwise; an entry that is not finite: OBHIP_ERR_NUMERIC), by the
+ * cyclic Jacobi method.  w: the n eigenvalues, descending; V: n x n column-major, column j the unit
+ * eigenvector of w[j], signed so that its component of largest magnitude is positive (the lowest index wins
+ * a tie). */
+int obhip_sym_eigh(uint64_t n, const double *A, double *w, double *V);
+
 /* ---- streaming Newton fit: rows come and go, one pass over each (no reference counterpart) ----
  * obfit (R/fitting.R:40-120) and every fit entry above take all rows at once and form the whole
  * Gram again per call.  An obhip_normal_acc keeps, in HBM, the sufficient statistics of the Newton

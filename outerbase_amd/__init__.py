@@ -15,8 +15,9 @@ from .obmod import (covf, covf_mat25, covf_mat25ang, covf_mat25pow, gethyp, getp
 from .fitting import BFGS_lpdf, BFGS_std, obfit, obpred, obpred_grad
 from .multi import MultiFit, fit_newton_multi
 from .glm import GlmFit, fit_glm
-from .sensitivity import (InputMoments, ShapleyResult, Sobol2Result, SobolResult, input_moments, interaction_effects,
-                          main_effects, shapley, sobol, sobol2, uniform_nodes)
+from .sensitivity import (ActiveSubspaceResult, GradMoments, InputMoments, ShapleyResult, Sobol2Result, SobolResult,
+                          active_subspace, input_grad_moments, input_moments, interaction_effects, main_effects,
+                          shapley, sobol, sobol2, sym_eigh, uniform_nodes)
 from .design import AcquireResult, DesignResult, Posterior, ThompsonResult
 from .torch_emulator import TorchCalibration, TorchEmulator
 from .product import (CalibrationLoglik, fit_newton_product, predict_product, predict_product_grad,
@@ -40,6 +41,7 @@ __all__ = [
     "Posterior", "DesignResult", "ThompsonResult", "AcquireResult",
     "InputMoments", "SobolResult", "input_moments", "uniform_nodes", "sobol", "main_effects",
     "Sobol2Result", "sobol2", "interaction_effects", "ShapleyResult", "shapley",
+    "GradMoments", "ActiveSubspaceResult", "input_grad_moments", "active_subspace", "sym_eigh",
     "predict_product", "product_loglik", "product_layout", "CalibrationLoglik",
     "predict_product_grad", "product_loglik_grad", "product_grad_layout", "TorchCalibration",
     "fit_newton_product", "product_side", "product_fit_layout",

@@ -39,11 +39,6 @@ namespace obhip {
 
 namespace {
 
-constexpr int kMomLT = 8;            // levels per accumulator tile
-constexpr int kMomP1 = kMomLT + 2;   // sums of pass 1: 8 levels, the weights, the bad weights
-constexpr int kMomP2 = kMomLT * kMomLT;
-constexpr int kMomBlocks = 512;      // row slices at most
-
 struct StoreCol {
   double *col;  // tile + thread
   int ccol0, nt;
@@ -57,45 +52,6 @@ __device__ __forceinline__ void eval_raw(const DimDesc &D, const double *ka, con
   const double c0 = build_dim_any(D, ka, kb, kc, rot, tab, xv, st);
   col[0] = c0;
   for (int t = 1; t < D.ncol; ++t) col[(size_t)t * nt] *= c0;
-}
-
-// the dimension's interval tables into LDS (all threads of the block call it); -> the table base
-__device__ __forceinline__ const double *stage_tab(DimDesc &D, const double *__restrict__ tab, double *ltab) {
-  if (D.tab < 0) return tab;
-  const int sz = ((D.m + 1) & ~1) + (D.m + 1) * D.ncol * 6;
-  if (sz > kIntervalTabMax) return tab;
-  for (int e = threadIdx.x; e < sz; e += blockDim.x) ltab[e] = tab[D.tab + e];
-  __syncthreads();
-  D.tab = 0;
-  return ltab;
-}
-
-__device__ __forceinline__ int mean_offset(const DimDesc *__restrict__ dims, int l) {
-  int o = 0;
-  for (int i = 0; i < l; ++i) o += dims[i].ncol;
-  return o;
-}
-__device__ __forceinline__ int cov_offset(const DimDesc *__restrict__ dims, int l) {
-  int o = 0;
-  for (int i = 0; i < l; ++i) o += dims[i].ncol * dims[i].ncol;
-  return o;
-}
-
-// part[k] = sum over the block of acc[k]: butterfly per wave, the waves in order
-template <int K>
-__device__ __forceinline__ void block_sums(const double (&acc)[K], double *red, double *__restrict__ part) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const double v = wave_sum(acc[k]);
-    if (lane == 0) red[wave * K + k] = v;
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < K) {
-    double s = 0.0;
-    for (int w = 0; w < nw; ++w) s += red[w * K + threadIdx.x];
-    part[threadIdx.x] = s;
-  }
 }
 
 // dynamic LDS: [interval tables kIntervalTabMax][reduction 4 * 64][tile lmax * threads]
@@ -168,14 +124,6 @@ k_dim_moments(const DimDesc *__restrict__ dims, const double *__restrict__ ka, c
   }
   __syncthreads();
   block_sums<K>(acc, red, part + (((uint64_t)l * gridDim.z + blockIdx.z) * gridDim.x + blockIdx.x) * K);
-}
-
-// sum over the nblk row slices of entry k of K, every lane of the wave gets it
-template <int K>
-__device__ __forceinline__ double slices_sum(const double *__restrict__ base, int nblk, int k) {
-  double s = 0.0;
-  for (int b = threadIdx.x; b < nblk; b += 64) s += base[(uint64_t)b * K + k];
-  return wave_sum(s);
 }
 
 // block (dimension, level tile), one wave: the means, the weight sum of the dimension, the flag
@@ -779,6 +727,14 @@ int launch_sobol_first(const uint8_t *d_lev, const int *d_meta, uint64_t p, uint
   hipLaunchKernelGGL(k_sobol_first, dim3((unsigned)d + 1, (unsigned)q), dim3(256), (lmax + 256) * sizeof(double),
                      cur_stream(), d_lev, d_meta, (int)p, (int)d, (int)sum_l, d_Theta, d_ctab, (const double *)d_excl,
                      (const double *)d_u, (int)lmax, d_out, d_g);
+  OB_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_sobol_excl(const uint8_t *d_lev, const int *d_meta, uint64_t p, uint64_t d, const double *d_mtab,
+                      double *d_excl, double *d_u) {
+  hipLaunchKernelGGL(k_sobol_excl, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, cur_stream(), d_lev, d_meta, (int)p,
+                     (int)d, d_mtab, d_excl, d_u);
   OB_HIP(hipGetLastError());
   return 0;
 }

@@ -987,6 +987,25 @@ uint64_t shapley_part_doubles(uint64_t p, uint64_t d, uint64_t q);  // partials 
 int launch_shapley_pairs(const ShapPlan &plan, const uint8_t *d_lev, const int *d_meta, uint64_t p, uint64_t d,
                          uint64_t q, uint64_t n_cov, const double *d_Theta, const double *d_mtab, const double *d_ctab,
                          double *d_part, double *d_out);
+// kernels_active.hip: E[grad f grad f^T] and E[grad f] of the fitted mean in closed form, DESIGN.md section 31
+constexpr int kActiveT = 5;   // dimensions per block of the d x d triangle of outputs (diagonal included)
+constexpr int kActiveRC = 2;  // responses per chunk of the pair sum
+int active_moment_threads(uint64_t lmax);                           // threads per block of k_dim_grad_moments
+size_t active_moments_lds(uint64_t lmax);                           // and its dynamic LDS
+size_t active_pairs_lds(uint64_t n_cov);                            // dynamic LDS of k_active_pairs
+uint64_t active_part_doubles(uint64_t p, uint64_t d, uint64_t q);   // partials of its pair sum
+// the exclusion products of launch_sobol_first alone (kernels_sobol.hip): d_excl p x d, d_u p
+int launch_sobol_excl(const uint8_t *d_lev, const int *d_meta, uint64_t p, uint64_t d, const double *d_mtab,
+                      double *d_excl, double *d_u);
+// d_dmean / d_cross / d_dd: the packed tables; *flag_out != 0: a bad weight or a weight column without mass
+int launch_dim_grad_moments(const obhip_model &m, obhip_terms &t, const double *d_nodes, uint64_t n, uint64_t ldx,
+                            const double *d_w, uint64_t ldw, double *d_dmean, double *d_cross, double *d_dd,
+                            int *flag_out);
+// d_out: q x (d + d (d + 1) / 2) row-major; d_excl (p x d), d_u (p) and d_part: scratch
+int launch_active(const uint8_t *d_lev, const int *d_meta, uint64_t p, uint64_t d, uint64_t q, uint64_t n_cov,
+                  const double *d_Theta, const double *d_mtab, const double *d_ctab, const double *d_dmtab,
+                  const double *d_xtab, const double *d_ddtab, double *d_excl, double *d_u, double *d_part,
+                  double *d_out);
 // ---- runtime value -> template argument -----------------------------------------------------------
 // pick_or<1, 2, 4, 8>(ng, miss, [&](auto NG) { ... NG() ... }): the lambda is called with the
 // std::integral_constant of the listed value that v equals and its result returned; `miss` when v

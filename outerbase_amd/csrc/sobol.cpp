@@ -1,6 +1,6 @@
 // Variance-based sensitivity of the fitted mean: the entry points (include/obhip.h, "variance-based
-// sensitivity").  No reference counterpart.  The kernels and their launches are in kernels_sobol.hip and
-// kernels_shapley.hip.
+// sensitivity" and "active subspaces").  No reference counterpart.  The kernels and their launches are in
+// kernels_sobol.hip, kernels_shapley.hip and kernels_active.hip.
 // Every check that can refuse a call runs before the first device call.
 #include "obhip_internal.h"
 
@@ -33,6 +33,16 @@ int sobol_layout(const char *who, const obhip_terms &t, Layout &lay) {
   if (sobol_pairs_lds(t.d, lay.n_cov) > kLdsBudget)
     return fail(OBHIP_ERR_INVALID, std::string(who) + ": the tables of these terms (" + std::to_string(lay.n_cov) +
                                        " covariances) do not fit the LDS of a workgroup");
+  return 0;
+}
+
+// sobol_layout with the limits of the gradient tables on top: three tables of n_cov entries in the LDS of
+// k_active_pairs, two basis tiles in that of k_dim_grad_moments
+int active_layout(const char *who, const obhip_terms &t, Layout &lay) {
+  OB_TRY(sobol_layout(who, t, lay));
+  if (active_pairs_lds(lay.n_cov) > kLdsBudget || active_moments_lds(lay.lmax) > kLdsBudget)
+    return fail(OBHIP_ERR_INVALID, std::string(who) + ": the tables of these terms (" + std::to_string(lay.n_cov) +
+                                       " entries each) do not fit the LDS of a workgroup");
   return 0;
 }
 
@@ -455,6 +465,143 @@ int obhip_shapley(const obhip_terms *t, const int32_t *groups, const double *The
   OB_TRY(ws.alloc(wsb));
   OB_TRY(obhip_shapley_dev(t, groups, dth.p, q, dm.p, dc.p, dout.p, ws.p, wsb));
   return d2h(out, dout.p, q * (uint64_t)plan.nplayers * sizeof(double));
+}
+
+// ---- active subspaces and derivative-based sensitivity ---------------------------------
+int obhip_active_layout(const obhip_terms *t, uint64_t *n_mean, uint64_t *n_cov, uint64_t *n_out) {
+  if (!t) return fail(OBHIP_ERR_INVALID, "active_layout: null terms");
+  Layout lay;
+  OB_TRY(active_layout("active_layout", *t, lay));
+  if (n_mean) *n_mean = lay.n_mean;
+  if (n_cov) *n_cov = lay.n_cov;
+  if (n_out) *n_out = t->d + t->d * (t->d + 1) / 2;
+  return 0;
+}
+
+int obhip_dim_grad_moments_dev(const obhip_model *m, const obhip_terms *t, const double *d_nodes, uint64_t n,
+                               uint64_t ldx, const double *d_weights, uint64_t ldw, double *d_dmean, double *d_cross,
+                               double *d_dd) {
+  if (!m || !t || !d_nodes || !d_dmean || !d_cross || !d_dd)
+    return fail(OBHIP_ERR_INVALID, "dim_grad_moments_dev: null model, terms, nodes, dmean, cross or dd");
+  if (n == 0) return fail(OBHIP_ERR_INVALID, "dim_grad_moments_dev: no nodes, so no measure");
+  if (n > kSobolMaxRows) return fail(OBHIP_ERR_INVALID, "dim_grad_moments_dev: more than 2^40 nodes in one call");
+  if (ldx < n) return fail(OBHIP_ERR_INVALID, "dim_grad_moments_dev: leading dimension of the nodes below n");
+  if (d_weights && ldw < n)
+    return fail(OBHIP_ERR_INVALID, "dim_grad_moments_dev: leading dimension of the weights below n");
+  OB_TRY(check_compat(m, t));
+  Layout lay;
+  OB_TRY(active_layout("dim_grad_moments_dev", *t, lay));
+  OB_TRY(require_device());
+  int flag = 0;
+  OB_TRY(launch_dim_grad_moments(*m, *const_cast<obhip_terms *>(t), d_nodes, n, ldx, d_weights, ldw, d_dmean, d_cross,
+                                 d_dd, &flag));
+  if (flag)
+    return fail(OBHIP_ERR_NUMERIC, "dim_grad_moments_dev: a weight is negative or not finite, or the weights of a "
+                                   "dimension do not sum to > 0");
+  return 0;
+}
+
+int obhip_active_workspace_bytes(uint64_t p, uint64_t d, uint64_t q, uint64_t *bytes) {
+  if (!bytes || p == 0 || d == 0 || d > 255 || q == 0 || q > kSobolMaxQ || p > (1ull << 24))
+    return fail(OBHIP_ERR_INVALID, "active_workspace_bytes: null bytes, or p, d, q out of range");
+  *bytes = align256(p * d * sizeof(double)) + align256(p * sizeof(double)) +
+           align256(active_part_doubles(p, d, q) * sizeof(double));
+  return 0;
+}
+
+int obhip_active_dev(const obhip_terms *t, const double *d_Theta, uint64_t q, const double *d_mean_tab,
+                     const double *d_cov_tab, const double *d_dmean, const double *d_cross, const double *d_dd,
+                     double *d_out, void *d_ws, uint64_t ws_bytes) {
+  if (!t || !d_Theta || !d_mean_tab || !d_cov_tab || !d_dmean || !d_cross || !d_dd || !d_out || !d_ws)
+    return fail(OBHIP_ERR_INVALID, "active_dev: null terms, Theta, tables, out or workspace");
+  if (q == 0 || q > kSobolMaxQ) return fail(OBHIP_ERR_INVALID, "active_dev: 1 to 65535 responses");
+  Layout lay;
+  OB_TRY(active_layout("active_dev", *t, lay));
+  uint64_t need = 0;
+  OB_TRY(obhip_active_workspace_bytes(t->p, t->d, q, &need));
+  if (ws_bytes < need)
+    return fail(OBHIP_ERR_INVALID, "active_dev: workspace smaller than obhip_active_workspace_bytes");
+  OB_TRY(require_device());
+  obhip_terms &tt = *const_cast<obhip_terms *>(t);
+  OB_TRY(ensure_sobol_tables(tt));
+  const uint64_t p = t->p, d = t->d;
+  char *ws = (char *)d_ws;
+  double *excl = (double *)ws;
+  double *u = (double *)(ws + align256(p * d * sizeof(double)));
+  double *part = (double *)(ws + align256(p * d * sizeof(double)) + align256(p * sizeof(double)));
+  return launch_active(tt.sobol_lev.p, tt.sobol_meta.p, p, d, q, lay.n_cov, d_Theta, d_mean_tab, d_cov_tab, d_dmean,
+                       d_cross, d_dd, excl, u, part, d_out);
+}
+
+int obhip_dim_grad_moments(const obhip_model *m, const obhip_terms *t, const double *nodes, uint64_t n, uint64_t ldx,
+                           const double *weights, uint64_t ldw, double *dmean, double *cross, double *dd) {
+  if (!m || !t || !nodes || !dmean || !cross || !dd)
+    return fail(OBHIP_ERR_INVALID, "dim_grad_moments: null model, terms, nodes, dmean, cross or dd");
+  if (n == 0) return fail(OBHIP_ERR_INVALID, "dim_grad_moments: no nodes, so no measure");
+  if (n > kSobolMaxRows) return fail(OBHIP_ERR_INVALID, "dim_grad_moments: more than 2^40 nodes in one call");
+  if (ldx < n) return fail(OBHIP_ERR_INVALID, "dim_grad_moments: leading dimension of the nodes below n");
+  if (weights && ldw < n) return fail(OBHIP_ERR_INVALID, "dim_grad_moments: leading dimension of the weights below n");
+  OB_TRY(check_compat(m, t));
+  Layout lay;
+  OB_TRY(active_layout("dim_grad_moments", *t, lay));
+  OB_TRY(require_device());
+  DevBuf<double> dx, dw, dm, dc, dv;
+  OB_TRY(upload_cols(dx, nodes, n, m->d, ldx));
+  if (weights) OB_TRY(upload_cols(dw, weights, n, m->d, ldw));
+  OB_TRY(dm.alloc(lay.n_mean));
+  OB_TRY(dc.alloc(lay.n_cov));
+  OB_TRY(dv.alloc(lay.n_cov));
+  OB_TRY(obhip_dim_grad_moments_dev(m, t, dx.p, n, n, dw.p, n, dm.p, dc.p, dv.p));
+  OB_TRY(d2h(dmean, dm.p, lay.n_mean * sizeof(double)));
+  OB_TRY(d2h(cross, dc.p, lay.n_cov * sizeof(double)));
+  return d2h(dd, dv.p, lay.n_cov * sizeof(double));
+}
+
+int obhip_active(const obhip_terms *t, const double *Theta, uint64_t q, const double *mean_tab, const double *cov_tab,
+                 const double *dmean, const double *cross, const double *dd, double *out) {
+  if (!t || !Theta || !mean_tab || !cov_tab || !dmean || !cross || !dd || !out)
+    return fail(OBHIP_ERR_INVALID, "active: null terms, Theta, tables or out");
+  if (q == 0 || q > kSobolMaxQ) return fail(OBHIP_ERR_INVALID, "active: 1 to 65535 responses");
+  Layout lay;
+  OB_TRY(active_layout("active", *t, lay));
+  uint64_t wsb = 0;
+  OB_TRY(obhip_active_workspace_bytes(t->p, t->d, q, &wsb));
+  OB_TRY(require_device());
+  const uint64_t nout = t->d + t->d * (t->d + 1) / 2;
+  DevBuf<double> dth, dm, dc, ddm, dx, dv, dout;
+  DevBuf<char> ws;
+  OB_TRY(dth.upload(Theta, t->p * q));
+  OB_TRY(dm.upload(mean_tab, lay.n_mean));
+  OB_TRY(dc.upload(cov_tab, lay.n_cov));
+  OB_TRY(ddm.upload(dmean, lay.n_mean));
+  OB_TRY(dx.upload(cross, lay.n_cov));
+  OB_TRY(dv.upload(dd, lay.n_cov));
+  OB_TRY(dout.alloc(q * nout));
+  OB_TRY(ws.alloc(wsb));
+  OB_TRY(obhip_active_dev(t, dth.p, q, dm.p, dc.p, ddm.p, dx.p, dv.p, dout.p, ws.p, wsb));
+  return d2h(out, dout.p, q * nout * sizeof(double));
+}
+
+int obhip_sym_eigh(uint64_t n, const double *A, double *w, double *V) {
+  if (n == 0 || !A || !w || !V) return fail(OBHIP_ERR_INVALID, "sym_eigh: n = 0, or null A, w or V");
+  if (n > 4096) return fail(OBHIP_ERR_INVALID, "sym_eigh: more than 4096 rows");
+  for (uint64_t i = 0; i < n * n; ++i)
+    if (!std::isfinite(A[i])) return fail(OBHIP_ERR_NUMERIC, "sym_eigh: an entry of A is not finite");
+  const int N = (int)n;
+  std::vector<double> a(n * n), ev, vec;
+  for (uint64_t i = 0; i < n; ++i)                       // the upper triangle, mirrored
+    for (uint64_t j = i; j < n; ++j) a[i * n + j] = a[j * n + i] = A[j * n + i];
+  jacobi_eigh(N, a, ev, vec);                            // ascending; vector j at vec[j n ..]
+  for (uint64_t j = 0; j < n; ++j) {
+    const double *v = &vec[(n - 1 - j) * n];
+    uint64_t big = 0;
+    for (uint64_t i = 1; i < n; ++i)
+      if (std::fabs(v[i]) > std::fabs(v[big])) big = i;  // (the lowest index wins a tie)
+    const double sg = v[big] < 0.0 ? -1.0 : 1.0;
+    w[j] = ev[n - 1 - j];
+    for (uint64_t i = 0; i < n; ++i) V[j * n + i] = sg * v[i];
+  }
+  return 0;
 }
 
 }  // extern "C"

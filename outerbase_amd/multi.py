@@ -245,6 +245,22 @@ class MultiFit:
         res.var = res.var * s2
         return res
 
+    def active_subspace(self, nodes, weights=None, scale=None):
+        """E[grad f grad f^T], the DGSM and the active subspace of every response under the product measure of
+        nodes / weights, in raw units: ActiveSubspaceResult with C, dgsm and the eigenvalues times y_sca^2,
+        mean_grad times y_sca and the eigenvectors unchanged (sensitivity.active_subspace)."""
+        from . import sensitivity
+        sensitivity._check_nodes(self.om, nodes, weights)
+        sensitivity._check_scale(self.om.d, scale)
+        gm = sensitivity.input_grad_moments(self.om, self._t, nodes, weights)
+        res = sensitivity.active_subspace(self.om, self._t, self.coeff, gm, scale)
+        s2 = self.y_sca * self.y_sca
+        res.C = res.C * s2[None, None, :]
+        res.dgsm = res.dgsm * s2[None, :]
+        res.mean_grad = res.mean_grad * self.y_sca[None, :]
+        res.eigenvalues = res.eigenvalues * s2[None, :]
+        return res
+
     def interaction_effects(self, dim_i, dim_j, grid_i, grid_j, nodes, weights=None):
         """the interaction surface of every response on grid_i x grid_j (Gi x Gj x q), in raw units (times y_sca)"""
         from . import sensitivity

@@ -1,4 +1,4 @@
-"""Sobol indices, Shapley effects and main effects of the fitted mean, in closed form.
+"""Sobol indices, Shapley effects, main effects and active subspaces of the fitted mean, in closed form.
 
 The fitted mean is a sum of products of one-dimensional functions, f(x) = sum_k theta_k prod_l
 psi_{l, t_kl}(x_l) with psi_l = getbase(l).  Under independent inputs with a discrete measure per
@@ -287,3 +287,135 @@ def shapley(om, terms, Theta, moments, groups=None):
          out.data_ptr(), ws.data_ptr(), wsb.value)
     torch.cuda.synchronize()
     return ShapleyResult(out.cpu().numpy(), players)
+
+
+class GradMoments:
+    """Result of input_grad_moments: `moments`, the InputMoments of the same measure (mean, cov), and per dimension
+    dmean[l] (L_l) = E[psi'], cross[l] (L_l x L_l, not symmetric) = E[psi'_a psi_b], dd[l] (L_l x L_l, symmetric) =
+    E[psi'_a psi'_b], psi' = d psi / d x_l in raw input units; the packed device copies dmean_dev, cross_dev,
+    dd_dev are what active_subspace reads.  One object serves sobol / sobol2 / shapley (through .moments) and
+    active_subspace."""
+
+    def __init__(self, moments, dmean_dev, cross_dev, dd_dev):
+        self.moments, self.terms, self.levels = moments, moments.terms, moments.levels
+        self.mean_dev, self.cov_dev, self.mean, self.cov = moments.mean_dev, moments.cov_dev, moments.mean, moments.cov
+        self.dmean_dev, self.cross_dev, self.dd_dev = dmean_dev, cross_dev, dd_dev
+        levels = self.levels
+        pm, px, pd = dmean_dev.cpu().numpy(), cross_dev.cpu().numpy(), dd_dev.cpu().numpy()
+        om_ = np.concatenate([[0], np.cumsum(levels)])
+        oc_ = np.concatenate([[0], np.cumsum(levels * levels)])
+        self.dmean = [pm[om_[l]:om_[l + 1]].copy() for l in range(len(levels))]
+        self.cross = [px[oc_[l]:oc_[l + 1]].reshape(levels[l], levels[l]).copy() for l in range(len(levels))]
+        self.dd = [pd[oc_[l]:oc_[l + 1]].reshape(levels[l], levels[l]).copy() for l in range(len(levels))]
+
+
+def sym_eigh(A):
+    """(w, V) of the symmetric matrix A by the library's Jacobi solver (obhip_sym_eigh, host only): w descending,
+    V[:, j] the unit eigenvector of w[j], its component of largest magnitude positive."""
+    A = np.asarray(A, dtype=np.float64)
+    if A.ndim != 2 or A.shape[0] != A.shape[1] or A.shape[0] == 0:
+        raise ValueError("A must be a square matrix with at least one row")
+    n = A.shape[0]
+    a = np.asfortranarray(A)
+    w, V = np.empty(n), np.empty((n, n), order="F")
+    call("obhip_sym_eigh", n, a.ctypes.data, w.ctypes.data, V.ctypes.data)
+    return w, np.ascontiguousarray(V)
+
+
+class ActiveSubspaceResult:
+    """C (d x d x q) = E[grad f grad f^T] per response, symmetric by construction (the device returns one triangle);
+    dgsm (d x q) = its diagonal, the derivative-based global sensitivity measures nu_l; mean_grad (d x q) = E[grad f];
+    scale (d, or None); eigenvalues (d x q, descending) and eigenvectors (d x d x q, [:, j, r] the j-th of response
+    r) of diag(scale) C diag(scale) -- of C itself without scale."""
+
+    def __init__(self, out, d, scale):
+        q = out.shape[0]
+        self.mean_grad = np.ascontiguousarray(out[:, :d].T)
+        iu = np.triu_indices(d)
+        self.C = np.empty((d, d, q))
+        self.C[iu[0], iu[1]] = out[:, d:].T
+        self.C[iu[1], iu[0]] = out[:, d:].T
+        self.dgsm = np.ascontiguousarray(self.C[np.arange(d), np.arange(d)])
+        self.scale = scale
+        self.eigenvalues, self.eigenvectors = np.empty((d, q)), np.empty((d, d, q))
+        self._eig()
+
+    def _eig(self):
+        s = np.ones(self.C.shape[0]) if self.scale is None else self.scale
+        for r in range(self.C.shape[2]):
+            self.eigenvalues[:, r], self.eigenvectors[:, :, r] = sym_eigh(self.C[:, :, r] * s[:, None] * s[None, :])
+
+    def activity_scores(self, k):
+        """alpha_l = sum_{j < k} lambda_j W[l, j]^2 (Constantine and Diaz 2017), d x q: what dimension l
+        contributes to the first k eigen-directions"""
+        k = int(k)
+        if not 1 <= k <= self.C.shape[0]:
+            raise ValueError("k must be 1 .. d")
+        return np.einsum("jr,ljr->lr", self.eigenvalues[:k], self.eigenvectors[:, :k] ** 2)
+
+    def project(self, x, k, response=0):
+        """the active variables y = W_k^T (x / scale) of the rows x (n x d) for one response, n x k: the coordinates
+        along the first k eigenvectors, in the scaled inputs the eigenvectors belong to"""
+        x = np.asarray(x, dtype=np.float64)
+        d = self.C.shape[0]
+        if x.ndim != 2 or x.shape[1] != d:
+            raise ValueError("x must be n x d")
+        k, response = int(k), int(response)
+        if not 1 <= k <= d:
+            raise ValueError("k must be 1 .. d")
+        if not 0 <= response < self.C.shape[2]:
+            raise ValueError("response out of range")
+        if self.scale is not None:
+            x = x / self.scale[None, :]
+        return x @ self.eigenvectors[:, :k, response]
+
+
+def _check_scale(d, scale):
+    if scale is None:
+        return None
+    scale = np.asarray(scale, dtype=np.float64)
+    if scale.shape != (d,) or not np.all(np.isfinite(scale)) or not np.all(scale > 0):
+        raise ValueError("scale must be d positive numbers")
+    return scale
+
+
+def input_grad_moments(om, terms, nodes, weights=None):
+    """GradMoments of the product measure of nodes / weights (as input_moments takes them): the moment tables and
+    the three gradient tables -- obhip_dim_moments_dev and obhip_dim_grad_moments_dev."""
+    nodes, weights = _check_nodes(om, nodes, weights)
+    t = obmod._terms_of(om, terms)
+    mom = input_moments(om, t, nodes, weights)
+    torch, dev = _device()
+    n = nodes.shape[0]
+    nm, nc = C.c_uint64(0), C.c_uint64(0)
+    call("obhip_active_layout", t._h, C.byref(nm), C.byref(nc), None)
+    dx = torch.from_numpy(np.ascontiguousarray(nodes.T)).to(dev)
+    dw = None if weights is None else torch.from_numpy(np.ascontiguousarray(weights.T)).to(dev)
+    dmean = torch.empty(nm.value, dtype=torch.float64, device=dev)
+    cross = torch.empty(nc.value, dtype=torch.float64, device=dev)
+    dd = torch.empty(nc.value, dtype=torch.float64, device=dev)
+    call("obhip_dim_grad_moments_dev", om._h, t._h, dx.data_ptr(), n, n, None if dw is None else dw.data_ptr(), n,
+         dmean.data_ptr(), cross.data_ptr(), dd.data_ptr())
+    return GradMoments(mom, dmean, cross, dd)
+
+
+def active_subspace(om, terms, Theta, gmoments, scale=None):
+    """ActiveSubspaceResult of the responses Theta (p x q, or p) under the measure of `gmoments`
+    (input_grad_moments) -- obhip_active_dev, then obhip_sym_eigh per response.  scale: d positive numbers (the box
+    widths, say): the eigen step takes diag(scale) C diag(scale), the matrix of the inputs x / scale."""
+    t = obmod._terms_of(om, terms)
+    Theta = _check_theta(t, Theta)
+    scale = _check_scale(t.d, scale)
+    torch, dev = _device()
+    q, d = Theta.shape[1], t.d
+    wsb, nout = C.c_uint64(0), C.c_uint64(0)
+    call("obhip_active_layout", t._h, None, None, C.byref(nout))
+    call("obhip_active_workspace_bytes", t.p, d, q, C.byref(wsb))
+    dth = torch.from_numpy(np.ascontiguousarray(Theta.T)).to(dev)
+    ws = torch.empty(wsb.value, dtype=torch.uint8, device=dev)
+    out = torch.empty((q, nout.value), dtype=torch.float64, device=dev)
+    g = gmoments
+    call("obhip_active_dev", t._h, dth.data_ptr(), q, g.mean_dev.data_ptr(), g.cov_dev.data_ptr(),
+         g.dmean_dev.data_ptr(), g.cross_dev.data_ptr(), g.dd_dev.data_ptr(), out.data_ptr(), ws.data_ptr(), wsb.value)
+    torch.cuda.synchronize()
+    return ActiveSubspaceResult(out.cpu().numpy(), d, scale)
