@@ -301,6 +301,28 @@ int obhip_basis_sqcolsums_gradhyp(const obhip_basis *b, const obhip_terms *t, do
 /* ob$residvar_gradhyp(terms): modandbase.cpp:904-925; n x nhyp */
 int obhip_basis_residvar_gradhyp(const obhip_basis *b, const obhip_terms *t, const obhip_model *m,
                                  double *out_gradhyp);
+/* What the hyper-gradient products above will launch for (b, t), read from the functions the launchers
+ * take their geometry from; the gradient basis and the terms' device tables are prepared as the
+ * products prepare them, nothing else runs (OBHIP_GRAD_D3 and OBHIP_GRAM_CHUNK_ROWS are read as there).
+ * info (16 entries):
+ *   [0] plan of the transposed products: 0 fused (dense pass + k_tmm_d3), 1 dense pass + restricted
+ *       views, 2 k_bt_times_u on the materialised design matrix + restricted views, 3 full views;
+ *   [1] k_tmm_d3 groups (0: the terms do not fit it, or it is switched off; matmul_gradhyp_dot takes
+ *       them under any plan), [10] their members in all;
+ *   the dense pass: [2] kernel (0 none, 1 k_tmm_ge0_db, 2 k_tmm_ge0 with 16 waves, 3 with 8 waves,
+ *       4 k_bt_times_u), [6] blocks along the terms, [7] row splits, [8] row tiles per split, [9] passes;
+ *   the terms' own tables: [3] W / 2 (column slots per term / 2), [4] used columns Mu, [5] p_pad;
+ *   [11] groups of restricted views (plans 1 and 2), [12] of them those too wide for one pass, which
+ *       go hyper-parameter by hyper-parameter;
+ *   [13] hyper-parameters, [14] row tiles of the basis, [15] compute units of its device.
+ * Optional outputs, sized from a first call without them:
+ * groups (10 x [1]): per k_tmm_d3 group nh (delta columns per view-term), W, Mu, view-terms p, p_pad,
+ *   NU (view-terms per lane: 2 or 4), blocks along the view-terms, row splits, row tiles per split,
+ *   members;
+ * members ([10] entries): the first hyper-parameter of every member, group after group;
+ * passes (4 x [9]): per dense pass h0, nh, NHB (1: a 16-block), N4 (groups of four). */
+int obhip_grad_plan_info(const obhip_basis *b, const obhip_terms *t, uint64_t *info, uint64_t *groups,
+                         uint64_t *members, int64_t *passes);
 
 /* ---- Gram / Newton ("back end A") -------------------------------------- */
 /* G = B^T B (loglik_std::hess without its e^{-2 sigma}, loglik_std.cpp:

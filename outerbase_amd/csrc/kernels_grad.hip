@@ -175,6 +175,10 @@ int run_d3_groups(obhip_basis &b, obhip_terms &t, int mode, const double *d_w1, 
 // ---- the groups of restricted views of a term set (delta: the delta views) -----------------------
 // One k_tmm pass over src (b's gradient basis or its squared store) and one blocking copy per group -- per
 // hyper-parameter where a group's columns exceed one LDS tile -- then each(h, term indices, values).
+// (one pass for the group: its concatenated view prepares and its columns fit one LDS tile)
+bool view_group_one_pass(obhip_terms &all, const obhip_basis &src) {
+  return all.prepare(src.md.cap, src.md.dims_h) == 0 && all.Mu <= 296;
+}
 template <typename F>
 int run_view_groups(const obhip_basis &src, obhip_terms &t, const obhip_basis &b, bool delta, const double *d_w,
                     F &&each) {
@@ -188,7 +192,7 @@ int run_view_groups(const obhip_basis &src, obhip_terms &t, const obhip_basis &b
   };
   for (obhip_terms::GeGroup &grp : grad_view_groups(t, b, delta)) {
     obhip_terms *all = grp.v.get();
-    if (all->prepare(src.md.cap, src.md.dims_h) == 0 && all->Mu <= 296) {
+    if (view_group_one_pass(*all, src)) {
       OB_TRY(pass(*all));
       for (size_t j = 0; j < grp.hyps.size(); ++j) each(grp.hyps[j], t.ge.sidx[grp.hyps[j]], tmp.data() + grp.off[j]);
       continue;
@@ -449,6 +453,69 @@ int obhip_basis_tmm_gradhyp(const obhip_basis *bc, const obhip_terms *tc, const 
     OB_TRY(d2h(out, dout.p, t.p * sizeof(double)));
   }
   return tmm_gradhyp_all(b, t, false, da.p, out_gradhyp);
+}
+
+// What the gradient products of (b, t) will launch, from the very functions the launchers take their
+// geometry from (grad_plan, build_d3_groups, d3_geometry, ge0_geometry, btu_geometry, grad_view_groups).
+// Nothing is launched but what prepares the tables: the gradient basis and the terms' device tables.
+int obhip_grad_plan_info(const obhip_basis *bc, const obhip_terms *tc, uint64_t *info, uint64_t *groups,
+                         uint64_t *members, int64_t *passes) {
+  OB_TRY(check_grad_args(bc, tc));
+  if (!info) return fail(OBHIP_ERR_INVALID, "grad_plan_info: null argument");
+  obhip_basis &b = *const_cast<obhip_basis *>(bc);
+  obhip_terms &t = *const_cast<obhip_terms *>(tc);
+  OB_TRY(ensure_gradbasis(b));
+  OB_TRY(t.prepare(b.md.cap, b.md.dims_h));
+  const GradPlan plan = grad_plan(b, t);
+  const bool d3 = build_d3_groups(t, b);  // (matmul_gradhyp_dot takes the groups under every plan that has them)
+  std::fill(info, info + 16, (uint64_t)0);
+  info[0] = (uint64_t)plan;
+  info[13] = b.model->nhyp();
+  info[14] = b.n_pad / kTileRows;
+  info[15] = (uint64_t)device_cus(b.device);
+  if (d3) {
+    info[1] = t.ge.d3.size();
+    for (const obhip_terms::GeD3 &grp : t.ge.d3) {
+      const D3Geom q = d3_geometry(b, grp);
+      const obhip_terms &v = *grp.v;
+      if (groups) {
+        const uint64_t row[10] = {(uint64_t)grp.nh, v.W, v.Mu, v.p, v.p_pad, (uint64_t)q.nu, q.pblocks, q.nsplit,
+                                  q.tps, (uint64_t)grp.hyp0.size()};
+        groups = std::copy(row, row + 10, groups);
+      }
+      if (members) members = std::copy(grp.hyp0.begin(), grp.hyp0.end(), members);
+      info[10] += grp.hyp0.size();
+    }
+  }
+  if (plan == GradPlan::Fused || plan == GradPlan::Ge0Views) {
+    const Ge0Geom q = ge0_geometry(b, t);
+    info[2] = q.nw == 32 ? 1 : (q.nw == 16 ? 2 : 3);
+    info[6] = q.pblocks, info[7] = q.nsplit, info[8] = q.tps, info[9] = q.passes.size();
+    if (passes)
+      for (const Ge0Pass &ps : q.passes) {
+        const int64_t row[4] = {ps.h0, ps.nh, ps.n4 >= 0 ? 1 : 0, ps.n4 < 0 ? -ps.n4 : ps.n4};
+        passes = std::copy(row, row + 4, passes);
+      }
+  } else if (plan == GradPlan::BmatViews) {
+    const BtuGeom q = btu_geometry(b, t);
+    const int nhyp = (int)b.model->nhyp();
+    info[2] = 4;
+    info[6] = q.gy, info[7] = q.nsplit, info[8] = q.tps, info[9] = (uint64_t)((nhyp + q.nhb - 1) / q.nhb);
+    if (passes)
+      for (int h0 = 0; h0 < nhyp; h0 += q.nhb) {
+        const int64_t row[4] = {h0, std::min(q.nhb, nhyp - h0), 0, 0};
+        passes = std::copy(row, row + 4, passes);
+      }
+  }
+  info[3] = t.W / 2, info[4] = t.Mu, info[5] = t.p_pad;
+  if (plan == GradPlan::Ge0Views || plan == GradPlan::BmatViews) {
+    const obhip_basis &src = *b.grad->gb;
+    for (obhip_terms::GeGroup &grp : grad_view_groups(t, b, false)) {
+      ++info[11];
+      if (!view_group_one_pass(*grp.v, src)) ++info[12];
+    }
+  }
+  return 0;
 }
 
 }  // extern "C"

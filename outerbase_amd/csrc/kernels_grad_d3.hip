@@ -213,6 +213,26 @@ k_tmm_d3(const double *__restrict__ bm, const double *__restrict__ scale,
 
 }  // namespace
 
+// 8 waves x 4 view-terms per lane, the tile loaded between the barriers (the other block of the CU
+// computes meanwhile; with prefetch registers this shape spills 77); up to 1024 view-terms 2 per lane,
+// the tile prefetched into registers.  Measured with 2 per lane at every size: 1.21 against 1.11 ms
+// per launch at d = 8, 1.96 against 1.91 at C3 (half the row-weight v_readlanes per view-term).  Also
+// measured: 2 per lane without prefetch 1.27, 16 waves x 1 per lane 1.42 (before the weights went into
+// the staged columns).
+constexpr int kD3Waves = 8;
+D3Geom d3_geometry(const obhip_basis &b, const obhip_terms::GeD3 &g) {
+  const obhip_terms &v = *g.v;
+  const uint64_t ntiles = b.n_pad / kTileRows;
+  D3Geom q;
+  q.nu = v.p_pad > 1024 ? 4 : 2;
+  const uint64_t tpb = (uint64_t)kD3Waves * q.nu * 64;
+  q.pblocks = (v.p_pad + tpb - 1) / tpb;
+  // two resident blocks per CU, one round
+  const RowSplit rs = split_rows(ntiles, (uint64_t)device_cus(b.device) * 2 / q.pblocks, 4);
+  q.nsplit = rs.nsplit, q.tps = rs.tps;
+  return q;
+}
+
 // d_out (device, [2 nh][v.p]: u1 of the group's first hyper-parameter, of its second, u2 likewise;
 // the rows a mode does not compute are left alone) for one group of build_d3_groups
 int launch_tmm_d3(obhip_basis &b, const obhip_terms::GeD3 &g, int mode, const double *d_w1, const double *d_w2,
@@ -220,19 +240,10 @@ int launch_tmm_d3(obhip_basis &b, const obhip_terms::GeD3 &g, int mode, const do
   const obhip_basis &src = *b.grad->gb;
   const obhip_terms &v = *g.v;
   const uint64_t ntiles = b.n_pad / kTileRows;
-  // 8 waves x 4 view-terms per lane, the tile loaded between the barriers (the other block of the CU
-  // computes meanwhile; with prefetch registers this shape spills 77); up to 1024 view-terms 2 per lane,
-  // the tile prefetched into registers.  Measured with 2 per lane at every size: 1.21 against 1.11 ms
-  // per launch at d = 8, 1.96 against 1.91 at C3 (half the row-weight v_readlanes per view-term).  Also
-  // measured: 2 per lane without prefetch 1.27, 16 waves x 1 per lane 1.42 (before the weights went into
-  // the staged columns).
-  constexpr int nw = 8;
-  const int nu = v.p_pad > 1024 ? 4 : 2;
-  const uint64_t tpb = (uint64_t)nw * nu * 64;
-  const uint64_t pblocks = (v.p_pad + tpb - 1) / tpb;
-  // two resident blocks per CU, one round
-  const RowSplit rs = split_rows(ntiles, (uint64_t)device_cus(b.device) * 2 / pblocks, 4);
-  const uint64_t nsplit = rs.nsplit, tps = rs.tps;
+  constexpr int nw = kD3Waves;
+  const D3Geom geo = d3_geometry(b, g);
+  const int nu = geo.nu;
+  const uint64_t pblocks = geo.pblocks, nsplit = geo.nsplit, tps = geo.tps;
   const int nc = 2 * g.nh;
   double *part = nullptr;
   OB_TRY(b.workspace(nsplit * nc * v.p_pad * sizeof(double), (void **)&part));

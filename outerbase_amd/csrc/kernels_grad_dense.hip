@@ -474,36 +474,31 @@ bool tmm_ge0_supports(const obhip_terms &t) {
   return w2 >= 1 && w2 <= 4 && ge0_tile_bytes(t, 32) <= kLdsTile;
 }
 
-// (squared: the squared stores are formed from the gradient basis while staging -- gbsq is not needed)
-int launch_tmm_ge0(obhip_basis &b, obhip_terms &t, bool squared, const double *d_a, double *d_out) {
-  obhip_gradbasis &g = *b.grad;
-  const obhip_basis &src = *g.gb;
+// a tile of more than half the LDS leaves one block per CU: 16 waves in it instead of 8
+// ... and where TWO tiles fit the LDS, 16 waves with the next tile prefetched into the second
+// buffer (k_tmm_ge0_db; nw = 32 stands for it below)
+// Hyper-parameters beyond a multiple of 16 (d = 20 mat25: 4 of 20) in groups of four on the
+// 4 x 4 x 4 matrix instruction instead of a mostly empty 16-block: 1 to 8 left over take a pass of
+// their own (NHB = 0), behind a 16-block they ride along with it (the products formed once; 22-39
+// registers of the W2 = 2 kernel spilled outside the read pipeline).  d = 20 mat25 at the headline
+// terms, 20 hyper-parameters, never / a pass of their own / riding along: dense part
+// 5.47 / 4.52 / 3.50 ms, obfit evaluation 30.8 / 29.8 / 28.5 ms (profiles/r05_fours_ab.txt).
+Ge0Geom ge0_geometry(const obhip_basis &b, const obhip_terms &t) {
   const int nhyp = (int)b.model->nhyp();
-  const DevBuf<int> &dc0 = g.ge0col;  // absolute columns in the combined array (resident: no upload,
-                                      // and no synchronisation at the end of this function)
   const uint64_t ntiles = b.n_pad / kTileRows;
-  // a tile of more than half the LDS leaves one block per CU: 16 waves in it instead of 8
-  // ... and where TWO tiles fit the LDS, 16 waves with the next tile prefetched into the second
-  // buffer (k_tmm_ge0_db; nw = 32 stands for it below)
-  // Hyper-parameters beyond a multiple of 16 (d = 20 mat25: 4 of 20) in groups of four on the
-  // 4 x 4 x 4 matrix instruction instead of a mostly empty 16-block: 1 to 8 left over take a pass of
-  // their own (NHB = 0), behind a 16-block they ride along with it (the products formed once; 22-39
-  // registers of the W2 = 2 kernel spilled outside the read pipeline).  d = 20 mat25 at the headline
-  // terms, 20 hyper-parameters, never / a pass of their own / riding along: dense part
-  // 5.47 / 4.52 / 3.50 ms, obfit evaluation 30.8 / 29.8 / 28.5 ms (profiles/r05_fours_ab.txt).
+  Ge0Geom q;
   const size_t tile_lds = ge0_tile_bytes(t, 16);
   const bool two_tiles = 2 * tile_lds <= kLdsTile;
   bool one_per_cu = tile_lds > 80 * 1024;
   int nw = one_per_cu ? 16 : 8;
   if (two_tiles) nw = 32;
   if (nw == 32) one_per_cu = true;
+  q.nw = nw;
   const uint64_t tpb = (uint64_t)(nw == 32 ? 16 : nw) * 64;
-  const uint64_t pblocks = (t.p_pad + tpb - 1) / tpb;
+  q.pblocks = (t.p_pad + tpb - 1) / tpb;
   const int ncu = device_cus(b.device);
-  const RowSplit rs = split_rows(ntiles, (uint64_t)ncu * (one_per_cu ? 1 : 2) / pblocks);
-  const uint64_t nsplit = rs.nsplit, tps = rs.tps;
-  const dim3 grid((unsigned)nsplit, (unsigned)pblocks);
-  ProfScope ps(squared ? "sqtmm_gradhyp_dense" : "tmm_gradhyp_dense");
+  const RowSplit rs = split_rows(ntiles, (uint64_t)ncu * (one_per_cu ? 1 : 2) / q.pblocks);
+  q.nsplit = rs.nsplit, q.tps = rs.tps;
   // 16 hyper-parameters per pass: with two 16-blocks per pass (NHB = 2) the 64 accumulator
   // registers of a wave no longer fit beside the pipeline and the compiler spills them in the
   // inner loop (measured 8.4 ms against 2 x 1.7 ms at C3)
@@ -516,16 +511,44 @@ int launch_tmm_ge0(obhip_basis &b, obhip_terms &t, bool squared, const double *d
     if (n4 > 0 && 2 * ge0_tile_bytes(t, 16 + 4 * n4) > kLdsTile) n4 = 0;
     const int nh = n4 > 0 ? rem : (n4 < 0 ? rem : std::min(16, rem));
     const int hs = n4 > 0 ? 16 + 4 * n4 : (n4 < 0 ? -4 * n4 : 16);
-    double *part = nullptr;
-    OB_TRY(b.workspace(nsplit * hs * t.p_pad * sizeof(double), (void **)&part));
-    OB_TRY(run_tmm_ge0(squared, nw, n4, src, t, dc0.p, nhyp, h0, d_a, grid, ntiles, tps, part));
-    hipLaunchKernelGGL(k_ge0_reduce, dim3((unsigned)((t.p + 255) / 256), (unsigned)nh), dim3(256), 0,
-                       cur_stream(), part, (int)nsplit, hs, t.p_pad, (int)t.p, nh,
-                       d_out + (uint64_t)h0 * t.p);
-    OB_HIP(hipGetLastError());
+    q.passes.push_back({h0, nh, n4, hs});
     h0 += nh;
   }
+  return q;
+}
+
+// (squared: the squared stores are formed from the gradient basis while staging -- gbsq is not needed)
+int launch_tmm_ge0(obhip_basis &b, obhip_terms &t, bool squared, const double *d_a, double *d_out) {
+  obhip_gradbasis &g = *b.grad;
+  const obhip_basis &src = *g.gb;
+  const int nhyp = (int)b.model->nhyp();
+  const DevBuf<int> &dc0 = g.ge0col;  // absolute columns in the combined array (resident: no upload,
+                                      // and no synchronisation at the end of this function)
+  const uint64_t ntiles = b.n_pad / kTileRows;
+  const Ge0Geom geo = ge0_geometry(b, t);
+  const uint64_t nsplit = geo.nsplit, tps = geo.tps;
+  const dim3 grid((unsigned)nsplit, (unsigned)geo.pblocks);
+  ProfScope ps(squared ? "sqtmm_gradhyp_dense" : "tmm_gradhyp_dense");
+  for (const Ge0Pass &ps1 : geo.passes) {
+    double *part = nullptr;
+    OB_TRY(b.workspace(nsplit * ps1.hs * t.p_pad * sizeof(double), (void **)&part));
+    OB_TRY(run_tmm_ge0(squared, geo.nw, ps1.n4, src, t, dc0.p, nhyp, ps1.h0, d_a, grid, ntiles, tps, part));
+    hipLaunchKernelGGL(k_ge0_reduce, dim3((unsigned)((t.p + 255) / 256), (unsigned)ps1.nh), dim3(256), 0,
+                       cur_stream(), part, (int)nsplit, ps1.hs, t.p_pad, (int)t.p, ps1.nh,
+                       d_out + (uint64_t)ps1.h0 * t.p);
+    OB_HIP(hipGetLastError());
+  }
   return 0;
+}
+
+BtuGeom btu_geometry(const obhip_basis &b, const obhip_terms &t) {
+  const uint64_t ntiles = b.n_pad / kTileRows;
+  BtuGeom q;
+  q.nhb = kNHB;
+  q.gy = (unsigned)((t.p_pad + 2047) / 2048);
+  const RowSplit rs = split_rows(ntiles, 1024 / q.gy);
+  q.nsplit = rs.nsplit, q.tps = rs.tps;
+  return q;
 }
 
 int launch_bt_times_ge0(obhip_basis &b, obhip_terms &t, bool squared, const double *d_a, double *d_out) {
@@ -534,9 +557,9 @@ int launch_bt_times_ge0(obhip_basis &b, obhip_terms &t, bool squared, const doub
   const obhip_basis &src = squared ? *g.gbsq : *g.gb;
   const int nhyp = (int)b.model->nhyp();
   const uint64_t ntiles = b.n_pad / kTileRows;
-  const unsigned gy = (unsigned)((t.p_pad + 2047) / 2048);
-  const RowSplit rs = split_rows(ntiles, 1024 / gy);
-  const uint64_t nsplit = rs.nsplit, tps = rs.tps;
+  const BtuGeom geo = btu_geometry(b, t);
+  const unsigned gy = geo.gy;
+  const uint64_t nsplit = geo.nsplit, tps = geo.tps;
   double *part = nullptr;
   OB_TRY(b.workspace(nsplit * kNHB * t.p_pad * sizeof(double), (void **)&part));
   ProfScope ps(squared ? "sqtmm_gradhyp_dense" : "tmm_gradhyp_dense");

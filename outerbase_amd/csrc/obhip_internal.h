@@ -739,8 +739,26 @@ bool build_d3_groups(obhip_terms &t, const obhip_basis &b);
 // kernels_grad_dense.hip: d_out (device, p x nhyp column-major) = sum_i a_i ge[h, 0]_i B_ik (squared: of
 // the squared stores), enqueued on the current stream; t prepared for b, b.grad built
 bool tmm_ge0_supports(const obhip_terms &t);  // at most 8 column slots and the tile within the LDS
+// the launch geometry of launch_tmm_ge0: what it runs and what obhip_grad_plan_info reports
+struct Ge0Pass {
+  int h0, nh;  // hyper-parameters h0 .. h0 + nh - 1
+  int n4;      // > 0: a 16-block and n4 groups of four; < 0: |n4| groups of four only; 0: the 16-block only
+  int hs;      // hyper-parameter slots of the pass' partial sums
+};
+struct Ge0Geom {
+  int nw;  // 8 | 16: k_tmm_ge0 with that many waves; 32: k_tmm_ge0_db (16 waves, two tile buffers)
+  uint64_t pblocks, nsplit, tps;
+  std::vector<Ge0Pass> passes;
+};
+Ge0Geom ge0_geometry(const obhip_basis &b, const obhip_terms &t);
 int launch_tmm_ge0(obhip_basis &b, obhip_terms &t, bool squared, const double *d_a, double *d_out);
 // (from the materialised design matrix; squared: b.grad->gbsq built)
+struct BtuGeom {
+  int nhb;  // hyper-parameters per pass
+  unsigned gy;
+  uint64_t nsplit, tps;
+};
+BtuGeom btu_geometry(const obhip_basis &b, const obhip_terms &t);
 int launch_bt_times_ge0(obhip_basis &b, obhip_terms &t, bool squared, const double *d_a, double *d_out);
 // kernels_grad.hip: device-level forms (inputs and n-sized results in HBM) for the likelihood classes
 int grad_mm_dev(obhip_basis &b, obhip_terms &t, bool squared, const double *a_host, const double *d_a,
@@ -754,6 +772,12 @@ constexpr int kD3Pre = 20;  // k_tmm_d3: prefetch registers per thread => at mos
 // group's first hyper-parameter, of its second, u2 likewise; mode bit 0: u1, bit 1: u2
 int launch_tmm_d3(obhip_basis &b, const obhip_terms::GeD3 &g, int mode, const double *d_w1, const double *d_w2,
                   double *d_out);
+// its launch geometry: what it runs and what obhip_grad_plan_info reports
+struct D3Geom {
+  int nu;  // view-terms per lane: 2 (tile prefetched into registers) or 4 (two half-runs)
+  uint64_t pblocks, nsplit, tps;
+};
+D3Geom d3_geometry(const obhip_basis &b, const obhip_terms::GeD3 &g);
 int grad_dual_dev(obhip_basis &b, obhip_terms &t, const double *a_host, const double *d_M, const double *d_w1,
                   const double *d_w2, double *out_dot, double *out_sq);
 int grad_wdot_dev(const double *d_G, const double *d_w, uint64_t n, uint64_t ncol, double *out_host);

@@ -442,6 +442,33 @@ class outerbase:
         call("obhip_basis_residvar_gradhyp", self._h, t._h, self.om._h, ptr(out))
         return out
 
+    def grad_plan_info(self, terms):
+        """What the hyper-gradient products of (self, terms) will launch (obhip_grad_plan_info,
+        include/obhip.h): the plan, the k_tmm_d3 groups and the dense pass with its passes."""
+        t = _terms_of(self.om, terms)
+        info = np.zeros(16, dtype=np.uint64)
+        call("obhip_grad_plan_info", self._h, t._h, ptr(info), None, None, None)
+        groups = np.zeros((int(info[1]), 10), dtype=np.uint64)
+        members = np.zeros(max(int(info[10]), 1), dtype=np.uint64)
+        passes = np.zeros((int(info[9]), 4), dtype=np.int64)
+        call("obhip_grad_plan_info", self._h, t._h, ptr(info), ptr(groups) if groups.size else None, ptr(members),
+             ptr(passes) if passes.size else None)
+        v = [int(q) for q in info]
+        keys = ("nh", "W", "Mu", "p", "p_pad", "NU", "pblocks", "nsplit", "tps")
+        out_groups, m0 = [], 0
+        for row in groups:
+            g = dict(zip(keys, (int(q) for q in row[:9])))
+            g["members"] = [int(h) for h in members[m0:m0 + int(row[9])]]
+            m0 += int(row[9])
+            out_groups.append(g)
+        dense = None
+        if v[2]:
+            dense = dict(kernel=("ge0_db", "ge0_16", "ge0_8", "bt_times_u")[v[2] - 1], W2=v[3], Mu=v[4], p_pad=v[5],
+                         pblocks=v[6], nsplit=v[7], tps=v[8], passes=[tuple(int(q) for q in row) for row in passes])
+        return dict(plan=("Fused", "Ge0Views", "BmatViews", "FullViews")[v[0]], groups=out_groups, dense=dense,
+                    W2=v[3], Mu=v[4], p_pad=v[5], view_groups=v[11], view_groups_per_hyp=v[12], nhyp=v[13],
+                    ntiles=v[14], cus=v[15])
+
     def matmul(self, terms, a):
         return self._mm("obhip_basis_mm", terms, a, "p", "n")
 

@@ -287,6 +287,64 @@ def ref_sqcolsums_gradhyp(B, bB, dB, bdB, C):
     return want, _sum_tol(C, bound, B.shape[0], 2 * np.einsum("it,ith->th", Bf, dBf))
 
 
+def _sq_grad_cube(B, bB, dB, bdB):
+    """d(B^2)/dhyp = 2 B dB per entry (the factor 2 is exact): value, bound, |value| in float64"""
+    Bf, bf, dBf, bdf = np.abs(_f64(B)), _f64(bB), np.abs(_f64(dB)), _f64(bdB)
+    return 2 * B[:, :, None] * dB, 2 * (bf[:, :, None] * dBf + Bf[:, :, None] * bdf), 2 * Bf[:, :, None] * dBf
+
+
+def ref_sqtmm_gradhyp(B, bB, dB, bdB, v, C):
+    """sum_i v_i 2 B[i, t] dB[i, t, h] with v of any sign: p x nhyp, n summands"""
+    S, bS, aS = _sq_grad_cube(B, bB, dB, bdB)
+    v = np.asarray(v, dtype=ld)
+    av = np.abs(_f64(v))
+    return np.einsum("ith,i->th", S, v), _sum_tol(C, np.einsum("ith,i->th", bS, av), B.shape[0],
+                                                  np.einsum("ith,i->th", aS, av))
+
+
+def ref_sqmm_gradhyp(B, bB, dB, bdB, a, C):
+    """sum_t a_t 2 B[i, t] dB[i, t, h]: n x nhyp, p summands"""
+    S, bS, aS = _sq_grad_cube(B, bB, dB, bdB)
+    a = np.asarray(a, dtype=ld)
+    aa = np.abs(_f64(a))
+    return np.einsum("ith,t->ih", S, a), _sum_tol(C, np.einsum("ith,t->ih", bS, aa), B.shape[1],
+                                                  np.einsum("ith,t->ih", aS, aa))
+
+
+def ref_matmul_gradhyp_dot(dB, bdB, a, v, C):
+    """sum_i sum_t v_i a_t dB[i, t, h]: nhyp values, each a double sum of n p summands"""
+    a, v = np.asarray(a, dtype=ld), np.asarray(v, dtype=ld)
+    aa, av = np.abs(_f64(a)), np.abs(_f64(v))
+    want = np.einsum("ith,t,i->h", dB, a, v)
+    return want, _sum_tol(C, np.einsum("ith,t,i->h", _f64(bdB), aa, av), dB.shape[0] * dB.shape[1],
+                          np.einsum("ith,t,i->h", np.abs(_f64(dB)), aa, av))
+
+
+def term_var(basisvar, knotptst, terms):
+    """om$getvar(terms) = exp(sum_l basisvar[knotptst[l] + t_l]) in long double, and the bound of a float64
+    evaluation of it: d additions in the exponent (absolute there, relative here) and one exponential"""
+    terms = np.asarray(terms, dtype=np.int64)
+    bv = np.asarray(basisvar, dtype=ld)[np.asarray(knotptst, dtype=np.int64)[None, :-1] + terms]
+    varc = np.exp(bv.sum(axis=1))
+    return varc, _f64(varc) * (gamma(terms.shape[1]) * np.abs(_f64(bv)).sum(axis=1) + 2 * U)
+
+
+def ref_residvar_gradhyp(B, bB, dB, bdB, varc, bvarc, lv, C):
+    """d/dhyp_h (1 - sum_t varc_t B[i, t]^2) = - sum_t varc_t (2 B dB[i, t, h] + B^2 lv[t, h]), lv[t, h] =
+    d log varc_t / d hyp_h (float64 data, exact): n x nhyp, 2 p summands and four roundings in forming them.
+    bvarc (term_var) enters as it is, not times C: it is a bound of float64 arithmetic, not of conditioning."""
+    S, bS, aS = _sq_grad_cube(B, bB, dB, bdB)
+    lv = np.asarray(lv, dtype=ld)
+    Bf, bf, alv = np.abs(_f64(B)), _f64(bB), np.abs(_f64(lv))
+    T = S + (B * B)[:, :, None] * lv[None, :, :]
+    bT = bS + (2 * Bf * bf)[:, :, None] * alv[None, :, :]
+    aT = aS + (Bf * Bf)[:, :, None] * alv[None, :, :]
+    vf = _f64(varc)
+    want = -np.einsum("ith,t->ih", T, np.asarray(varc, dtype=ld))
+    return want, _sum_tol(C, np.einsum("ith,t->ih", bT, vf), 2 * B.shape[1] + 4, np.einsum("ith,t->ih", aT, vf)) \
+        + np.einsum("ith,t->ih", aT, _f64(bvarc))
+
+
 # -- measuring ---------------------------------------------------------------------------------------
 def maxnorm_relerr(got, want):
     """the criterion the older tests use: max |got - want| / max |want|"""

@@ -160,6 +160,74 @@ def test_instrument_against_50_digit_arithmetic():
     print("long double against 50 digits: worst error %.3g eps_longdouble x bound" % worst)
 
 
+@pytest.mark.parametrize("kind", ["mat25", "mat25pow", "mat25ang"])
+def test_gradient_product_references_against_50_digit_arithmetic(kind):
+    """ref_sqtmm_gradhyp (signed v), ref_sqmm_gradhyp, ref_matmul_gradhyp_dot and ref_residvar_gradhyp on a
+    case small enough to sum every entry in 50 digits: the long double value, the sum of |summands| under
+    gamma_k and the propagated bound under C are each what their docstrings say."""
+    mp = pytest.importorskip("mpmath")
+    kinds = [kind, "mat25", kind]
+    om = oracle_model(kinds, knots_for(kinds, 8))
+    n, terms = 3, np.array([[0, 0, 0], [1, 0, 0], [2, 1, 0], [0, 3, 2], [1, 2, 3]])
+    p, nh = len(terms), len(om.hypmatch)
+    rng = np.random.default_rng(len(kind))
+    x = sample_x(rng, n, kinds)
+    a, v = rng.standard_normal(p), rng.standard_normal(n)
+    assert (a < 0).any() and (a > 0).any() and (v < 0).any() and (v > 0).any()
+    ref = reference_of(om, x, grad=True)
+    B, bB = ref.getmat(terms)
+    dB, bdB = ref.getmat_gradhyp(terms)
+    varc, bvarc = E.term_var(om.basisvar, om.knotptst, terms)
+    lv = om.getlvar_gradhyp(terms)
+    f = lambda q: mp.mpf(float(q))
+    with mp.workdps(50):
+        Bm = [[_mp_entry(om, x, terms[t], i) for t in range(p)] for i in range(n)]
+        dBm = [[[_mp_entry(om, x, terms[t], i, h) for h in range(nh)] for t in range(p)] for i in range(n)]
+        vm = [mp.exp(mp.fsum(f(om.basisvar[om.knotptst[l] + terms[t, l]]) for l in range(om.d))) for t in range(p)]
+        R, T = range(n), range(p)
+        # per product: entries -> (summands, their propagated bounds, k)
+        sq = lambda i, t, h: (2 * Bm[i][t] * dBm[i][t][h],
+                              2 * (f(bB[i, t]) * abs(dBm[i][t][h]) + abs(Bm[i][t]) * f(bdB[i, t, h])))
+        res = lambda i, t, h: [(-vm[t] * sq(i, t, h)[0], vm[t] * sq(i, t, h)[1]),         # two summands per term
+                               (-vm[t] * Bm[i][t] ** 2 * f(lv[t, h]), vm[t] * 2 * abs(Bm[i][t]) * f(bB[i, t]) * abs(f(lv[t, h])))]
+        products = {
+            "sqtmm": (E.ref_sqtmm_gradhyp, (B, bB, dB, bdB, v), (p, nh), n,
+                      lambda t, h: [(f(v[i]) * sq(i, t, h)[0], abs(f(v[i])) * sq(i, t, h)[1]) for i in R]),
+            "sqmm": (E.ref_sqmm_gradhyp, (B, bB, dB, bdB, a), (n, nh), p,
+                     lambda i, h: [(f(a[t]) * sq(i, t, h)[0], abs(f(a[t])) * sq(i, t, h)[1]) for t in T]),
+            "dot": (E.ref_matmul_gradhyp_dot, (dB, bdB, a, v), (nh,), n * p,
+                    lambda h: [(f(v[i]) * f(a[t]) * dBm[i][t][h], abs(f(v[i]) * f(a[t])) * f(bdB[i, t, h]))
+                               for i in R for t in T]),
+            "residvar": (E.ref_residvar_gradhyp, (B, bB, dB, bdB, varc, bvarc, lv), (n, nh), 2 * p + 4,
+                         lambda i, h: [q for t in T for q in res(i, t, h)]),
+        }
+        for name, (fn, args, shape, k, summands) in products.items():
+            want, tol0 = fn(*args, 0.0)
+            tol1 = fn(*args, 1.0)[1]
+            assert want.shape == tol0.shape == shape, name
+            worst = 0.0
+            for idx in np.ndindex(*shape):
+                s = summands(*idx)
+                exact, absum, bound = mp.fsum(q[0] for q in s), mp.fsum(abs(q[0]) for q in s), mp.fsum(q[1] for q in s)
+                scale = float(absum + bound)
+                err = float(abs(_mp_of(want[idx]) - exact))
+                worst = max(worst, err / (E.EPS * scale))
+                assert err <= 64 * E.EPS * scale, (name, idx, err, scale)
+                # C x (propagated bound) and gamma_k x (sum of |summands|), each to float64 rounding; residvar's
+                # term for the float64 exponential of varc (not under C) comes on top of the latter
+                # (to 1e-6: |summands| are taken of the long double entries, right to eps_longdouble x their bounds)
+                assert abs(float(tol1[idx] - tol0[idx]) - float(bound)) <= 1e-6 * float(bound), (name, idx)
+                g = E.gamma(k) * float(absum)
+                top = float(np.max(bvarc / np.asarray(varc, dtype=np.float64))) * float(absum) if name == "residvar" else 0.0
+                assert g * (1 - 1e-6) <= tol0[idx] <= (g + top) * (1 + 1e-6), (name, idx)
+            print("%s %s: long double against 50 digits, worst %.3g eps_longdouble x (sum |summands| + bound)"
+                  % (kind, name, worst))
+        for t in range(p):       # term_var: the value, and its bound covers a float64 evaluation
+            assert abs(_mp_of(varc[t]) - vm[t]) <= 8 * E.EPS * float(vm[t])
+            v64 = np.exp(np.sum(om.basisvar[om.knotptst[:-1] + terms[t]]))
+            assert abs(mp.mpf(float(v64)) - vm[t]) <= float(bvarc[t]) and bvarc[t] <= 1e-13 * float(vm[t])
+
+
 # ---- the float64 oracle against the instrument ------------------------------------------------
 @pytest.mark.parametrize("name", list(CASES))
 def test_oracle_sits_at_a_few_eps_of_the_per_entry_bound(name):
