@@ -1263,6 +1263,65 @@ int obhip_acquire(const obhip_posterior *post, const double *theta, const double
                   const uint8_t *skip, uint64_t k, int64_t *index, double *score, double *score0,
                   double *mean, double *var, uint64_t *n_picked);
 
+/* ---- acquisition gradients (no reference counterpart) --------------------------------------
+ * The latent variance d_i = b_i^T inv(H) b_i (the full posterior covariance, what the design and
+ * acquisition entries score with), the latent mean mu_i = b_i^T theta, an acquisition criterion and
+ * the gradients of all three by the inputs, at the n rows d_x (column-major n x d), in standardised
+ * units: what moves a point continuously to where a criterion is best.  Gradients are column-major
+ * n x d with leading dimension n.  With S = inv(H), b_ik = s_i P_ik (s_i the row scale, P_ik the
+ * term product; the names of obhip_predict_grad_dev), t_i = S b_i, rho_l = R'_l0 / R_l0, E_kl the
+ * product of term k's columns other than that of dimension l and r'_l,t that column's derivative:
+ *   d_i         = s sum_k t_ik P_k
+ *   dd_i/dx_l   = 2 s (rho_l sum_k t_ik P_k + sum_{k has l} t_ik E_kl r'_l,t)      (S is symmetric)
+ *   dmu_i/dx_l  =   s (rho_l sum_k theta_k P_k + sum_{k has l} theta_k E_kl r'_l,t)
+ * and with sd = sqrt(max(d, 0)), dsd = dd / (2 sd), mu~ = mu (maximize != 0: -mu, with -best and
+ * -level, as obhip_acquire_dev), t = best - xi - mu~, u = t / sd:
+ *   OBHIP_ACQ_EI        score t Phi(u) + sd phi(u)       gradient -Phi(u) dmu~ + phi(u) dsd
+ *   OBHIP_ACQ_PI        score Phi(u)                     gradient phi(u) (-dmu~ - u dsd) / sd
+ *   OBHIP_ACQ_LCB       score kappa sd - mu~             gradient kappa dsd - dmu~
+ *   OBHIP_ACQ_STRADDLE  score kappa sd - |mu~ - level|   gradient kappa dsd - sign(mu~ - level) dmu~
+ * with sign(0) = 0.  Where d <= 0: dsd = 0 and the scores are obhip_acquire_dev's sd = 0 branches, so
+ * the EI gradient is -dmu~ where t > 0 and 0 elsewhere and the PI gradient is 0.  A row with a
+ * coordinate that is not finite gets NaN in every output.  criterion and params (host: best, xi,
+ * kappa, level) are obhip_acquire_dev's, checked as there.
+ *
+ * inv(H) is formed by the first of these calls on a handle (as the design and acquisition entries
+ * form theirs on every call), kept on the handle and freed with it; a handle from
+ * obhip_posterior_condition_dev starts without one.  The rows are taken in chunks: per chunk the
+ * stored product Y = S B^T (term-major, in pooled scratch, every entry summed in one fixed order) and
+ * one fused kernel pass (csrc/kernels_acquire_dx.hip).  chunk_rows bounds the workspace -- two blocks
+ * of pad128(p) x chunk_rows doubles: 0 = the library's choice (at most 1 GiB per block), otherwise a
+ * positive multiple of 128; anything else is refused.  No atomics anywhere and a summation order that
+ * does not depend on where a row stands: two calls give the same bits, a chunked call the bits of the
+ * unchunked one, bit-identical rows bit-identical results.  The rules of the posterior block hold:
+ * every argument check runs before the first launch and a refused call changes nothing; n = 0 is a
+ * no-op; p <= 65535 and n <= 2^40.
+ *
+ * var_grad  d_var (n) = d_i (+ e^{2 sigma} when with_noise) and d_gradvar (n x d) = dd_i/dx_l; no
+ *           theta, no criterion.  Both required. */
+int obhip_posterior_var_grad_dev(const obhip_posterior *post, const double *d_x, uint64_t n,
+                                 uint64_t chunk_rows, int with_noise, double *d_var,
+                                 double *d_gradvar);
+/* d_theta (p): the standardised coefficients of one response.  d_score (n) and d_gradscore (n x d)
+ * are required; d_mean (n) = mu, d_gradmean (n x d) = dmu/dx (of mu, not of mu~), d_var (n) = d
+ * without the noise and d_gradvar (n x d) = dd/dx may each be NULL: not wanted, not written. */
+int obhip_acquire_grad_dev(const obhip_posterior *post, const double *d_theta, const double *d_x,
+                           uint64_t n, int criterion,
+                           const double *params /* host: best, xi, kappa, level */, int maximize,
+                           uint64_t chunk_rows, double *d_score, double *d_gradscore,
+                           double *d_mean, double *d_gradmean, double *d_var, double *d_gradvar);
+/* the same on host buffers; x and every gradient n x d column-major with leading dimension n */
+int obhip_acquire_grad(const obhip_posterior *post, const double *theta, const double *x, uint64_t n,
+                       int criterion, const double *params, int maximize, uint64_t chunk_rows,
+                       double *score, double *gradscore, double *mean, double *gradmean,
+                       double *var, double *gradvar);
+/* which kernel the two entries above run on this handle's terms: *fused = 1 the tile in LDS
+ * (*lds_bytes of it per workgroup), 0 the tile in pooled scratch (more than 8 factors per term, a
+ * tile beyond the LDS, or OBHIP_FORCE_GENERIC); *default_chunk_rows = what chunk_rows = 0 stands for.
+ * Any pointer may be NULL. */
+int obhip_acquire_grad_layout(const obhip_posterior *post, int *fused, uint64_t *lds_bytes,
+                              uint64_t *default_chunk_rows);
+
 /* ---- the model layer: lpdf, loglik_*, logpr_gauss, lpdfvec, predictor ------------------
  * Module rows src/interfaceR.cpp:696-762; classes src/fit.h:23-361; arithmetic
  * src/fit.cpp:37-612 and src/lpdfs/{loglik_std,loglik_gauss,loglik_gda,logpr_gauss}.cpp.

@@ -18,8 +18,8 @@ from .glm import GlmFit, fit_glm
 from .sensitivity import (ActiveSubspaceResult, GradMoments, InputMoments, ShapleyResult, Sobol2Result, SobolResult,
                           active_subspace, input_grad_moments, input_moments, interaction_effects, main_effects,
                           shapley, sobol, sobol2, sym_eigh, uniform_nodes)
-from .design import AcquireResult, DesignResult, Posterior, ThompsonResult
-from .torch_emulator import TorchCalibration, TorchEmulator
+from .design import AcquireGradResult, AcquireResult, DesignResult, Posterior, ThompsonResult
+from .torch_emulator import TorchAcquisition, TorchCalibration, TorchEmulator
 from .product import (CalibrationLoglik, fit_newton_product, predict_product, predict_product_grad,
                       product_fit_layout, product_grad_layout, product_layout, product_loglik, product_loglik_grad,
                       product_side)
@@ -38,7 +38,7 @@ __all__ = [
     "design_dx", "fit_newton_grad",
     "predict_jac", "predict_vjp", "predict_hvp", "predict_hess", "TorchEmulator",
     "GlmFit", "fit_glm",
-    "Posterior", "DesignResult", "ThompsonResult", "AcquireResult",
+    "Posterior", "DesignResult", "ThompsonResult", "AcquireResult", "AcquireGradResult", "TorchAcquisition",
     "InputMoments", "SobolResult", "input_moments", "uniform_nodes", "sobol", "main_effects",
     "Sobol2Result", "sobol2", "interaction_effects", "ShapleyResult", "shapley",
     "GradMoments", "ActiveSubspaceResult", "input_grad_moments", "active_subspace", "sym_eigh",

@@ -12,6 +12,7 @@
 #include <ctime>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <tuple>
 #include <type_traits>
@@ -626,6 +627,9 @@ struct obhip_posterior {
   double sigma = 0.0, logdet = 0.0;
   obhip::DevBuf<double> H;  // p x p, symmetric
   obhip::PostFactor f;
+  // S = inv(H) = X X^T (pp x pp), built by the first call that needs it (posterior_inverse), freed with the handle
+  mutable obhip::DevBuf<double> S;
+  mutable std::mutex S_lock;
 };
 namespace obhip {
 // *out = a new handle that takes the symmetric p x p d_H over (copied); waits for the factorisation
@@ -695,6 +699,24 @@ int launch_acq_update(const AcqStep &s, double *d_score0);
 // the partial pairs -> the step's pick: index and score appended at slot `step`, the row marked, x_j gathered
 // into d_xj, delta and the incumbent into scal; no eligible candidate: scal[5] = 1 and nothing else written
 int launch_acq_pick(const AcqStep &s, uint64_t d, uint64_t step, int64_t *d_index, double *d_score, double *d_xj);
+// acquire_dx.cpp / kernels_acquire_dx.hip: input gradients of the latent variance and of the acquisition criteria
+// (include/obhip.h, "acquisition gradients")
+constexpr int kAdxNone = -1;  // no criterion: the variance and its gradient only
+struct AcqDxArgs {
+  double sgn = 1.0, best = 0.0, xi = 0.0, kappa = 0.0, level = 0.0;  // best, level: in the sign scored with
+  double noise = 0.0;   // added to var
+  uint64_t row0 = 0, ldo = 0;  // the chunk's first row and the leading dimension of every output
+  double *score = nullptr, *gradscore = nullptr;  // n, n x d: required with a criterion
+  double *mean = nullptr, *gradmean = nullptr, *var = nullptr, *gradvar = nullptr;  // may be null
+};
+// *S = the handle's inv(H), formed on first use exactly as the design and acquisition entries form theirs
+int posterior_inverse(const obhip_posterior &post, const double **S);
+bool acquire_dx_fused(const obhip_terms &t);  // predict_dx_supports and no OBHIP_FORCE_GENERIC
+uint64_t acquire_dx_lds_bytes(const obhip_terms &t, uint64_t d, bool fused);
+// one chunk: the n rows at d_x (column-major, leading dimension ldx) against their stored product d_Y = S B^T
+// (term-major, pitch npad >= the rows' 64-row tiles, zeros behind row n); crit: kAdxNone or OBHIP_ACQ_*
+int launch_acquire_dx(const obhip_model &m, obhip_terms &t, int crit, const double *d_theta, const double *d_Y,
+                      uint64_t npad, const double *d_x, uint64_t ldx, uint64_t n, const AcqDxArgs &a);
 // sample.cpp / kernels_sample.hip: draws from N(theta, inv(H)) and the per-draw extremum of their sample
 // paths over a candidate set (include/obhip.h, "posterior draws")
 constexpr uint64_t kDrawChunk = 64;  // draws of one launch of k_draw outside the fused pass (which takes up to 128)

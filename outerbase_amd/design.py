@@ -24,7 +24,9 @@ normals (or the caller does, z=), the library the arithmetic.
 Acquisition.  acquire picks k candidates one after the other by expected improvement, probability of
 improvement, a confidence bound or the straddle contour criterion of the latent mean and variance; after
 every pick the run there is given a value without being made (the kriging believer or a constant liar) and
-every candidate's mean and variance are downdated on the device (csrc/kernels_acquire.hip).
+every candidate's mean and variance are downdated on the device (csrc/kernels_acquire.hip).  var_grad and
+acquire_grad give the latent variance, the same four criteria and their gradients by the inputs at any rows
+(csrc/kernels_acquire_dx.hip): what a gradient ascent from the best candidates needs.
 
 torch holds the device memory; all arithmetic is in libobhip.
 """
@@ -84,6 +86,15 @@ class AcquireResult:
     picked; score0 (m): every candidate's criterion at the first step, eligible or not; mean, var (m): the latent
     mean and variance (without the noise) of every candidate after all fantasies; criterion.  Fewer than k
     picks: no eligible candidate was left."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+class AcquireGradResult:
+    """score (n): the criterion at every row; grad (n x d): its gradient by the inputs; mean, var (n): the latent
+    mean and variance (without the noise); grad_mean, grad_var (n x d): their gradients; criterion.  A row with a
+    coordinate that is not finite has NaN everywhere."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -305,6 +316,123 @@ class Posterior:
                 score, score0 = sc[1] * score + off, sc[1] * score0 + off
         return AcquireResult(index=index.cpu().numpy()[:n].copy(), score=score, score0=score0, mean=mean, var=var,
                              criterion=criterion, n_picked=n, k=k)
+
+    # -- acquisition gradients ---------------------------------------------------------------
+    @staticmethod
+    def _chunk_rows(chunk_rows):
+        chunk_rows = int(chunk_rows)
+        if chunk_rows < 0 or chunk_rows % 128:
+            raise ValueError("chunk_rows must be 0 (the library's choice) or a positive multiple of 128")
+        return chunk_rows
+
+    def var_grad(self, x, noise=False, chunk_rows=0):
+        """The latent variance d_i = b_i^T inv(H) b_i at the rows x (n x d) -- the full posterior covariance, what
+        select and acquire score with; noise=True adds e^{2 sigma} -- and its gradient by the inputs,
+        dd_i/dx = 2 (db_i/dx)^T inv(H) b_i -> (var (n), grad (n x d)), standardised units.  A row with a coordinate
+        that is not finite gets NaN.  inv(H) is formed by the first call on this posterior and kept with it.
+        chunk_rows bounds the workspace (two blocks of pad128(p) x chunk_rows doubles): 0 = the library's choice,
+        otherwise a positive multiple of 128; the result does not depend on it, bit for bit."""
+        import torch
+        self._need()
+        x = _rows(self.om, x, "x")
+        chunk_rows = self._chunk_rows(chunk_rows)
+        n, d = x.shape
+        if n == 0:
+            return np.zeros(0), np.zeros((0, d))
+        dev = _stream()
+        dx = _dev_cols(x, dev)
+        var = torch.empty(n, dtype=torch.float64, device=dev)
+        grad = torch.empty((d, n), dtype=torch.float64, device=dev)
+        call("obhip_posterior_var_grad_dev", self._h, dx.data_ptr(), n, chunk_rows, int(bool(noise)), var.data_ptr(),
+             grad.data_ptr())
+        torch.cuda.synchronize()
+        return var.cpu().numpy(), grad.cpu().numpy().T.copy()
+
+    def _acquire_grad_args(self, criterion, best, level, kappa, xi, response):
+        """the criterion's parameters, checked and standardised: (best, xi, kappa, level), (centre, scale) or None"""
+        if criterion not in ACQUISITIONS:
+            raise ValueError("criterion must be one of %s" % sorted(ACQUISITIONS))
+        if criterion in ("ei", "pi") and best is None:
+            raise ValueError("criterion %r needs best, the incumbent" % criterion)
+        if criterion == "straddle" and level is None:
+            raise ValueError("criterion 'straddle' needs level")
+        best, level = 0.0 if best is None else float(best), 0.0 if level is None else float(level)
+        kappa, xi = float(kappa), float(xi)
+        if not all(np.isfinite(v) for v in (best, level, xi)):
+            raise ValueError("best, level and xi must be finite")
+        if not (np.isfinite(kappa) and kappa >= 0):
+            raise ValueError("kappa must be finite and >= 0")
+        sc = self._scale(response)
+        if sc is not None:                                       # raw units -> standardised
+            best, level, xi = (best - sc[0]) / sc[1], (level - sc[0]) / sc[1], xi / sc[1]
+        return (best, xi, kappa, level), sc
+
+    def acquire_grad(self, x, theta, criterion="ei", best=None, level=None, kappa=1.96, xi=0.0, maximize=False,
+                     response=None, chunk_rows=0):
+        """An acquisition criterion and its gradient by the inputs at the rows x (n x d): what moves a point
+        continuously to where the criterion is best (screen a candidate cloud with acquire, then refine the best
+        starts by gradient ascent on score).  theta (p): the standardised coefficients of one response.  With the
+        latent mean mu = b^T theta, the latent variance d = b^T inv(H) b (without the noise), sd = sqrt(max(d, 0)),
+        dsd = dd / (2 sd), written for minimisation (maximize=True: the same on -mu, -best, -level), t = best - xi
+        - mu, u = t / sd:
+          "ei"        score t Phi(u) + sd phi(u)     gradient -Phi(u) dmu + phi(u) dsd        (best required)
+          "pi"        score Phi(u)                   gradient phi(u) (-dmu - u dsd) / sd      (best required)
+          "lcb"       score kappa sd - mu            gradient kappa dsd - dmu
+          "straddle"  score kappa sd - |mu - level|  gradient kappa dsd - sign(mu - level) dmu  (level required)
+        sign(0) = 0.  Where d <= 0, dsd is taken as 0 and the scores are acquire's sd = 0 branches: the ei gradient
+        is -dmu where t > 0 and 0 elsewhere, the pi gradient 0.  A row with a coordinate that is not finite gets NaN
+        in every output.  The scores are those of acquire(k=1).score0 up to rounding (acquire sums d in another
+        order).
+        response=j on a posterior that carries meansd: best, level and xi are given in raw units of response j and
+        standardised on the way in; with sca the response's scale, mean, score (ei, lcb, straddle) and their
+        gradients come back times sca, var and its gradient times sca^2, pi is left alone; the centre is added to
+        mean and to the lcb score and has no gradient.
+        inv(H) is formed by the first call on this posterior and kept with it.  chunk_rows bounds the workspace
+        (two blocks of pad128(p) x chunk_rows doubles): 0 = the library's choice, otherwise a positive multiple of
+        128; the result does not depend on it, bit for bit.  Two calls give the same bits.
+        -> AcquireGradResult(score (n), grad (n x d), mean (n), grad_mean (n x d), var (n), grad_var (n x d),
+        criterion)"""
+        import torch
+        self._need()
+        x = _rows(self.om, x, "x")
+        chunk_rows = self._chunk_rows(chunk_rows)
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.shape != (self.p,):
+            raise ValueError("theta must be the p standardised coefficients of one response")
+        pars, sc = self._acquire_grad_args(criterion, best, level, kappa, xi, response)
+        n, d = x.shape
+        if n == 0:
+            z1, z2 = np.zeros(0), np.zeros((0, d))
+            return AcquireGradResult(score=z1, grad=z2, mean=z1.copy(), grad_mean=z2.copy(), var=z1.copy(),
+                                     grad_var=z2.copy(), criterion=criterion)
+        dev = _stream()
+        dx = _dev_cols(x, dev)
+        dth = torch.from_numpy(theta).to(dev)
+        score, mean, var = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(3))
+        grad, gmean, gvar = (torch.empty((d, n), dtype=torch.float64, device=dev) for _ in range(3))
+        call("obhip_acquire_grad_dev", self._h, dth.data_ptr(), dx.data_ptr(), n, ACQUISITIONS[criterion],
+             (C.c_double * 4)(*pars), int(bool(maximize)), chunk_rows, score.data_ptr(), grad.data_ptr(),
+             mean.data_ptr(), gmean.data_ptr(), var.data_ptr(), gvar.data_ptr())
+        torch.cuda.synchronize()
+        score, mean, var = (a.cpu().numpy() for a in (score, mean, var))
+        grad, gmean, gvar = (a.cpu().numpy().T.copy() for a in (grad, gmean, gvar))
+        if sc is not None:
+            mean, gmean, var, gvar = sc[0] + sc[1] * mean, sc[1] * gmean, sc[1] ** 2 * var, sc[1] ** 2 * gvar
+            if criterion in ("ei", "straddle"):
+                score, grad = sc[1] * score, sc[1] * grad
+            elif criterion == "lcb":                             # kappa sd - mu: the centre comes back with the sign of -mu
+                score, grad = sc[1] * score + (sc[0] if maximize else -sc[0]), sc[1] * grad
+        return AcquireGradResult(score=score, grad=grad, mean=mean, grad_mean=gmean, var=var, grad_var=gvar,
+                                 criterion=criterion)
+
+    def acquire_grad_layout(self):
+        """-> (fused, lds_bytes, default_chunk_rows): whether var_grad / acquire_grad keep their tile in LDS on this
+        posterior's terms, the LDS of a workgroup, and the rows chunk_rows=0 stands for"""
+        self._need()
+        _stream()
+        fused, lds, rows = C.c_int(0), C.c_uint64(0), C.c_uint64(0)
+        call("obhip_acquire_grad_layout", self._h, C.byref(fused), C.byref(lds), C.byref(rows))
+        return bool(fused.value), lds.value, rows.value
 
     # -- draws -------------------------------------------------------------------------------
     def _draw_args(self, theta, n_draws, seed, z):

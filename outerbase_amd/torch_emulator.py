@@ -6,6 +6,10 @@ torch.optim loop: forward is obhip_predict_multi_dev, backward the vector-Jacobi
 obhip_predict_vjp_multi_dev, the backward of that the Hessian-vector and Jacobian-vector product
 obhip_predict_hvp_multi_dev (include/obhip.h), all on the current stream; neither the n x d x q
 Jacobian nor a Hessian is formed.  All arithmetic is in libobhip; torch holds the memory and the graph.
+
+TorchCalibration does the same for the calibration log-likelihood by the candidate parameters and
+TorchAcquisition for an acquisition criterion of a Posterior by the inputs (obhip_acquire_grad_dev), each
+differentiable once.
 """
 import ctypes as C
 
@@ -21,6 +25,10 @@ if torch is None:  # host-only use of the package: the name exists, building one
     class TorchCalibration:
         def __init__(self, *args, **kwargs):
             raise ImportError("TorchCalibration needs torch")
+
+    class TorchAcquisition:
+        def __init__(self, *args, **kwargs):
+            raise ImportError("TorchAcquisition needs torch")
 else:
     def _colmajor(a):
         """the (rows, cols) tensor a as a contiguous (cols, rows) tensor: column-major storage of a"""
@@ -171,3 +179,62 @@ else:
             if t.device != self.theta.device:
                 raise ValueError("t is on another device than the calibration")
             return _CalibrationLoglik.apply(t, self)
+
+    class _AcquireScore(torch.autograd.Function):
+        """score (n) of the rows x (n x d) and, saved for backward, its gradient (n x d): one
+        obhip_acquire_grad_dev call.  backward is cot[:, None] * grad; the gradient itself is not
+        differentiable (the library has no second derivatives of the criteria)."""
+
+        @staticmethod
+        def forward(ctx, x, acq):
+            n, d = x.shape
+            score = torch.empty((n,), dtype=torch.float64, device=x.device)
+            grad = torch.empty((d, n), dtype=torch.float64, device=x.device)
+            if n > 0:
+                xc = _colmajor(x)
+                call("obhip_set_stream", C.c_void_p(torch.cuda.current_stream().cuda_stream))
+                call("obhip_acquire_grad_dev", acq._post._h, acq.theta.data_ptr(), xc.data_ptr(), n, acq._crit,
+                     (C.c_double * 4)(*acq._params), acq._maximize, acq._chunk_rows, score.data_ptr(), grad.data_ptr(),
+                     None, None, None, None)
+            ctx.save_for_backward(grad.t())
+            return score
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, cot):
+            grad, = ctx.saved_tensors
+            return cot[:, None] * grad, None
+
+    class TorchAcquisition(torch.nn.Module):
+        """An acquisition criterion of a Posterior as a torch module: forward(x) takes the rows x (n x d, float64 on
+        the GPU) and returns their n scores in standardised units, differentiable by x once (backward =
+        grad_output[:, None] * d score / d x, from the same obhip_acquire_grad_dev call; a second derivative
+        raises), so that n starting points climb in one torch.optim loop.  criterion, best, level, kappa, xi and
+        maximize are Posterior.acquire_grad's; theta (p): the standardised coefficients of one response, uploaded
+        once.  inv(H) is formed by the first forward on the posterior and kept with it; neither x nor the gradient
+        passes through the host.  The posterior must stay open as long as the module is used."""
+
+        def __init__(self, post, theta, criterion="ei", best=None, level=None, kappa=1.96, xi=0.0, maximize=False,
+                     chunk_rows=0):
+            super().__init__()
+            from . import design
+            post._need()
+            theta = np.ascontiguousarray(theta, dtype=np.float64)
+            if theta.shape != (post.p,):
+                raise ValueError("theta must be the p standardised coefficients of one response")
+            self._params, _ = post._acquire_grad_args(criterion, best, level, kappa, xi, None)
+            self._post, self._crit, self._maximize = post, design.ACQUISITIONS[criterion], int(bool(maximize))
+            self._chunk_rows = post._chunk_rows(chunk_rows)
+            self.criterion, self.d = criterion, int(post.om.d)
+            dev = torch.device("cuda", torch.cuda.current_device())
+            self.register_buffer("theta", torch.from_numpy(theta).to(dev))
+
+        def forward(self, x):
+            if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float64:
+                raise TypeError("TorchAcquisition takes a float64 tensor on the GPU")
+            if x.dim() != 2 or x.shape[1] != self.d:
+                raise ValueError("x must be n x d")
+            if x.device != self.theta.device:
+                raise ValueError("x is on another device than the acquisition")
+            self._post._need()
+            return _AcquireScore.apply(x, self)
