@@ -351,6 +351,17 @@ int obhip_gram_dedup_info(const obhip_terms *t, uint64_t *tile_pairs, uint64_t *
  * s' * p + t' of the entry it is copied from (s' <= t', in a tile pair that is computed), -1
  * everywhere else. */
 int obhip_gram_dedup_table_dev(const obhip_terms *t, int64_t *d_src);
+/* The same one level finer: a wave of the Gram kernel computes a 64 x 64 wave tile, and a wave tile outside
+ * the diagonal tile pairs all of whose entries occur in wave tiles nearer the diagonal is dropped; the kept ones
+ * are packed into blocks anew (the diagonal tiles' wave tiles fill the gaps).  A launch takes that plan when it
+ * saves a block per row split and, by the launch's cost model, more time than its one-off analysis takes;
+ * OBHIP_GRAM_DEDUP_QUADS=1 forces it wherever a wave tile can be dropped, =0 forbids it.  wave_tiles: those of
+ * the upper triangle; dropped, blocks_per_split: of the analysis (both 0 while none has run: it runs at the first
+ * launch long enough to pay for it, or here when forced); engaged: the term set's latest Gram launch ran the plan
+ * (forced: the next one will).  While engaged, obhip_gram_dedup_table_dev reports the dropped wave tiles' sources
+ * (in kept wave tiles) instead.  Any out pointer may be NULL. */
+int obhip_gram_dedup_quads_info(const obhip_terms *t, uint64_t *wave_tiles, uint64_t *dropped, uint64_t *blocks_per_split,
+                                int *engaged);
 /* bytes of device workspace obhip_newton_solve_dev needs for p terms */
 int obhip_newton_workspace_bytes(uint64_t p, uint64_t *bytes);
 /* One Newton step from coeff = 0 of lpdfvec(loglik_std, logpr_gauss)

@@ -1,4 +1,5 @@
-// Which 128 x 128 tile pairs of G = B^T B hold nothing that is not somewhere else in G.
+// Which 128 x 128 tile pairs of G = B^T B -- and, one level finer, which 64 x 64 wave tiles -- hold nothing
+// that is not somewhere else in G.
 //
 // A column of the design matrix is scale x the product over the dimensions of one level function
 // each (level 0: no factor), so G[s][t] = sum_i scale_i^2 prod_k r_k,s_k r_k,t_k depends on the
@@ -21,6 +22,12 @@
 // A source is a segment head, heads keep their tile pairs, so sources always lie in kept pairs.
 // Diagonal tile pairs (their diagonal entries are unique, the prior and diagH live there) and
 // tile pairs that touch the padding columns of the last tile are kept whatever the analysis says.
+//
+// The same pipeline with a tile edge of 64 (`lg` = 6 in place of 7) numbers the entries by the 64 x 64 tile
+// one WAVE of the kernel computes, in the same order of priority over the 2 nb column groups: one keep byte
+// per wave tile, sources in kept wave tiles.  The wave tiles of the diagonal tile pairs and those that touch
+// padding columns are kept by rule.  gram_plan.h packs what is kept into blocks (gram_quads_pack); a launch
+// takes that plan when gram_quads_get says it pays.
 #include <string.h>  // (memset for rocprim's headers)
 
 #include <rocprim/rocprim.hpp>
@@ -35,11 +42,17 @@ namespace obhip {
 namespace {
 
 constexpr int kGT = kGramTile;
+constexpr int kLgPair = 7, kLgWave = 6;  // log2 of the tile edge of either granularity
 constexpr uint32_t kTileEntries = kGT * kGT;
 constexpr uint64_t kNoKey = ~0ull;  // padding, and the lower half of diagonal tiles
 // entries of all tile pairs above which the analysis is not run (p = 8192: 34 million; its
 // temporaries take 32 bytes an entry and the sort's own storage, budgeted as 36)
 constexpr uint64_t kMaxEntries = 48ull << 20;
+// What the analysis at wave-tile granularity and the packing of its plan cost a term set, once, in host wall
+// time: 2.0 ms measured at the headline set, half as much again for the run-to-run
+// spread of such a figure.  The packed plan is taken when it is modelled to save more than this in ONE launch.
+constexpr double kQuadsSetupMs = 3.0;
+constexpr double kBlockTileMs = 0.0146;  // a block's time per row tile (gram_cost's unit), DESIGN.md section 8
 
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {  // splitmix64's finaliser
   z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
@@ -47,23 +60,23 @@ __device__ __forceinline__ uint64_t mix64(uint64_t z) {  // splitmix64's finalis
   return z ^ (z >> 31);
 }
 
-// entry e = rank << 14 | row << 7 | column of the tile pair order[rank] = I | J << 16
-__device__ __forceinline__ bool dd_entry(uint32_t e, const uint32_t *__restrict__ order, uint32_t p, uint32_t &s,
+// entry e = rank << 2 lg | row << lg | column of the tile order[rank] = I | J << 16 (edge 1 << lg)
+__device__ __forceinline__ bool dd_entry(uint32_t e, const uint32_t *__restrict__ order, uint32_t p, int lg, uint32_t &s,
                                          uint32_t &t) {
-  const uint32_t ij = order[e >> 14], I = ij & 0xffffu, J = ij >> 16;
-  s = I * kGT + ((e >> 7) & 127u);
-  t = J * kGT + (e & 127u);
+  const uint32_t ij = order[e >> (2 * lg)], I = ij & 0xffffu, J = ij >> 16, m = (1u << lg) - 1u;
+  s = (I << lg) + ((e >> lg) & m);
+  t = (J << lg) + (e & m);
   return s < p && t < p && s <= t;
 }
 
 __global__ void __launch_bounds__(256)
 k_dd_keys(const uint16_t *__restrict__ lev, uint32_t p, uint32_t d, const uint32_t *__restrict__ order, uint32_t n,
-          int hashbits, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals) {
+          int lg, int hashbits, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals) {
   const uint32_t e = blockIdx.x * 256u + threadIdx.x;
   if (e >= n) return;
   uint32_t s, t;
   uint64_t key = kNoKey;
-  if (dd_entry(e, order, p, s, t)) {
+  if (dd_entry(e, order, p, lg, s, t)) {
     const uint16_t *ls = lev + (size_t)s * d, *lt = lev + (size_t)t * d;
     uint64_t h = 0x9e3779b97f4a7c15ull;
     for (uint32_t k = 0; k < d; ++k) {
@@ -85,19 +98,19 @@ k_dd_heads(const uint64_t *__restrict__ keys, uint32_t n, uint32_t *__restrict__
 
 __global__ void __launch_bounds__(256)
 k_dd_resolve(const uint16_t *__restrict__ lev, uint32_t p, uint32_t d, const uint32_t *__restrict__ order, uint32_t n,
-             const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals, const uint32_t *__restrict__ head,
-             uint8_t *__restrict__ keep, uint32_t *__restrict__ src) {
+             int lg, const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals,
+             const uint32_t *__restrict__ head, uint8_t *__restrict__ keep, uint32_t *__restrict__ src) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
   const uint32_t e = vals[i];
   src[e] = ~0u;
-  if (keys[i] == kNoKey) return;  // (their tile pairs are kept by rule)
+  if (keys[i] == kNoKey) return;  // (their tiles are kept by rule)
   const uint32_t h = vals[head[i]];
   bool same = false;
   uint32_t s, t, hs = 0, ht = 0;
-  if ((h >> 14) != (e >> 14)) {  // stable sort: the head's tile pair comes first in priority
-    dd_entry(e, order, p, s, t);
-    dd_entry(h, order, p, hs, ht);
+  if ((h >> (2 * lg)) != (e >> (2 * lg))) {  // stable sort: the head's tile comes first in priority
+    dd_entry(e, order, p, lg, s, t);
+    dd_entry(h, order, p, lg, hs, ht);
     const uint16_t *ls = lev + (size_t)s * d, *lt = lev + (size_t)t * d;
     const uint16_t *ms = lev + (size_t)hs * d, *mt = lev + (size_t)ht * d;
     // (a head on the diagonal of G -- a term set with a duplicate term -- is no source: a formed
@@ -111,19 +124,22 @@ k_dd_resolve(const uint16_t *__restrict__ lev, uint32_t p, uint32_t d, const uin
   if (same)
     src[e] = hs << 16 | ht;
   else
-    keep[e >> 14] = 1;
+    keep[e >> (2 * lg)] = 1;
 }
 
-// G[s][t] = G[t][s] = G[s'][t'] for every entry of the skipped tile pairs (row-major or packed sink)
+// G[s][t] = G[t][s] = G[s'][t'] for every entry of the skipped tiles of edge 1 << LG: tile pairs, or wave
+// tiles (row-major or packed sink)
+template <int LG>
 __global__ void __launch_bounds__(256)
 k_gram_fill(const uint32_t *__restrict__ pairs, const uint32_t *__restrict__ src, uint32_t p,
             double *__restrict__ G, int packed) {
+  constexpr uint32_t edge = 1u << LG, entries = edge * edge;
   const uint32_t ij = pairs[blockIdx.x], I = ij & 0xffffu, J = ij >> 16;
-  const uint32_t *tab = src + (size_t)blockIdx.x * kTileEntries;
-  for (uint32_t w = blockIdx.y * 256u + threadIdx.x; w < kTileEntries; w += gridDim.y * 256u) {
-    const uint32_t s = I * kGT + (w >> 7), t = J * kGT + (w & 127u);
+  const uint32_t *tab = src + (size_t)blockIdx.x * entries;
+  for (uint32_t w = blockIdx.y * 256u + threadIdx.x; w < entries; w += gridDim.y * 256u) {
+    const uint32_t s = I * edge + (w >> LG), t = J * edge + (w & (edge - 1u));
     const uint32_t q = tab[w], ss = q >> 16, st = q & 0xffffu;
-    if (s >= p || t >= p || ss >= p || st >= p || ss > st) continue;  // (never: skipped pairs hold no padding)
+    if (s >= p || t >= p || ss >= p || st >= p || ss > st) continue;  // (never: skipped tiles hold no padding)
     if (packed) {
       G[tri_off(s, p) + (t - s)] = G[tri_off(ss, p) + (st - ss)];
     } else {
@@ -140,20 +156,22 @@ int dedup_hashbits() {
   return std::max(1, std::min(63, v));
 }
 
-int analyse(obhip_terms &t, GramDedup &dd) {
-  const double t0 = HostTimer::now();
+std::atomic<uint64_t> g_mask_serial{0};  // exact key of the task tables built on a mask
+
+// One run of the pipeline over the tiles of edge 1 << lg that `order` lists by priority (I | J << 16).
+// keep[rank] = 1: the tile holds a canonical occurrence (or a collision); src: the sources, rank-major, in
+// the arena until it goes.  ok = false: levels beyond 16 bits (no such model), nothing analysed.
+struct DdRun {
+  bool ok = false;
+  DevBuf<char> arena;
+  uint32_t *src = nullptr;
+  std::vector<uint8_t> keep;
+};
+int run_pipeline(obhip_terms &t, int lg, const std::vector<uint32_t> &order, int hashbits, DdRun &run) {
   const uint32_t p = (uint32_t)t.p, d = (uint32_t)t.d;
-  const int nb = dd.nb, npairs = dd.npairs;
-  const uint32_t n = (uint32_t)npairs * kTileEntries;
+  const size_t ntile = order.size();
+  const uint32_t n = (uint32_t)ntile << (2 * lg);
   hipStream_t st = cur_stream();
-  // tile pairs in the order of priority
-  std::vector<uint32_t> order;
-  std::vector<int> slot_of_rank;
-  for (int dist = 0; dist < nb; ++dist)
-    for (int I = 0; I + dist < nb; ++I) {
-      order.push_back((uint32_t)I | (uint32_t)(I + dist) << 16);
-      slot_of_rank.push_back(pair_slot(nb, I, I + dist));
-    }
   std::vector<uint16_t> lev16((size_t)p * d);
   for (size_t k = 0; k < lev16.size(); ++k) {
     if (t.lev[k] > 65535u) return 0;  // (no such model; nothing skipped)
@@ -164,40 +182,60 @@ int analyse(obhip_terms &t, GramDedup &dd) {
   OB_TRY(dlev.upload(lev16.data(), lev16.size()));
   OB_TRY(dorder.upload(order.data(), order.size()));
   // the temporaries in ONE allocation (allocating and freeing eight took 12 of the analysis' 14 ms):
-  // keys and values in and out, segment heads, sources (32 bytes an entry), a byte per tile pair,
+  // keys and values in and out, segment heads, sources (32 bytes an entry), a byte per tile,
   // the sort's own storage
   size_t sort_b = 0, scan_b = 0;
   OB_HIP(rocprim::radix_sort_pairs(nullptr, sort_b, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
                                    (uint32_t *)nullptr, (size_t)n, 0u, 64u, st));
   OB_HIP(rocprim::inclusive_scan(nullptr, scan_b, (uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)n,
                                  rocprim::maximum<uint32_t>(), st));
-  const size_t keep_b = ((size_t)npairs + 255) / 256 * 256;
-  DevBuf<char> arena;
-  OB_TRY(arena.alloc((size_t)n * 32 + keep_b + std::max(sort_b, scan_b) + 256));
-  uint64_t *keys0 = (uint64_t *)arena.p, *keys1 = keys0 + n;  // (n is a multiple of 16384: all parts aligned)
+  const size_t keep_b = (ntile + 255) / 256 * 256;
+  OB_TRY(run.arena.alloc((size_t)n * 32 + keep_b + std::max(sort_b, scan_b) + 256));
+  uint64_t *keys0 = (uint64_t *)run.arena.p, *keys1 = keys0 + n;  // (n is a multiple of 4096: all parts aligned)
   uint32_t *vals0 = (uint32_t *)(keys1 + n), *vals1 = vals0 + n, *head = vals1 + n, *src = head + n;
   uint8_t *keep = (uint8_t *)(src + n);
   char *tmp = (char *)keep + keep_b;
-  OB_HIP(hipMemsetAsync(keep, 0, (size_t)npairs, st));
+  OB_HIP(hipMemsetAsync(keep, 0, ntile, st));
   const unsigned blocks = (n + 255u) / 256u;
-  hipLaunchKernelGGL(k_dd_keys, dim3(blocks), dim3(256), 0, st, dlev.p, p, d, dorder.p, n, dd.hashbits, keys0,
+  hipLaunchKernelGGL(k_dd_keys, dim3(blocks), dim3(256), 0, st, dlev.p, p, d, dorder.p, n, lg, hashbits, keys0,
                      vals0);
   OB_HIP(hipGetLastError());
   OB_HIP(rocprim::radix_sort_pairs(tmp, sort_b, keys0, keys1, vals0, vals1, (size_t)n, 0u, 64u, st));
   hipLaunchKernelGGL(k_dd_heads, dim3(blocks), dim3(256), 0, st, keys1, n, vals0);
   OB_HIP(hipGetLastError());
   OB_HIP(rocprim::inclusive_scan(tmp, scan_b, vals0, head, (size_t)n, rocprim::maximum<uint32_t>(), st));
-  hipLaunchKernelGGL(k_dd_resolve, dim3(blocks), dim3(256), 0, st, dlev.p, p, d, dorder.p, n, keys1, vals1,
+  hipLaunchKernelGGL(k_dd_resolve, dim3(blocks), dim3(256), 0, st, dlev.p, p, d, dorder.p, n, lg, keys1, vals1,
                      head, keep, src);
   OB_HIP(hipGetLastError());
-  std::vector<uint8_t> keep_h((size_t)npairs);
-  OB_TRY(d2h(keep_h.data(), keep, keep_h.size()));
+  run.keep.resize(ntile);
+  OB_TRY(d2h(run.keep.data(), keep, ntile));
+  run.src = src;
+  run.ok = true;
+  return 0;
+}
+
+int analyse(obhip_terms &t, GramDedup &dd) {
+  const double t0 = HostTimer::now();
+  const uint32_t p = (uint32_t)t.p;
+  const int nb = dd.nb, npairs = dd.npairs;
+  hipStream_t st = cur_stream();
+  // tile pairs in the order of priority
+  std::vector<uint32_t> order;
+  std::vector<int> slot_of_rank;
+  for (int dist = 0; dist < nb; ++dist)
+    for (int I = 0; I + dist < nb; ++I) {
+      order.push_back((uint32_t)I | (uint32_t)(I + dist) << 16);
+      slot_of_rank.push_back(pair_slot(nb, I, I + dist));
+    }
+  DdRun run;
+  OB_TRY(run_pipeline(t, kLgPair, order, dd.hashbits, run));
+  if (!run.ok) return 0;
   // never skipped: the diagonal, and the last tile's row and column when it holds padding
   std::vector<uint32_t> pairs;
   std::vector<int> ranks;
   for (int r = 0; r < npairs; ++r) {
     const int I = (int)(order[r] & 0xffffu), J = (int)(order[r] >> 16);
-    if (keep_h[r] || I == J || (p % kGT != 0 && J == nb - 1)) continue;
+    if (run.keep[r] || I == J || (p % kGT != 0 && J == nb - 1)) continue;
     pairs.push_back(order[r]);
     ranks.push_back(r);
     dd.skip[slot_of_rank[r]] = 1;
@@ -205,17 +243,117 @@ int analyse(obhip_terms &t, GramDedup &dd) {
   dd.nskip = (int)pairs.size();
   if (dd.nskip > 0) {
     OB_TRY(dd.pairs.upload(pairs.data(), pairs.size()));
-    OB_TRY(dd.skip_dev.upload(dd.skip.data(), dd.skip.size()));
+    // (k_gram_reduce reads a bit per quadrant: all four of a skipped pair)
+    std::vector<uint8_t> quadrants(dd.skip.size());
+    for (size_t k = 0; k < quadrants.size(); ++k) quadrants[k] = dd.skip[k] ? 0x0f : 0;
+    OB_TRY(dd.skip_dev.upload(quadrants.data(), quadrants.size()));
     OB_TRY(dd.src.alloc((size_t)dd.nskip * kTileEntries));
     for (int k = 0; k < dd.nskip; ++k)
-      OB_HIP(hipMemcpyAsync(dd.src.p + (size_t)k * kTileEntries, src + (size_t)ranks[k] * kTileEntries,
+      OB_HIP(hipMemcpyAsync(dd.src.p + (size_t)k * kTileEntries, run.src + (size_t)ranks[k] * kTileEntries,
                             kTileEntries * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
     OB_HIP(hipStreamSynchronize(st));
-    static std::atomic<uint64_t> serial{0};  // exact key of the task tables built on this mask
-    dd.sig = ++serial;
+    dd.sig = ++g_mask_serial;
   }
   dd.analysis_ms = HostTimer::now() - t0;
   return 0;
+}
+
+// the same at wave-tile granularity: q.keep, the dropped wave tiles with their sources, the quadrant bits of
+// the reduction, and the blocks per split the packed plan needs
+int analyse_quads(obhip_terms &t, GramDedup::Quads &q, int nb) {
+  const double t0 = HostTimer::now();
+  const uint32_t p = (uint32_t)t.p;
+  const int ng = 2 * nb;
+  constexpr uint32_t kWaveEntries = 64 * 64;
+  hipStream_t st = cur_stream();
+  std::vector<uint32_t> order;
+  for (int dist = 0; dist < ng; ++dist)
+    for (int a = 0; a + dist < ng; ++a) order.push_back((uint32_t)a | (uint32_t)(a + dist) << 16);
+  DdRun run;
+  OB_TRY(run_pipeline(t, kLgWave, order, q.hashbits, run));
+  if (!run.ok) return 0;
+  // never dropped: the wave tiles of the diagonal tile pairs, and those that reach into the padding columns
+  std::vector<uint32_t> tiles, ranks;
+  for (size_t r = 0; r < order.size(); ++r) {
+    const int a = (int)(order[r] & 0xffffu), b = (int)(order[r] >> 16);
+    if (run.keep[r] || a / 2 == b / 2 || (uint32_t)(b + 1) * 64u > p) continue;
+    tiles.push_back(order[r]);
+    ranks.push_back((uint32_t)r);
+    q.keep[(size_t)pair_slot(ng, a, b)] = 0;
+  }
+  q.ndrop = (int)tiles.size();
+  if (q.ndrop > 0) {
+    std::vector<uint8_t> quadrants(gram_npairs(nb), 0);
+    for (uint32_t ab : tiles) {
+      const int a = (int)(ab & 0xffffu), b = (int)(ab >> 16);
+      quadrants[(size_t)pair_slot(nb, a / 2, b / 2)] |= (uint8_t)(1u << (2 * (a & 1) + (b & 1)));
+    }
+    DevBuf<uint32_t> dranks;
+    OB_TRY(q.tiles.upload(tiles.data(), tiles.size()));
+    OB_TRY(dranks.upload(ranks.data(), ranks.size()));
+    OB_TRY(q.qskip_dev.upload(quadrants.data(), quadrants.size()));
+    OB_TRY(q.src.alloc((size_t)q.ndrop * kWaveEntries));
+    uint32_t *dst = q.src.p;
+    const uint32_t *from = run.src, *rk = dranks.p;
+    OB_TRY(vmap((uint64_t)q.ndrop * kWaveEntries, [=] __device__(uint64_t w) {
+      dst[w] = from[(uint64_t)rk[w / kWaveEntries] * kWaveEntries + w % kWaveEntries];
+    }));
+    OB_HIP(hipStreamSynchronize(st));
+    q.sig = ++g_mask_serial;
+    std::vector<QuadBlock> blocks;
+    gram_quads_pack(nb, q.keep.data(), blocks);
+    q.blocks = (int)blocks.size();
+  }
+  q.setup_ms = HostTimer::now() - t0;
+  return 0;
+}
+
+bool dedup_off() {
+  const char *e = getenv("OBHIP_GRAM_DEDUP");
+  return e && atoi(e) == 0;
+}
+// OBHIP_GRAM_DEDUP_QUADS: 1 forces the plan at wave-tile granularity, 0 forbids it, unset (-1) lets the model decide
+int quads_mode() {
+  const char *e = getenv("OBHIP_GRAM_DEDUP_QUADS");
+  return e ? (atoi(e) != 0 ? 1 : 0) : -1;
+}
+
+// t's analysis at wave-tile granularity, run on first use and kept with the terms (ndrop = 0: nothing to
+// drop, fewer than two tiles, or too many entries)
+int quads_analysis(obhip_terms &t, GramDedup::Quads **out) {
+  GramDedup::Quads &q = t.dedup.quads;
+  *out = &q;
+  const int hashbits = dedup_hashbits();
+  if (q.tried && q.hashbits == hashbits) return 0;
+  const int nb = (int)((t.p + kGT - 1) / kGT);
+  q.ndrop = q.blocks = q.blocks_pairs = 0;
+  q.sig = 0;
+  q.setup_ms = 0.0;
+  q.engaged = false;
+  q.key = GramKey();
+  q.tried = true;
+  q.hashbits = hashbits;
+  q.keep.assign(gram_npairs(2 * nb), 1);
+  const uint64_t n = gram_npairs(2 * nb) * 64 * 64;
+  size_t free_b = 0, total_b = 0;
+  const bool fits = n <= kMaxEntries && hipMemGetInfo(&free_b, &total_b) == hipSuccess && n * 36 <= free_b / 8;
+  if (nb >= 2 && fits) {
+    const int rc = analyse_quads(t, q, nb);
+    if (rc) {
+      q.ndrop = 0;
+      return rc;
+    }
+  }
+  return 0;
+}
+
+template <int LG>
+int dedup_table(const uint32_t *tiles, const uint32_t *src, uint64_t ntile, uint64_t p, int64_t *d_src) {
+  return vmap(ntile << (2 * LG), [=] __device__(uint64_t w) {
+    const uint32_t ij = tiles[w >> (2 * LG)], q = src[w], m = (1u << LG) - 1u;
+    const uint64_t s = ((uint64_t)(ij & 0xffffu) << LG) + ((w >> LG) & m), tt = ((uint64_t)(ij >> 16) << LG) + (w & m);
+    if (s < p && tt < p && q != ~0u) d_src[s * p + tt] = (int64_t)((uint64_t)(q >> 16) * p + (q & 0xffffu));
+  });
 }
 
 }  // namespace
@@ -224,8 +362,7 @@ int analyse(obhip_terms &t, GramDedup &dd) {
 // nothing is skipped: OBHIP_GRAM_DEDUP=0, too few or too many tile pairs, or no redundant pair.
 int gram_dedup_get(obhip_terms &t, const GramDedup **out) {
   *out = nullptr;
-  if (const char *e = getenv("OBHIP_GRAM_DEDUP"))
-    if (atoi(e) == 0) return 0;
+  if (dedup_off()) return 0;
   GramDedup &dd = t.dedup;
   const int hashbits = dedup_hashbits();
   if (!dd.tried || dd.hashbits != hashbits) {
@@ -255,19 +392,62 @@ int gram_dedup_get(obhip_terms &t, const GramDedup **out) {
   return 0;
 }
 
-// the fill table as a p x p array of linear source indices (-1: not an entry of a skipped tile pair)
-int dedup_table(const GramDedup &dd, uint64_t p, int64_t *d_src) {
-  const uint32_t *pairs = dd.pairs.p, *src = dd.src.p;
-  return vmap((uint64_t)dd.nskip * kTileEntries, [=] __device__(uint64_t w) {
-    const uint32_t ij = pairs[w / kTileEntries], q = src[w];
-    const uint64_t s = (uint64_t)(ij & 0xffffu) * kGT + ((w >> 7) & 127u), tt = (uint64_t)(ij >> 16) * kGT + (w & 127u);
-    if (s < p && tt < p && q != ~0u) d_src[s * p + tt] = (int64_t)((uint64_t)(q >> 16) * p + (q & 0xffffu));
-  });
+// Whether the launch of `shape` at `plan` (the split, and the dealing the whole-pair plan takes with its mask
+// `skip`, may be null) runs the packed plan at wave-tile granularity instead.  Forced: whenever a wave tile can
+// be dropped.  Otherwise only when the plan saves a block per split and, by gram_cost at kBlockTileMs a row tile,
+// more time in this one launch than its set-up cost the term set; a launch whose whole modelled time is below
+// that is not even analysed.  The decision is kept with the analysis until shape, split or mask change.
+int gram_quads_get(obhip_terms &t, const GramShape &shape, const GramPlan &plan, const uint8_t *skip, uint64_t skip_sig,
+                   const GramDedup::Quads **out) {
+  *out = nullptr;
+  GramDedup::Quads &q0 = t.dedup.quads;
+  const int mode = dedup_off() ? 0 : quads_mode();
+  if (mode == 0) {
+    q0.engaged = false;
+    q0.key = GramKey();
+    return 0;
+  }
+  const GramKey key = {shape, plan.nsplit, skip_sig, 2 * mode + (plan.continuous ? 1 : 0)};
+  if (q0.key == key) {
+    if (q0.engaged) *out = &q0;
+    return 0;
+  }
+  std::vector<uint64_t> tab;
+  build_task_order(shape.nb, (int)plan.nsplit, shape.diag4, plan.continuous, skip, tab);
+  const double cost_pairs = gram_table_cost(shape, plan.nsplit, plan.continuous, tab);
+  if (mode < 0 && cost_pairs * kBlockTileMs <= kQuadsSetupMs) {
+    q0.engaged = false;
+    q0.key = key;
+    return 0;
+  }
+  GramDedup::Quads *q = nullptr;
+  OB_TRY(quads_analysis(t, &q));
+  q->key = key;
+  q->engaged = false;
+  if (q->ndrop == 0) return 0;
+  q->blocks_pairs = (int)((tab.size() - (size_t)std::count(tab.begin(), tab.end(), kAtbNoTask)) / plan.nsplit);
+  double cost = 0.0;
+  q->continuous = gram_quads_choose_dealing(shape, plan.nsplit, q->keep.data(), &cost);
+  q->engaged = mode == 1 || (q->blocks + 1 <= q->blocks_pairs && (cost_pairs - cost) * kBlockTileMs > kQuadsSetupMs);
+  if (getenv("OBHIP_GRAM_DBG") && atoi(getenv("OBHIP_GRAM_DBG")) != 0)
+    fprintf(stderr, "[gram dbg] wave-tile plan: %d dropped, %d blocks per split (whole pairs %d), gram_cost %.1f -> %.1f, "
+                    "set-up %.2f ms, %s\n", q->ndrop, q->blocks, q->blocks_pairs, cost_pairs, cost, q->setup_ms,
+            q->engaged ? "engaged" : "not engaged");
+  if (q->engaged) *out = q;
+  return 0;
 }
 
 int launch_gram_fill(const GramDedup &dd, int p, const GramSink &sink) {
   ProfScope ps("gram_fill");
-  hipLaunchKernelGGL(k_gram_fill, dim3((unsigned)dd.nskip, 8), dim3(256), 0, cur_stream(), dd.pairs.p, dd.src.p,
+  hipLaunchKernelGGL(k_gram_fill<kLgPair>, dim3((unsigned)dd.nskip, 8), dim3(256), 0, cur_stream(), dd.pairs.p, dd.src.p,
+                     (uint32_t)p, sink.out, sink.packed ? 1 : 0);
+  OB_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_gram_fill_quads(const GramDedup::Quads &q, int p, const GramSink &sink) {
+  ProfScope ps("gram_fill");
+  hipLaunchKernelGGL(k_gram_fill<kLgWave>, dim3((unsigned)q.ndrop, 2), dim3(256), 0, cur_stream(), q.tiles.p, q.src.p,
                      (uint32_t)p, sink.out, sink.packed ? 1 : 0);
   OB_HIP(hipGetLastError());
   return 0;
@@ -292,16 +472,39 @@ int obhip_gram_dedup_info(const obhip_terms *tc, uint64_t *tile_pairs, uint64_t 
   return 0;
 }
 
+int obhip_gram_dedup_quads_info(const obhip_terms *tc, uint64_t *wave_tiles, uint64_t *dropped, uint64_t *blocks_per_split,
+                                int *engaged) {
+  if (!tc) return fail(OBHIP_ERR_INVALID, "gram_dedup_quads_info: null argument");
+  OB_TRY(require_device());
+  obhip_terms &t = *const_cast<obhip_terms *>(tc);
+  const uint64_t ng = 2 * ((t.p + kGT - 1) / kGT);
+  const int mode = dedup_off() ? 0 : quads_mode();
+  GramDedup::Quads *q = &t.dedup.quads;
+  if (mode == 1) OB_TRY(quads_analysis(t, &q));
+  const bool known = mode != 0 && q->tried && q->hashbits == dedup_hashbits();
+  if (wave_tiles) *wave_tiles = ng * (ng + 1) / 2;
+  if (dropped) *dropped = known ? (uint64_t)q->ndrop : 0;
+  if (blocks_per_split) *blocks_per_split = known ? (uint64_t)q->blocks : 0;
+  if (engaged) *engaged = known && q->ndrop > 0 && (mode == 1 || q->engaged) ? 1 : 0;
+  return 0;
+}
+
 int obhip_gram_dedup_table_dev(const obhip_terms *tc, int64_t *d_src) {
   if (!tc || !d_src) return fail(OBHIP_ERR_INVALID, "gram_dedup_table_dev: null argument");
   OB_TRY(require_device());
   obhip_terms &t = *const_cast<obhip_terms *>(tc);
-  const GramDedup *dd = nullptr;
-  OB_TRY(gram_dedup_get(t, &dd));
   const uint64_t p = t.p;
   OB_HIP(hipMemsetAsync(d_src, 0xff, p * p * sizeof(int64_t), cur_stream()));  // -1
+  int engaged = 0;
+  OB_TRY(obhip_gram_dedup_quads_info(tc, nullptr, nullptr, nullptr, &engaged));
+  if (engaged) {
+    const GramDedup::Quads &q = t.dedup.quads;
+    return dedup_table<kLgWave>(q.tiles.p, q.src.p, (uint64_t)q.ndrop, p, d_src);
+  }
+  const GramDedup *dd = nullptr;
+  OB_TRY(gram_dedup_get(t, &dd));
   if (!dd) return 0;
-  return dedup_table(*dd, p, d_src);
+  return dedup_table<kLgPair>(dd->pairs.p, dd->src.p, (uint64_t)dd->nskip, p, d_src);
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 // (tests/gram_plan_check.cpp).
 #pragma once
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <tuple>
 #include <vector>
@@ -281,6 +282,215 @@ inline bool gram_choose_dealing(const GramShape &s, uint64_t nsplit, const uint8
     return gram_cost(s, nsplit, continuous, tab.size() / kXcd /* the longest XCD sequence */, blocks);
   };
   return price(true) < price(false) - 1e-9;
+}
+
+// ---- the plan at wave-tile granularity ----------------------------------------------------------------
+// A block's four waves each compute one 64 x 64 wave tile of G from the 256 staged columns [panel I | panel J]:
+// any of the four of (I, J), the three of (I, I) and the three of (J, J).  With a keep byte per wave tile of
+// the upper triangle of ng = 2 nb column groups (slot pair_slot(ng, a, b), a <= b; 0 = every entry repeats in a
+// kept wave tile, gram_dedup.hip) the kept off-diagonal wave tiles stay in the block of their tile pair, the
+// diagonal tiles' wave tiles (always kept) fill the waves a partial pair leaves free -- as many as a maximum
+// matching places -- and what is left of the diagonal goes to neighbour blocks (i, i + 1), the way types 1-3
+// of atb_wave_code pack it.  A wave without a wave tile idles (kWaveIdle): it stages, waits at the barriers
+// and stores nothing.  Every kept wave tile is computed exactly once, no dropped one at all.
+constexpr uint8_t kWaveIdle = 0xc0;  // the unused value of the output-tile bits
+// the byte (atb_wave_code's format) of wave tile (a <= b) in a block that stages panels (I, J)
+inline uint8_t wave_byte(int I, int J, int a, int b) {
+  const int ta = a / 2, ra = a & 1, cb = b & 1;
+  uint32_t A, B, sel;
+  if (ta == b / 2) {  // of diagonal tile ta: panel I's groups are 0, 1 and panel J's 2, 3
+    sel = ta == I ? 0u : 1u;
+    A = 2 * sel + (uint32_t)ra;
+    B = 2 * sel + (uint32_t)cb;
+  } else {
+    sel = 2;
+    A = (uint32_t)ra;
+    B = 2u + (uint32_t)cb;
+  }
+  (void)J;
+  return (uint8_t)(A | B << 2 | (uint32_t)ra << 4 | (uint32_t)cb << 5 | sel << 6);
+}
+struct QuadBlock {
+  int I, J;
+  uint8_t w[4];
+  uint32_t bytes() const { return (uint32_t)w[0] | (uint32_t)w[1] << 8 | (uint32_t)w[2] << 16 | (uint32_t)w[3] << 24; }
+};
+// The blocks of one row split: those of the off-diagonal tile pairs that keep a wave tile, in row-major order
+// of the pairs, then the neighbour blocks of the diagonal's rest.
+inline void gram_quads_pack(int nb, const uint8_t *keep, std::vector<QuadBlock> &blocks) {
+  const int ng = 2 * nb;
+  blocks.clear();
+  struct Hole { int block, wave; };
+  std::vector<Hole> holes;
+  for (int I = 0; I < nb; ++I)
+    for (int J = I + 1; J < nb; ++J) {
+      QuadBlock q = {I, J, {kWaveIdle, kWaveIdle, kWaveIdle, kWaveIdle}};
+      int k = 0;
+      for (int r = 0; r < 2; ++r)
+        for (int c = 0; c < 2; ++c)
+          if (keep[pair_slot(ng, 2 * I + r, 2 * J + c)]) q.w[k++] = wave_byte(I, J, 2 * I + r, 2 * J + c);
+      if (k == 0) continue;
+      for (; k < 4; ++k) holes.push_back({(int)blocks.size(), k});
+      blocks.push_back(q);
+    }
+  // diagonal wave tile u = 3 tile + {0: (lo, lo), 1: (lo, hi), 2: (hi, hi)}; a hole of block (I, J) takes one
+  // of I's or J's: maximum bipartite matching by augmenting paths (holes and units by the hundred)
+  const int nunits = 3 * nb;
+  std::vector<int> hole_of(nunits, -1);
+  std::vector<char> seen;
+  auto try_hole = [&](auto &&self, int h) -> bool {
+    for (int side = 0; side < 2; ++side) {
+      const int tile = side ? blocks[holes[h].block].J : blocks[holes[h].block].I;
+      for (int u = 3 * tile; u < 3 * tile + 3; ++u) {
+        if (seen[u]) continue;
+        seen[u] = 1;
+        if (hole_of[u] < 0 || self(self, hole_of[u])) {
+          hole_of[u] = h;
+          return true;
+        }
+      }
+    }
+    return false;
+  };
+  for (int h = 0; h < (int)holes.size(); ++h) {
+    seen.assign(nunits, 0);
+    try_hole(try_hole, h);
+  }
+  auto unit_byte = [&](int I, int J, int u) {
+    const int tile = u / 3, k = u % 3;
+    return wave_byte(I, J, 2 * tile + (k == 2), 2 * tile + (k >= 1));
+  };
+  std::vector<std::vector<int>> rest(nb);
+  for (int u = 0; u < nunits; ++u)
+    if (hole_of[u] >= 0) {
+      QuadBlock &q = blocks[holes[hole_of[u]].block];
+      q.w[holes[hole_of[u]].wave] = unit_byte(q.I, q.J, u);
+    } else {
+      rest[u / 3].push_back(u);
+    }
+  // the rest, left to right: all of tile i's and as many of tile i + 1's as still fit
+  for (int i = 0; i < nb; ++i) {
+    if (rest[i].empty()) continue;
+    QuadBlock q = {i + 1 < nb ? i : std::max(i - 1, 0), i + 1 < nb ? i + 1 : i, {kWaveIdle, kWaveIdle, kWaveIdle, kWaveIdle}};
+    int k = 0;
+    for (int u : rest[i]) q.w[k++] = unit_byte(q.I, q.J, u);
+    rest[i].clear();
+    if (i + 1 < nb)
+      while (k < 4 && !rest[i + 1].empty()) {
+        q.w[k++] = unit_byte(q.I, q.J, rest[i + 1].front());
+        rest[i + 1].erase(rest[i + 1].begin());
+      }
+    blocks.push_back(q);
+  }
+}
+// The task table of the packed blocks and, entry for entry, their four wave bytes (whatever at a padding task):
+// build_task_order's dealings on the packed list -- units are the 8 x 8 squares by a block's (I, J); an
+// off-diagonal square that lost blocks is topped up to 64 from the diagonal squares of its own bands first,
+// what is left of those goes out in runs of 64; or the list in unit order cut into 8 equal runs.
+inline void gram_quads_table(int nb, int nsplit, bool continuous, const uint8_t *keep, std::vector<uint64_t> &tab,
+                             std::vector<uint32_t> &wbytes) {
+  std::vector<QuadBlock> blocks;
+  gram_quads_pack(nb, keep, blocks);
+  const int nsq = (nb + kSq - 1) / kSq;
+  // an entry while dealing: block index | split << 32
+  std::vector<std::vector<uint64_t>> square((size_t)nsq * nsq);
+  for (size_t m = 0; m < blocks.size(); ++m)
+  {
+    // (a neighbour block (i, i + 1) of the diagonal's rest belongs to the diagonal square of i, also where i + 1 is
+    // the first tile of the next square: an off-diagonal square of 65 blocks would shift every later run of its
+    // XCD by one slot, and the sharers of a panel would no longer start together)
+    const QuadBlock &q = blocks[m];
+    const bool rest = (q.w[0] >> 6) != 2;  // no wave tile of (I, J) itself: the off-diagonal blocks put theirs first
+    square[(size_t)(q.I / kSq) * nsq + (rest ? q.I : q.J) / kSq].push_back(m);
+  }
+  XcdDeal xcd;
+  constexpr size_t kFull = (size_t)kSq * kSq;
+  std::vector<std::vector<uint64_t>> runs;
+  std::vector<uint64_t> all;
+  for (int y = 0; y < nsplit; ++y) {
+    auto of_split = [&](const std::vector<uint64_t> &sq) {
+      std::vector<uint64_t> r(sq);
+      for (uint64_t &e : r) e |= (uint64_t)y << 32;
+      return r;
+    };
+    if (continuous) {
+      for (int bi = 0; bi < nsq; ++bi)
+        for (int bj = bi; bj < nsq; ++bj) {
+          const std::vector<uint64_t> r = of_split(square[(size_t)bi * nsq + bj]);
+          all.insert(all.end(), r.begin(), r.end());
+        }
+      continue;
+    }
+    std::vector<std::vector<uint64_t>> diag((size_t)nsq);
+    for (int sq = 0; sq < nsq; ++sq) diag[(size_t)sq] = of_split(square[(size_t)sq * nsq + sq]);
+    for (int bi = 0; bi < nsq; ++bi)
+      for (int bj = bi + 1; bj < nsq; ++bj) {
+        std::vector<uint64_t> r = of_split(square[(size_t)bi * nsq + bj]);
+        if (r.empty()) continue;
+        for (int pass = 0; pass < 2 && r.size() < kFull; ++pass)
+          for (int sq = 0; sq < nsq && r.size() < kFull; ++sq) {
+            if ((pass == 0) != (sq == bi || sq == bj)) continue;
+            std::vector<uint64_t> &pool = diag[(size_t)sq];
+            while (!pool.empty() && r.size() < kFull) {
+              r.push_back(pool.back());
+              pool.pop_back();
+            }
+          }
+        runs.push_back(std::move(r));
+      }
+    // what is left of the diagonal squares in runs of 64, the fullest squares first: two that lost nothing to
+    // the top-up are 60 blocks on 16 panels, where the squares in their order put parts of all four -- 28
+    // panels, whose window of 8 chunks no longer fits the L2 -- into one run
+    std::stable_sort(diag.begin(), diag.end(),
+                     [](const std::vector<uint64_t> &a, const std::vector<uint64_t> &b) { return a.size() > b.size(); });
+    // ... and last the smallest square that still holds the whole short run at the end: the short runs of four
+    // splits share a round at the tail of an XCD's sequence, 8 panels each instead of parts of two squares
+    size_t total = 0;
+    for (const auto &pool : diag) total += pool.size();
+    for (size_t m = diag.size(); m-- > 0;)
+      if (total % kFull != 0 && diag[m].size() >= total % kFull) {
+        std::rotate(diag.begin() + (std::ptrdiff_t)m, diag.begin() + (std::ptrdiff_t)m + 1, diag.end());
+        break;
+      }
+    std::vector<uint64_t> rest;
+    for (auto &pool : diag) rest.insert(rest.end(), pool.begin(), pool.end());
+    for (size_t m = 0; m < rest.size(); m += kFull)
+      runs.emplace_back(rest.begin() + m, rest.begin() + std::min(rest.size(), m + kFull));
+  }
+  if (continuous) {
+    const uint64_t run = (all.size() + kXcd - 1) / kXcd;
+    for (size_t m = 0; m < all.size(); ++m) xcd.seq[m / run].push_back(all[m]);
+  } else {
+    std::stable_sort(runs.begin(), runs.end(),
+                     [](const std::vector<uint64_t> &a, const std::vector<uint64_t> &b) { return a.size() > b.size(); });
+    for (const auto &r : runs) xcd.deal(r);
+  }
+  tab = xcd.table();
+  wbytes.assign(tab.size(), 0);
+  for (size_t m = 0; m < tab.size(); ++m) {
+    if (tab[m] == kAtbNoTask) continue;
+    const QuadBlock &q = blocks[(size_t)(tab[m] & 0xffffffffu)];
+    wbytes[m] = q.bytes();
+    tab[m] = atb_task((uint64_t)q.I, (uint64_t)q.J, tab[m] >> 32);
+  }
+}
+// what gram_cost says of a task table
+inline double gram_table_cost(const GramShape &s, uint64_t nsplit, bool continuous, const std::vector<uint64_t> &tab) {
+  const uint64_t blocks = tab.size() - (uint64_t)std::count(tab.begin(), tab.end(), kAtbNoTask);
+  return gram_cost(s, nsplit, continuous, tab.size() / kXcd /* the longest XCD sequence */, blocks);
+}
+// the dealing of the packed blocks at a split, priced like gram_choose_dealing; *cost: that of the choice
+inline bool gram_quads_choose_dealing(const GramShape &s, uint64_t nsplit, const uint8_t *keep, double *cost = nullptr) {
+  std::vector<uint64_t> tab;
+  std::vector<uint32_t> wb;
+  double c[2];
+  for (int continuous = 0; continuous < 2; ++continuous) {
+    gram_quads_table(s.nb, (int)nsplit, continuous != 0, keep, tab, wb);
+    c[continuous] = gram_table_cost(s, nsplit, continuous != 0, tab);
+  }
+  const bool pick = c[1] < c[0] - 1e-9;
+  if (cost) *cost = c[pick ? 1 : 0];
+  return pick;
 }
 
 // ---- row chunks ---------------------------------------------------------------------------------------

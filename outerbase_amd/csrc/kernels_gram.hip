@@ -41,7 +41,10 @@ k_gram_reduce(const double *__restrict__ part, int npairs, int nsplit, int nb, i
               double *__restrict__ G, int acc, int packed, int form, double e2,
               const double *__restrict__ prec, double *__restrict__ diagH, const uint8_t *__restrict__ skip) {
   __shared__ double S[kRedRows * 65];  // the slice, so that the mirror goes out in row segments too
-  if (skip && skip[blockIdx.x]) return;  // no task wrote its partials: k_gram_fill copies the entries
+  // skip: per tile pair one bit per quadrant (2 row + column) that no wave wrote partials of: k_gram_fill
+  // copies its entries (a skipped tile pair has all four set)
+  const int qd = (int)blockIdx.y / (64 / kRedRows), r0 = ((int)blockIdx.y % (64 / kRedRows)) * kRedRows;
+  if (skip && (skip[blockIdx.x] >> qd & 1)) return;
   int I = 0, rem = blockIdx.x;
   while (rem >= nb - I) {
     rem -= nb - I;
@@ -49,7 +52,6 @@ k_gram_reduce(const double *__restrict__ part, int npairs, int nsplit, int nb, i
   }
   const int J = I + rem;
   const int c = threadIdx.x & 63, r4 = threadIdx.x >> 6;
-  const int qd = (int)blockIdx.y / (64 / kRedRows), r0 = ((int)blockIdx.y % (64 / kRedRows)) * kRedRows;
   const int qr = qd >> 1, qc = qd & 1;
   if (I == J && qr > qc) return;  // diagonal tiles: the lower-left quadrant is the mirror
   const bool dq = I == J && qr == qc;  // quadrant on the diagonal of G

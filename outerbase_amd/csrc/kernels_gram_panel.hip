@@ -182,6 +182,9 @@ __device__ __forceinline__ void lds_rd_h1(const uint32_t (&baddr)[4], double (&b
 //   (i, i + 1) takes i's three and (lo, lo) of i + 1; (i + 1, i + 2) the other two of i + 1 and
 //   two of i + 2; (i + 2, i + 3) the last of i + 2 and i + 3's three.  One block in four of the
 //   diagonal's saved: 1.5 % of all blocks at p = 4096.
+// The plan at wave-tile granularity (gram_plan.h: gram_quads_table) hands the kernel the four bytes of every
+// block in an array beside the task table instead: any of the ten wave tiles of (I, J), (I, I), (J, J) per wave,
+// or output tile 3 = nothing (kWaveIdle).
 __device__ __forceinline__ uint32_t atb_wave_code(uint32_t type, int wave) {
   constexpr uint32_t W = 0x80u;  // output tile (I, J)
   const uint32_t t0 = (W | 0x08u) | (W | 0x2cu) << 8 | (W | 0x19u) << 16 | (W | 0x3du) << 24;
@@ -199,8 +202,9 @@ __global__ void __launch_bounds__(256, 2)
 k_atb_dma2(const double *__restrict__ A, uint64_t ldA, const double *__restrict__ Bm, uint64_t ldB,
            int nb, int npairs, uint64_t ntiles, uint64_t split_base /* Gram: tiles per row split ... */,
            int tri /* Gram: ... the first `tri` splits take one more tile */,
-           const uint64_t *__restrict__ tasks, double *__restrict__ part, uint64_t ldo,
-           unsigned long long *dbgout) {
+           const uint64_t *__restrict__ tasks, const uint32_t *__restrict__ wbytes /* Gram: the four wave bytes
+           of every task (gram_quads_table), or null: the task's type decides */,
+           double *__restrict__ part, uint64_t ldo, unsigned long long *dbgout) {
   extern __shared__ double T[];  // [2][16][272]
   constexpr int tszb = kCR * kTP * 8;  // bytes per buffer
   unsigned long long st0 = 0, sr0 = 0;
@@ -217,7 +221,8 @@ k_atb_dma2(const double *__restrict__ A, uint64_t ldA, const double *__restrict_
   const uint64_t task = tasks[blockIdx.x];
   if (task == kAtbNoTask) return;  // padding of the shorter per-XCD sequences
   const int I = (int)(task & 0xffffff), J = (int)((task >> 24) & 0xffffff), ysplit = (int)((task >> 48) & 0x3fff);
-  const uint32_t wcode = atb_wave_code(MODE == kAtbGram ? (uint32_t)(task >> 62) : 0u, wave);
+  uint32_t wcode = atb_wave_code(MODE == kAtbGram ? (uint32_t)(task >> 62) : 0u, wave);
+  if (MODE == kAtbGram && wbytes) wcode = (wbytes[blockIdx.x] >> (8 * wave)) & 0xffu;
 
   uint64_t t0, t1;  // range of 64-row tiles of k
   if constexpr (MODE == kAtbGram) {
@@ -326,7 +331,9 @@ k_atb_dma2(const double *__restrict__ A, uint64_t ldA, const double *__restrict_
 
   if constexpr (MODE == kAtbGram) {
     // output tile of this wave: (I, J), or the diagonal tile of I or of J
+    // (3: a wave the packed plan gave nothing to; it has staged and waited with the others and stores nothing)
     const int sel = (int)(wcode >> 6);
+    if (sel == 3) return;
     const int oi = sel == 1 ? J : I, oj = sel == 0 ? I : J;
     const int slot = oi * nb - oi * (oi - 1) / 2 + (oj - oi);  // row-major index in the upper triangle
     double *out = part + ((uint64_t)ysplit * npairs + slot) * (kGT * kGT);
@@ -465,12 +472,12 @@ int materialize_any(const obhip_basis &b, obhip_terms &t, double *d_B, GramFuse 
 // one launch of k_atb_dma2<MODE, DBG, FIXED>, a block per entry of the task table
 template <int MODE, bool DBG, bool FIXED = false>
 int run_atb(const double *A, uint64_t ldA, const double *Bm, uint64_t ldB, int nb, int npairs, uint64_t ntiles,
-            uint64_t split_base, int tri, const DevBuf<uint64_t> &tasks, double *out, uint64_t ldo,
-            unsigned long long *dbgout) {
+            uint64_t split_base, int tri, const DevBuf<uint64_t> &tasks, const uint32_t *wbytes, double *out,
+            uint64_t ldo, unsigned long long *dbgout) {
   const size_t lds = (size_t)2 * kCR * kTP * sizeof(double);
   OB_TRY(ensure_dyn_lds((const void *)k_atb_dma2<MODE, DBG, FIXED>, lds));
   hipLaunchKernelGGL((k_atb_dma2<MODE, DBG, FIXED>), dim3((unsigned)tasks.n), dim3(256), lds, cur_stream(), A, ldA,
-                     Bm, ldB, nb, npairs, ntiles, split_base, tri, tasks.p, out, ldo, dbgout);
+                     Bm, ldB, nb, npairs, ntiles, split_base, tri, tasks.p, wbytes, out, ldo, dbgout);
   OB_HIP(hipGetLastError());
   return 0;
 }
@@ -538,14 +545,25 @@ int gram_of_staged(obhip_basis &b, const double *d_B, uint64_t ntiles, obhip_ter
     plan.continuous = d.continuous;
   }
   if (sw.continuous) plan.continuous = atoi(sw.continuous) != 0;
+  // the plan at wave-tile granularity in place of all that, when it pays or is forced (gram_quads_get): the same
+  // split, its own dealing, the four wave bytes of every block beside the task table
+  const GramDedup::Quads *quads = nullptr;
+  OB_TRY(gram_quads_get(t, shape, plan, skip, dd ? dd->sig : 0, &quads));
+  if (quads) plan.continuous = sw.continuous ? plan.continuous : quads->continuous;
   // the table: built and uploaded when anything it depends on has changed
   obhip_basis::GramTable &tb = b.gram_table;
-  const GramKey tkey = {{nb, 0, 0, sw.diag4}, plan.nsplit, dd ? dd->sig : 0, plan.continuous ? 1 : 0};
+  const GramKey tkey = {{nb, 0, 0, sw.diag4}, plan.nsplit, quads ? quads->sig : dd ? dd->sig : 0, plan.continuous ? 1 : 0};
   if (!(tb.key == tkey)) {
     std::vector<uint64_t> tab;
-    build_task_order(nb, (int)plan.nsplit, sw.diag4, plan.continuous, skip, tab);
+    std::vector<uint32_t> wbytes;
+    if (quads)
+      gram_quads_table(nb, (int)plan.nsplit, plan.continuous, quads->keep.data(), tab, wbytes);
+    else
+      build_task_order(nb, (int)plan.nsplit, sw.diag4, plan.continuous, skip, tab);
     tb.key = GramKey();  // (not the old table's key should the upload fail)
     OB_TRY(tb.tab.upload(tab.data(), tab.size()));
+    if (quads) OB_TRY(tb.wbytes.upload(wbytes.data(), wbytes.size()));
+    tb.packed = quads != nullptr;
     tb.key = tkey;
   }
   const size_t part_n = (size_t)plan.nsplit * npairs * kGT * kGT;
@@ -555,14 +573,16 @@ int gram_of_staged(obhip_basis &b, const double *d_B, uint64_t ntiles, obhip_ter
   OB_TRY(pick_bool(sw.dbg, [&](auto DBG) {
     ProfScope ps("gram");
     return run_atb<kAtbGram, DBG()>(d_B, t.p_pad, d_B, t.p_pad, nb, npairs, ntiles, ntiles / plan.nsplit,
-                                    (int)(ntiles % plan.nsplit), tb.tab, part, 0, dbgout);
+                                    (int)(ntiles % plan.nsplit), tb.tab, tb.packed ? tb.wbytes.p : nullptr, part, 0,
+                                    dbgout);
   }));
   if (dbgout) OB_TRY(print_gram_dbg(dbgout));
   OB_TRY(launch_gram_reduce(part, npairs, (int)plan.nsplit, nb, (int)t.p, sink, accumulate, last,
-                            dd ? dd->skip_dev.p : nullptr));
-  // the skipped pairs' entries from their sources in the sink: after every reduction (of a row
-  // chunk too: the sources then hold the sums so far, the copies likewise), formed values when the
+                            quads ? quads->qskip_dev.p : dd ? dd->skip_dev.p : nullptr));
+  // the skipped pairs' (dropped wave tiles') entries from their sources in the sink: after every reduction (of
+  // a row chunk too: the sources then hold the sums so far, the copies likewise), formed values when the
   // reduction formed the Hessian
+  if (quads) return launch_gram_fill_quads(*quads, (int)t.p, sink);
   return dd ? launch_gram_fill(*dd, (int)t.p, sink) : 0;
 }
 
@@ -690,7 +710,7 @@ int launch_atb(int mode, const double *A, uint64_t ldA, uint64_t M, const double
   return pick_or<kAtbStoreFixed, kAtbStore, kAtbNorm>(mode, 0, [&](auto M) {
     constexpr int m = M();  // (kAtbStoreFixed is kAtbStore's body with FIXED)
     return run_atb<m == kAtbNorm ? kAtbNorm : kAtbStore, false, m == kAtbStoreFixed>(
-        A, ldA, Bm, ldB, 0, 0, K / kTileRows, K / kTileRows, tri ? 1 : 0, *dtabp, out, ldo, nullptr);
+        A, ldA, Bm, ldB, 0, 0, K / kTileRows, K / kTileRows, tri ? 1 : 0, *dtabp, nullptr, out, ldo, nullptr);
   });
 }
 

@@ -292,6 +292,25 @@ struct GramDedup {
   DevBuf<uint8_t> skip_dev;    // the same on the device
   DevBuf<uint32_t> pairs;      // nskip skipped tile pairs, I | J << 16
   DevBuf<uint32_t> src;        // nskip x 128 x 128: the entry's source s' << 16 | t' (s' <= t', in a kept pair)
+  // The same analysis at the granularity of a wave's 64 x 64 tile (gram_plan.h: the plan at wave-tile
+  // granularity), run when a launch is long enough to pay for it or OBHIP_GRAM_DEDUP_QUADS=1 asks
+  struct Quads {
+    bool tried = false;
+    int hashbits = 0;
+    int ndrop = 0;               // dropped wave tiles
+    int blocks = 0;              // blocks per row split of the packed plan ...
+    int blocks_pairs = 0;        // ... and of the whole-pair plan (build_task_order under `skip`)
+    double setup_ms = 0.0;       // host wall time of the analysis and the packing
+    uint64_t sig = 0;
+    GramKey key;                 // the launch the decision below was taken for: shape, split, the whole-pair mask and
+                                 // dealing it competes with, the switch (no shape: none taken)
+    bool engaged = false;        // that launch runs the packed plan ...
+    bool continuous = false;     // ... dealt continuously or in whole runs
+    std::vector<uint8_t> keep;   // per wave tile (slot pair_slot(2 nb, a, b)): 0 = dropped
+    DevBuf<uint8_t> qskip_dev;   // per tile pair: bit 2 r + c set = its quadrant (r, c) is not computed
+    DevBuf<uint32_t> tiles;      // ndrop dropped wave tiles, a | b << 16 (64-column groups)
+    DevBuf<uint32_t> src;        // ndrop x 64 x 64 sources, in kept wave tiles
+  } quads;
 };
 }  // namespace obhip
 
@@ -467,6 +486,8 @@ struct obhip_basis {
   struct GramTable {            // XCD-aware (tile pair, row split) task order of that kernel ...
     obhip::GramKey key;         // ... and what it was built for (no shape: no table)
     obhip::DevBuf<uint64_t> tab;
+    obhip::DevBuf<uint32_t> wbytes;  // the four wave bytes of every task (packed plan; unused otherwise)
+    bool packed = false;
   } gram_table;
   std::unique_ptr<obhip_gradbasis> grad;  // built on first *_gradhyp call, dropped on rebuild
   int device = 0;
@@ -575,13 +596,20 @@ struct GramFuse {
 };
 int launch_gram(const obhip_basis &b, obhip_terms &t, double *d_G);
 int launch_gram_to(const obhip_basis &b, obhip_terms &t, const GramSink &sink, GramFuse *fuse = nullptr);
-// skip (device, may be null): tile pairs whose partials were never written and that are left alone
+// skip (device, may be null): per tile pair one bit per quadrant (2 row + column) whose partials were never
+// written and that is left alone (0x0f: the whole pair)
 int launch_gram_reduce(const double *part, int npairs, int nsplit, int nb, int p, const GramSink &sink,
                        bool accumulate, bool last, const uint8_t *skip = nullptr);
 // gram_dedup.hip: *out = the redundant tile pairs of t's term set, nullptr when there are none (or
 // OBHIP_GRAM_DEDUP=0); launch_gram_fill copies their entries from their sources in the sink
 int gram_dedup_get(obhip_terms &t, const GramDedup **out);
 int launch_gram_fill(const GramDedup &dd, int p, const GramSink &sink);
+// the analysis at wave-tile granularity and its packed plan (OBHIP_GRAM_DEDUP_QUADS): *out = t.dedup.quads when the
+// launch of this shape at this split is to run it (forced, or it saves a block per split and more modelled
+// time than its set-up took), nullptr otherwise; launch_gram_fill_quads copies the dropped wave tiles' entries
+int gram_quads_get(obhip_terms &t, const GramShape &shape, const GramPlan &plan, const uint8_t *skip, uint64_t skip_sig,
+                   const GramDedup::Quads **out);
+int launch_gram_fill_quads(const GramDedup::Quads &q, int p, const GramSink &sink);
 void set_gram_backend(int b);
 int get_gram_backend();
 // kernels_gram_panel.hip
