@@ -1024,16 +1024,15 @@ int launch_main_effect(const obhip_model &m, obhip_terms &t, uint64_t dim, const
 // second-order and total-interaction variances and the interaction surface
 constexpr int kSobol2T = 5;  // dimensions per block of the d x d triangle of outputs: T x T accumulators per pass
 inline int sobol2_reg_dims(uint64_t d) { return d <= 8 ? 8 : 24; }  // dimensions whose row offsets stay in registers
-size_t sobol2_pairs_lds(uint64_t n_cov);                             // dynamic LDS of k_sobol_pairs2
-uint64_t sobol2_part_doubles(uint64_t p, uint64_t d, uint64_t q);    // partials of its pair sum
+size_t sobol2_pairs_lds(uint64_t n_cov);                             // dynamic LDS of k_block_pairs<Sobol2Op>
 // pairs: obhip_terms::sobol_pairs; gmax: the largest L_i L_j; d_out q x 2 n_pairs (the V2 half), d_G may be null
 int launch_sobol2_second(const uint8_t *d_lev, const int *d_meta, const int *d_pairs, uint64_t p, uint64_t d, uint64_t q,
                          uint64_t n_pairs, uint64_t n_G, uint64_t gmax, const double *d_Theta, const double *d_mtab,
                          const double *d_ctab, double *d_out, double *d_G);
-// the VT2 half of d_out
-int launch_sobol2_pairs(const uint8_t *d_lev, const int *d_meta, const int *d_pairs, uint64_t p, uint64_t d, uint64_t q,
-                        uint64_t n_cov, const double *d_Theta, const double *d_mtab, const double *d_ctab,
-                        double *d_part, double *d_out);
+// the VT2 half of d_out; d_part: pair_part_doubles (sens_plan.h) at kSobol2T, kSobolRC
+int launch_sobol2_pairs(const uint8_t *d_lev, const int *d_meta, uint64_t p, uint64_t d, uint64_t q, uint64_t n_cov,
+                        const double *d_Theta, const double *d_mtab, const double *d_ctab, double *d_part,
+                        double *d_out);
 // d_Gij: G of the pair (di, dj) of response 0, response j at j * n_G
 int launch_interaction_effect(const obhip_model &m, obhip_terms &t, uint64_t di, uint64_t dj, const double *d_Gij,
                               uint64_t n_G, uint64_t q, const double *d_grid_i, uint64_t Gi, const double *d_grid_j,
@@ -1064,10 +1063,9 @@ int launch_shapley_pairs(const ShapPlan &plan, const uint8_t *d_lev, const int *
 // kernels_active.hip: E[grad f grad f^T] and E[grad f] of the fitted mean in closed form, DESIGN.md section 31
 constexpr int kActiveT = 5;   // dimensions per block of the d x d triangle of outputs (diagonal included)
 constexpr int kActiveRC = 2;  // responses per chunk of the pair sum
-int active_moment_threads(uint64_t lmax);                           // threads per block of k_dim_grad_moments
-size_t active_moments_lds(uint64_t lmax);                           // and its dynamic LDS
-size_t active_pairs_lds(uint64_t n_cov);                            // dynamic LDS of k_active_pairs
-uint64_t active_part_doubles(uint64_t p, uint64_t d, uint64_t q);   // partials of its pair sum
+int active_moment_threads(uint64_t lmax);                           // threads per block of the derivative moments
+size_t active_moments_lds(uint64_t lmax);                           // and their dynamic LDS (kernels_moments.hip)
+size_t active_pairs_lds(uint64_t n_cov);                            // dynamic LDS of k_block_pairs<ActiveOp>
 // the exclusion products of launch_sobol_first alone (kernels_sobol.hip): d_excl p x d, d_u p
 int launch_sobol_excl(const uint8_t *d_lev, const int *d_meta, uint64_t p, uint64_t d, const double *d_mtab,
                       double *d_excl, double *d_u);
@@ -1075,7 +1073,8 @@ int launch_sobol_excl(const uint8_t *d_lev, const int *d_meta, uint64_t p, uint6
 int launch_dim_grad_moments(const obhip_model &m, obhip_terms &t, const double *d_nodes, uint64_t n, uint64_t ldx,
                             const double *d_w, uint64_t ldw, double *d_dmean, double *d_cross, double *d_dd,
                             int *flag_out);
-// d_out: q x (d + d (d + 1) / 2) row-major; d_excl (p x d), d_u (p) and d_part: scratch
+// d_out: q x (d + d (d + 1) / 2) row-major; d_excl (p x d), d_u (p) and d_part (pair_part_doubles at kActiveT,
+// kActiveRC): scratch
 int launch_active(const uint8_t *d_lev, const int *d_meta, uint64_t p, uint64_t d, uint64_t q, uint64_t n_cov,
                   const double *d_Theta, const double *d_mtab, const double *d_ctab, const double *d_dmtab,
                   const double *d_xtab, const double *d_ddtab, double *d_excl, double *d_u, double *d_part,

@@ -3,6 +3,7 @@
 // kernels_sobol.hip, kernels_shapley.hip and kernels_active.hip.
 // Every check that can refuse a call runs before the first device call.
 #include "obhip_internal.h"
+#include "sens_plan.h"
 
 #include <cfloat>
 #include <cmath>
@@ -37,7 +38,7 @@ int sobol_layout(const char *who, const obhip_terms &t, Layout &lay) {
 }
 
 // sobol_layout with the limits of the gradient tables on top: three tables of n_cov entries in the LDS of
-// k_active_pairs, two basis tiles in that of k_dim_grad_moments
+// k_block_pairs<ActiveOp>, two basis tiles in that of the derivative moments
 int active_layout(const char *who, const obhip_terms &t, Layout &lay) {
   OB_TRY(sobol_layout(who, t, lay));
   if (active_pairs_lds(lay.n_cov) > kLdsBudget || active_moments_lds(lay.lmax) > kLdsBudget)
@@ -47,6 +48,56 @@ int active_layout(const char *who, const obhip_terms &t, Layout &lay) {
 }
 
 uint64_t align256(uint64_t b) { return (b + 255) / 256 * 256; }
+
+int check_q(const char *who, uint64_t q) {
+  if (q == 0 || q > kSobolMaxQ) return fail(OBHIP_ERR_INVALID, std::string(who) + ": 1 to 65535 responses");
+  return 0;
+}
+
+// the nodes of a measure and, where there are weights, their leading dimension
+int check_nodes(const char *who, uint64_t n, uint64_t ldx, bool weights, uint64_t ldw) {
+  const std::string w(who);
+  if (n == 0) return fail(OBHIP_ERR_INVALID, w + ": no nodes, so no measure");
+  if (n > kSobolMaxRows) return fail(OBHIP_ERR_INVALID, w + ": more than 2^40 nodes in one call");
+  if (ldx < n) return fail(OBHIP_ERR_INVALID, w + ": leading dimension of the nodes below n");
+  if (weights && ldw < n) return fail(OBHIP_ERR_INVALID, w + ": leading dimension of the weights below n");
+  return 0;
+}
+
+// the arguments of a *_workspace_bytes call
+int check_ws_args(const char *who, uint64_t p, uint64_t d, uint64_t q, const uint64_t *bytes) {
+  if (!bytes || p == 0 || d == 0 || d > 255 || q == 0 || q > kSobolMaxQ || p > (1ull << 24))
+    return fail(OBHIP_ERR_INVALID, std::string(who) + ": null bytes, or p, d, q out of range");
+  return 0;
+}
+
+// the workspace of a pair sum that also needs the exclusion products: excl (p x d), u (p), the partials
+struct PairWs {
+  double *excl, *u, *part;
+  PairWs(void *ws, uint64_t p, uint64_t d)
+      : excl((double *)ws), u((double *)((char *)ws + align256(p * d * sizeof(double)))),
+        part((double *)((char *)ws + align256(p * d * sizeof(double)) + align256(p * sizeof(double)))) {}
+  static uint64_t bytes(uint64_t p, uint64_t d, uint64_t part_doubles) {
+    return align256(p * d * sizeof(double)) + align256(p * sizeof(double)) + align256(part_doubles * sizeof(double));
+  }
+};
+
+// the device side of a host entry: Theta and the mean and covariance tables up, the output and the workspace
+struct HostSums {
+  DevBuf<double> th, mean, cov, out;
+  DevBuf<char> ws;
+  uint64_t n_out = 0;
+  int up(const obhip_terms *t, const Layout &lay, const double *Theta, uint64_t q, const double *mean_tab,
+         const double *cov_tab, uint64_t out_doubles, uint64_t ws_bytes) {
+    n_out = out_doubles;
+    OB_TRY(th.upload(Theta, t->p * q));
+    OB_TRY(mean.upload(mean_tab, lay.n_mean));
+    OB_TRY(cov.upload(cov_tab, lay.n_cov));
+    OB_TRY(out.alloc(n_out));
+    return ws.alloc(ws_bytes);
+  }
+  int down(double *host_out) { return d2h(host_out, out.p, n_out * sizeof(double)); }
+};
 
 // levels as bytes and the table offsets on the device, once per term set
 int ensure_sobol_tables(obhip_terms &t) {
@@ -171,10 +222,7 @@ int obhip_dim_moments_dev(const obhip_model *m, const obhip_terms *t, const doub
                           const double *d_weights, uint64_t ldw, double *d_mean, double *d_cov) {
   if (!m || !t || !d_nodes || !d_mean || !d_cov)
     return fail(OBHIP_ERR_INVALID, "dim_moments_dev: null model, terms, nodes, mean or cov");
-  if (n == 0) return fail(OBHIP_ERR_INVALID, "dim_moments_dev: no nodes, so no measure");
-  if (n > kSobolMaxRows) return fail(OBHIP_ERR_INVALID, "dim_moments_dev: more than 2^40 nodes in one call");
-  if (ldx < n) return fail(OBHIP_ERR_INVALID, "dim_moments_dev: leading dimension of the nodes below n");
-  if (d_weights && ldw < n) return fail(OBHIP_ERR_INVALID, "dim_moments_dev: leading dimension of the weights below n");
+  OB_TRY(check_nodes("dim_moments_dev", n, ldx, d_weights != nullptr, ldw));
   OB_TRY(check_compat(m, t));
   Layout lay;
   OB_TRY(sobol_layout("dim_moments_dev", *t, lay));
@@ -188,10 +236,8 @@ int obhip_dim_moments_dev(const obhip_model *m, const obhip_terms *t, const doub
 }
 
 int obhip_sobol_workspace_bytes(uint64_t p, uint64_t d, uint64_t q, uint64_t *bytes) {
-  if (!bytes || p == 0 || d == 0 || d > 255 || q == 0 || q > kSobolMaxQ || p > (1ull << 24))
-    return fail(OBHIP_ERR_INVALID, "sobol_workspace_bytes: null bytes, or p, d, q out of range");
-  *bytes = align256(p * d * sizeof(double)) + align256(p * sizeof(double)) +
-           align256(sobol_part_doubles(p, d, q) * sizeof(double));
+  OB_TRY(check_ws_args("sobol_workspace_bytes", p, d, q, bytes));
+  *bytes = PairWs::bytes(p, d, sobol_part_doubles(p, d, q));
   return 0;
 }
 
@@ -199,7 +245,7 @@ int obhip_sobol_dev(const obhip_terms *t, const double *d_Theta, uint64_t q, con
                     const double *d_cov_tab, double *d_out, double *d_g, void *d_ws, uint64_t ws_bytes) {
   if (!t || !d_Theta || !d_mean_tab || !d_cov_tab || !d_out || !d_ws)
     return fail(OBHIP_ERR_INVALID, "sobol_dev: null terms, Theta, tables, out or workspace");
-  if (q == 0 || q > kSobolMaxQ) return fail(OBHIP_ERR_INVALID, "sobol_dev: 1 to 65535 responses");
+  OB_TRY(check_q("sobol_dev", q));
   Layout lay;
   OB_TRY(sobol_layout("sobol_dev", *t, lay));
   uint64_t need = 0;
@@ -209,14 +255,11 @@ int obhip_sobol_dev(const obhip_terms *t, const double *d_Theta, uint64_t q, con
   obhip_terms &tt = *const_cast<obhip_terms *>(t);
   OB_TRY(ensure_sobol_tables(tt));
   const uint64_t p = t->p, d = t->d;
-  char *ws = (char *)d_ws;
-  double *excl = (double *)ws;
-  double *u = (double *)(ws + align256(p * d * sizeof(double)));
-  double *part = (double *)(ws + align256(p * d * sizeof(double)) + align256(p * sizeof(double)));
+  const PairWs ws(d_ws, p, d);
   OB_TRY(launch_sobol_first(tt.sobol_lev.p, tt.sobol_meta.p, p, d, q, lay.lmax, lay.n_mean, d_Theta, d_mean_tab,
-                            d_cov_tab, excl, u, d_out, d_g));
-  return launch_sobol_pairs(tt.sobol_lev.p, tt.sobol_meta.p, p, d, q, lay.n_cov, d_Theta, d_mean_tab, d_cov_tab, part,
-                            d_out);
+                            d_cov_tab, ws.excl, ws.u, d_out, d_g));
+  return launch_sobol_pairs(tt.sobol_lev.p, tt.sobol_meta.p, p, d, q, lay.n_cov, d_Theta, d_mean_tab, d_cov_tab,
+                            ws.part, d_out);
 }
 
 int obhip_sobol2_layout(const obhip_terms *t, uint64_t *n_pairs, uint64_t *n_G) {
@@ -230,9 +273,9 @@ int obhip_sobol2_layout(const obhip_terms *t, uint64_t *n_pairs, uint64_t *n_G) 
 }
 
 int obhip_sobol2_workspace_bytes(uint64_t p, uint64_t d, uint64_t q, uint64_t *bytes) {
-  if (!bytes || p == 0 || d == 0 || d > 255 || q == 0 || q > kSobolMaxQ || p > (1ull << 24))
-    return fail(OBHIP_ERR_INVALID, "sobol2_workspace_bytes: null bytes, or p, d, q out of range");
-  *bytes = std::max<uint64_t>(256, align256(sobol2_part_doubles(p, d, q) * sizeof(double)));
+  OB_TRY(check_ws_args("sobol2_workspace_bytes", p, d, q, bytes));
+  const uint64_t part = pair_part_doubles(p, d, q, kSobol2T, kSobolRC, kSobolTW);
+  *bytes = std::max<uint64_t>(256, align256(part * sizeof(double)));
   return 0;
 }
 
@@ -240,7 +283,7 @@ int obhip_sobol2_dev(const obhip_terms *t, const double *d_Theta, uint64_t q, co
                      const double *d_cov_tab, double *d_out, double *d_G, void *d_ws, uint64_t ws_bytes) {
   if (!t || !d_Theta || !d_mean_tab || !d_cov_tab)
     return fail(OBHIP_ERR_INVALID, "sobol2_dev: null terms, Theta or tables");
-  if (q == 0 || q > kSobolMaxQ) return fail(OBHIP_ERR_INVALID, "sobol2_dev: 1 to 65535 responses");
+  OB_TRY(check_q("sobol2_dev", q));
   Layout lay;
   OB_TRY(sobol_layout("sobol2_dev", *t, lay));
   if (t->d == 1) return 0;  // no pairs: nothing to write
@@ -256,8 +299,8 @@ int obhip_sobol2_dev(const obhip_terms *t, const double *d_Theta, uint64_t q, co
   OB_TRY(ensure_sobol_pairs(tt));
   OB_TRY(launch_sobol2_second(tt.sobol_lev.p, tt.sobol_meta.p, tt.sobol_pairs.p, t->p, t->d, q, pl.n_pairs, pl.n_G,
                               pl.gmax, d_Theta, d_mean_tab, d_cov_tab, d_out, d_G));
-  return launch_sobol2_pairs(tt.sobol_lev.p, tt.sobol_meta.p, tt.sobol_pairs.p, t->p, t->d, q, lay.n_cov, d_Theta,
-                             d_mean_tab, d_cov_tab, (double *)d_ws, d_out);
+  return launch_sobol2_pairs(tt.sobol_lev.p, tt.sobol_meta.p, t->p, t->d, q, lay.n_cov, d_Theta, d_mean_tab, d_cov_tab,
+                             (double *)d_ws, d_out);
 }
 
 int obhip_gauss_legendre01(uint64_t G, double *nodes, double *weights) {
@@ -304,8 +347,7 @@ int obhip_shapley_layout(const obhip_terms *t, const int32_t *groups, uint64_t *
 }
 
 int obhip_shapley_workspace_bytes(uint64_t p, uint64_t d, uint64_t q, uint64_t *bytes) {
-  if (!bytes || p == 0 || d == 0 || d > 255 || q == 0 || q > kSobolMaxQ || p > (1ull << 24))
-    return fail(OBHIP_ERR_INVALID, "shapley_workspace_bytes: null bytes, or p, d, q out of range");
+  OB_TRY(check_ws_args("shapley_workspace_bytes", p, d, q, bytes));
   *bytes = align256(shapley_part_doubles(p, d, q) * sizeof(double));
   return 0;
 }
@@ -314,7 +356,7 @@ int obhip_shapley_dev(const obhip_terms *t, const int32_t *groups, const double 
                       const double *d_mean_tab, const double *d_cov_tab, double *d_out, void *d_ws, uint64_t ws_bytes) {
   if (!t || !d_Theta || !d_mean_tab || !d_cov_tab || !d_out || !d_ws)
     return fail(OBHIP_ERR_INVALID, "shapley_dev: null terms, Theta, tables, out or workspace");
-  if (q == 0 || q > kSobolMaxQ) return fail(OBHIP_ERR_INVALID, "shapley_dev: 1 to 65535 responses");
+  OB_TRY(check_q("shapley_dev", q));
   Layout lay;
   OB_TRY(sobol_layout("shapley_dev", *t, lay));  // (tables that fit k_sobol_pairs fit k_shapley_pairs: two of three)
   if (shapley_pairs_lds(t->d, lay.n_cov) > kLdsBudget)
@@ -337,7 +379,7 @@ int obhip_interaction_effect_dev(const obhip_model *m, const obhip_terms *t, uin
                                  const double *d_grid_j, uint64_t Gj, double *d_out) {
   if (!m || !t || !d_G || !d_grid_i || !d_grid_j || !d_out)
     return fail(OBHIP_ERR_INVALID, "interaction_effect_dev: null model, terms, G, grids or out");
-  if (q == 0 || q > kSobolMaxQ) return fail(OBHIP_ERR_INVALID, "interaction_effect_dev: 1 to 65535 responses");
+  OB_TRY(check_q("interaction_effect_dev", q));
   if (Gi > (1ull << 32) || Gj > (1ull << 32) || Gi * Gj > (1ull << 32))
     return fail(OBHIP_ERR_INVALID, "interaction_effect_dev: more than 2^32 grid points in one call");
   OB_TRY(check_compat(m, t));
@@ -361,7 +403,7 @@ int obhip_main_effect_dev(const obhip_model *m, const obhip_terms *t, uint64_t d
                           const double *d_grid, uint64_t G, double *d_out) {
   if (!m || !t || !d_g || !d_grid || !d_out)
     return fail(OBHIP_ERR_INVALID, "main_effect_dev: null model, terms, g, grid or out");
-  if (q == 0 || q > kSobolMaxQ) return fail(OBHIP_ERR_INVALID, "main_effect_dev: 1 to 65535 responses");
+  OB_TRY(check_q("main_effect_dev", q));
   if (G > kSobolMaxRows) return fail(OBHIP_ERR_INVALID, "main_effect_dev: more than 2^40 grid points in one call");
   OB_TRY(check_compat(m, t));
   if (dim >= m->d) return fail(OBHIP_ERR_INVALID, "main_effect_dev: dimension out of range");
@@ -376,10 +418,7 @@ int obhip_dim_moments(const obhip_model *m, const obhip_terms *t, const double *
                       const double *weights, uint64_t ldw, double *mean, double *cov) {
   if (!m || !t || !nodes || !mean || !cov)
     return fail(OBHIP_ERR_INVALID, "dim_moments: null model, terms, nodes, mean or cov");
-  if (n == 0) return fail(OBHIP_ERR_INVALID, "dim_moments: no nodes, so no measure");
-  if (n > kSobolMaxRows) return fail(OBHIP_ERR_INVALID, "dim_moments: more than 2^40 nodes in one call");
-  if (ldx < n) return fail(OBHIP_ERR_INVALID, "dim_moments: leading dimension of the nodes below n");
-  if (weights && ldw < n) return fail(OBHIP_ERR_INVALID, "dim_moments: leading dimension of the weights below n");
+  OB_TRY(check_nodes("dim_moments", n, ldx, weights != nullptr, ldw));
   OB_TRY(check_compat(m, t));
   Layout lay;
   OB_TRY(sobol_layout("dim_moments", *t, lay));
@@ -398,22 +437,18 @@ int obhip_sobol(const obhip_terms *t, const double *Theta, uint64_t q, const dou
                 double *out, double *g) {
   if (!t || !Theta || !mean_tab || !cov_tab || !out)
     return fail(OBHIP_ERR_INVALID, "sobol: null terms, Theta, tables or out");
-  if (q == 0 || q > kSobolMaxQ) return fail(OBHIP_ERR_INVALID, "sobol: 1 to 65535 responses");
+  OB_TRY(check_q("sobol", q));
   Layout lay;
   OB_TRY(sobol_layout("sobol", *t, lay));
   uint64_t wsb = 0;
   OB_TRY(obhip_sobol_workspace_bytes(t->p, t->d, q, &wsb));
   OB_TRY(require_device());
-  DevBuf<double> dth, dm, dc, dout, dg;
-  DevBuf<char> ws;
-  OB_TRY(dth.upload(Theta, t->p * q));
-  OB_TRY(dm.upload(mean_tab, lay.n_mean));
-  OB_TRY(dc.upload(cov_tab, lay.n_cov));
-  OB_TRY(dout.alloc(q * (2 + 2 * t->d)));
+  HostSums h;
+  DevBuf<double> dg;
+  OB_TRY(h.up(t, lay, Theta, q, mean_tab, cov_tab, q * (2 + 2 * t->d), wsb));
   if (g) OB_TRY(dg.alloc(q * lay.n_mean));
-  OB_TRY(ws.alloc(wsb));
-  OB_TRY(obhip_sobol_dev(t, dth.p, q, dm.p, dc.p, dout.p, dg.p, ws.p, wsb));
-  OB_TRY(d2h(out, dout.p, q * (2 + 2 * t->d) * sizeof(double)));
+  OB_TRY(obhip_sobol_dev(t, h.th.p, q, h.mean.p, h.cov.p, h.out.p, dg.p, h.ws.p, wsb));
+  OB_TRY(h.down(out));
   if (g) OB_TRY(d2h(g, dg.p, q * lay.n_mean * sizeof(double)));
   return 0;
 }
@@ -421,7 +456,7 @@ int obhip_sobol(const obhip_terms *t, const double *Theta, uint64_t q, const dou
 int obhip_sobol2(const obhip_terms *t, const double *Theta, uint64_t q, const double *mean_tab, const double *cov_tab,
                  double *out, double *G) {
   if (!t || !Theta || !mean_tab || !cov_tab) return fail(OBHIP_ERR_INVALID, "sobol2: null terms, Theta or tables");
-  if (q == 0 || q > kSobolMaxQ) return fail(OBHIP_ERR_INVALID, "sobol2: 1 to 65535 responses");
+  OB_TRY(check_q("sobol2", q));
   Layout lay;
   OB_TRY(sobol_layout("sobol2", *t, lay));
   if (t->d == 1) return 0;
@@ -430,16 +465,12 @@ int obhip_sobol2(const obhip_terms *t, const double *Theta, uint64_t q, const do
   OB_TRY(obhip_sobol2_workspace_bytes(t->p, t->d, q, &wsb));
   const PairLayout pl = pair_layout(*t);
   OB_TRY(require_device());
-  DevBuf<double> dth, dm, dc, dout, dg;
-  DevBuf<char> ws;
-  OB_TRY(dth.upload(Theta, t->p * q));
-  OB_TRY(dm.upload(mean_tab, lay.n_mean));
-  OB_TRY(dc.upload(cov_tab, lay.n_cov));
-  OB_TRY(dout.alloc(q * 2 * pl.n_pairs));
+  HostSums h;
+  DevBuf<double> dg;
+  OB_TRY(h.up(t, lay, Theta, q, mean_tab, cov_tab, q * 2 * pl.n_pairs, wsb));
   if (G) OB_TRY(dg.alloc(q * pl.n_G));
-  OB_TRY(ws.alloc(wsb));
-  OB_TRY(obhip_sobol2_dev(t, dth.p, q, dm.p, dc.p, dout.p, dg.p, ws.p, wsb));
-  OB_TRY(d2h(out, dout.p, q * 2 * pl.n_pairs * sizeof(double)));
+  OB_TRY(obhip_sobol2_dev(t, h.th.p, q, h.mean.p, h.cov.p, h.out.p, dg.p, h.ws.p, wsb));
+  OB_TRY(h.down(out));
   if (G) OB_TRY(d2h(G, dg.p, q * pl.n_G * sizeof(double)));
   return 0;
 }
@@ -448,7 +479,7 @@ int obhip_shapley(const obhip_terms *t, const int32_t *groups, const double *The
                   const double *cov_tab, double *out) {
   if (!t || !Theta || !mean_tab || !cov_tab || !out)
     return fail(OBHIP_ERR_INVALID, "shapley: null terms, Theta, tables or out");
-  if (q == 0 || q > kSobolMaxQ) return fail(OBHIP_ERR_INVALID, "shapley: 1 to 65535 responses");
+  OB_TRY(check_q("shapley", q));
   Layout lay;
   OB_TRY(sobol_layout("shapley", *t, lay));
   ShapPlan plan;
@@ -456,15 +487,10 @@ int obhip_shapley(const obhip_terms *t, const int32_t *groups, const double *The
   uint64_t wsb = 0;
   OB_TRY(obhip_shapley_workspace_bytes(t->p, t->d, q, &wsb));
   OB_TRY(require_device());
-  DevBuf<double> dth, dm, dc, dout;
-  DevBuf<char> ws;
-  OB_TRY(dth.upload(Theta, t->p * q));
-  OB_TRY(dm.upload(mean_tab, lay.n_mean));
-  OB_TRY(dc.upload(cov_tab, lay.n_cov));
-  OB_TRY(dout.alloc(q * (uint64_t)plan.nplayers));
-  OB_TRY(ws.alloc(wsb));
-  OB_TRY(obhip_shapley_dev(t, groups, dth.p, q, dm.p, dc.p, dout.p, ws.p, wsb));
-  return d2h(out, dout.p, q * (uint64_t)plan.nplayers * sizeof(double));
+  HostSums h;
+  OB_TRY(h.up(t, lay, Theta, q, mean_tab, cov_tab, q * (uint64_t)plan.nplayers, wsb));
+  OB_TRY(obhip_shapley_dev(t, groups, h.th.p, q, h.mean.p, h.cov.p, h.out.p, h.ws.p, wsb));
+  return h.down(out);
 }
 
 // ---- active subspaces and derivative-based sensitivity ---------------------------------
@@ -483,11 +509,7 @@ int obhip_dim_grad_moments_dev(const obhip_model *m, const obhip_terms *t, const
                                double *d_dd) {
   if (!m || !t || !d_nodes || !d_dmean || !d_cross || !d_dd)
     return fail(OBHIP_ERR_INVALID, "dim_grad_moments_dev: null model, terms, nodes, dmean, cross or dd");
-  if (n == 0) return fail(OBHIP_ERR_INVALID, "dim_grad_moments_dev: no nodes, so no measure");
-  if (n > kSobolMaxRows) return fail(OBHIP_ERR_INVALID, "dim_grad_moments_dev: more than 2^40 nodes in one call");
-  if (ldx < n) return fail(OBHIP_ERR_INVALID, "dim_grad_moments_dev: leading dimension of the nodes below n");
-  if (d_weights && ldw < n)
-    return fail(OBHIP_ERR_INVALID, "dim_grad_moments_dev: leading dimension of the weights below n");
+  OB_TRY(check_nodes("dim_grad_moments_dev", n, ldx, d_weights != nullptr, ldw));
   OB_TRY(check_compat(m, t));
   Layout lay;
   OB_TRY(active_layout("dim_grad_moments_dev", *t, lay));
@@ -502,10 +524,8 @@ int obhip_dim_grad_moments_dev(const obhip_model *m, const obhip_terms *t, const
 }
 
 int obhip_active_workspace_bytes(uint64_t p, uint64_t d, uint64_t q, uint64_t *bytes) {
-  if (!bytes || p == 0 || d == 0 || d > 255 || q == 0 || q > kSobolMaxQ || p > (1ull << 24))
-    return fail(OBHIP_ERR_INVALID, "active_workspace_bytes: null bytes, or p, d, q out of range");
-  *bytes = align256(p * d * sizeof(double)) + align256(p * sizeof(double)) +
-           align256(active_part_doubles(p, d, q) * sizeof(double));
+  OB_TRY(check_ws_args("active_workspace_bytes", p, d, q, bytes));
+  *bytes = PairWs::bytes(p, d, pair_part_doubles(p, d, q, kActiveT, kActiveRC, kSobolTW));
   return 0;
 }
 
@@ -514,7 +534,7 @@ int obhip_active_dev(const obhip_terms *t, const double *d_Theta, uint64_t q, co
                      double *d_out, void *d_ws, uint64_t ws_bytes) {
   if (!t || !d_Theta || !d_mean_tab || !d_cov_tab || !d_dmean || !d_cross || !d_dd || !d_out || !d_ws)
     return fail(OBHIP_ERR_INVALID, "active_dev: null terms, Theta, tables, out or workspace");
-  if (q == 0 || q > kSobolMaxQ) return fail(OBHIP_ERR_INVALID, "active_dev: 1 to 65535 responses");
+  OB_TRY(check_q("active_dev", q));
   Layout lay;
   OB_TRY(active_layout("active_dev", *t, lay));
   uint64_t need = 0;
@@ -525,22 +545,16 @@ int obhip_active_dev(const obhip_terms *t, const double *d_Theta, uint64_t q, co
   obhip_terms &tt = *const_cast<obhip_terms *>(t);
   OB_TRY(ensure_sobol_tables(tt));
   const uint64_t p = t->p, d = t->d;
-  char *ws = (char *)d_ws;
-  double *excl = (double *)ws;
-  double *u = (double *)(ws + align256(p * d * sizeof(double)));
-  double *part = (double *)(ws + align256(p * d * sizeof(double)) + align256(p * sizeof(double)));
+  const PairWs ws(d_ws, p, d);
   return launch_active(tt.sobol_lev.p, tt.sobol_meta.p, p, d, q, lay.n_cov, d_Theta, d_mean_tab, d_cov_tab, d_dmean,
-                       d_cross, d_dd, excl, u, part, d_out);
+                       d_cross, d_dd, ws.excl, ws.u, ws.part, d_out);
 }
 
 int obhip_dim_grad_moments(const obhip_model *m, const obhip_terms *t, const double *nodes, uint64_t n, uint64_t ldx,
                            const double *weights, uint64_t ldw, double *dmean, double *cross, double *dd) {
   if (!m || !t || !nodes || !dmean || !cross || !dd)
     return fail(OBHIP_ERR_INVALID, "dim_grad_moments: null model, terms, nodes, dmean, cross or dd");
-  if (n == 0) return fail(OBHIP_ERR_INVALID, "dim_grad_moments: no nodes, so no measure");
-  if (n > kSobolMaxRows) return fail(OBHIP_ERR_INVALID, "dim_grad_moments: more than 2^40 nodes in one call");
-  if (ldx < n) return fail(OBHIP_ERR_INVALID, "dim_grad_moments: leading dimension of the nodes below n");
-  if (weights && ldw < n) return fail(OBHIP_ERR_INVALID, "dim_grad_moments: leading dimension of the weights below n");
+  OB_TRY(check_nodes("dim_grad_moments", n, ldx, weights != nullptr, ldw));
   OB_TRY(check_compat(m, t));
   Layout lay;
   OB_TRY(active_layout("dim_grad_moments", *t, lay));
@@ -561,25 +575,21 @@ int obhip_active(const obhip_terms *t, const double *Theta, uint64_t q, const do
                  const double *dmean, const double *cross, const double *dd, double *out) {
   if (!t || !Theta || !mean_tab || !cov_tab || !dmean || !cross || !dd || !out)
     return fail(OBHIP_ERR_INVALID, "active: null terms, Theta, tables or out");
-  if (q == 0 || q > kSobolMaxQ) return fail(OBHIP_ERR_INVALID, "active: 1 to 65535 responses");
+  OB_TRY(check_q("active", q));
   Layout lay;
   OB_TRY(active_layout("active", *t, lay));
   uint64_t wsb = 0;
   OB_TRY(obhip_active_workspace_bytes(t->p, t->d, q, &wsb));
   OB_TRY(require_device());
   const uint64_t nout = t->d + t->d * (t->d + 1) / 2;
-  DevBuf<double> dth, dm, dc, ddm, dx, dv, dout;
-  DevBuf<char> ws;
-  OB_TRY(dth.upload(Theta, t->p * q));
-  OB_TRY(dm.upload(mean_tab, lay.n_mean));
-  OB_TRY(dc.upload(cov_tab, lay.n_cov));
+  HostSums h;
+  DevBuf<double> ddm, dx, dv;
+  OB_TRY(h.up(t, lay, Theta, q, mean_tab, cov_tab, q * nout, wsb));
   OB_TRY(ddm.upload(dmean, lay.n_mean));
   OB_TRY(dx.upload(cross, lay.n_cov));
   OB_TRY(dv.upload(dd, lay.n_cov));
-  OB_TRY(dout.alloc(q * nout));
-  OB_TRY(ws.alloc(wsb));
-  OB_TRY(obhip_active_dev(t, dth.p, q, dm.p, dc.p, ddm.p, dx.p, dv.p, dout.p, ws.p, wsb));
-  return d2h(out, dout.p, q * nout * sizeof(double));
+  OB_TRY(obhip_active_dev(t, h.th.p, q, h.mean.p, h.cov.p, ddm.p, dx.p, dv.p, h.out.p, h.ws.p, wsb));
+  return h.down(out);
 }
 
 int obhip_sym_eigh(uint64_t n, const double *A, double *w, double *V) {

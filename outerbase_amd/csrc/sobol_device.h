@@ -1,8 +1,11 @@
-// Device helpers shared by kernels_sobol.hip, kernels_shapley.hip and kernels_active.hip.
+// Device helpers shared by kernels_sobol.hip, kernels_shapley.hip, kernels_active.hip and kernels_moments.hip.
+// The index arithmetic that the host shares is in sens_plan.h, the frame of the term-pair sums in pair_sum.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "obhip_internal.h"
+#include "device_common.h"
+#include "sens_plan.h"
 
 namespace obhip {
 
@@ -12,27 +15,18 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
-// the z-th pair (I <= J) of ntile term tiles in the order (0,0), (0,1), .. (0,ntile-1), (1,1), ..
-__device__ __forceinline__ void tile_pair(int z, int ntile, int &I, int &J) {
-  I = 0;
-  while (z >= ntile - I) {
-    z -= ntile - I;
-    ++I;
+// sum over the block's 256 threads by a tree in red[256]; every thread gets it
+__device__ __forceinline__ double block_tree_256(double v, double *red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int off = 128; off >= 1; off >>= 1) {
+    if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+    __syncthreads();
   }
-  J = I + z;
+  return red[0];
 }
 
-// the z-th pair (ta >= tb) of level tiles in the order (0,0), (1,0), (1,1), (2,0), ..
-__device__ __forceinline__ void tile_pair_lower(int z, int &ta, int &tb) {
-  ta = 0;
-  while (z >= ta + 1) {
-    z -= ta + 1;
-    ++ta;
-  }
-  tb = z;
-}
-
-// ---- the moment kernels (k_dim_moments, k_dim_grad_moments) -------------------------------------------------
+// ---- the moment kernels (kernels_moments.hip) ---------------------------------------------------------------
 constexpr int kMomLT = 8;            // levels per accumulator tile
 constexpr int kMomP1 = kMomLT + 2;   // sums of pass 1: 8 levels, the weights, the bad weights
 constexpr int kMomP2 = kMomLT * kMomLT;
@@ -58,6 +52,28 @@ __device__ __forceinline__ int cov_offset(const DimDesc *__restrict__ dims, int 
   int o = 0;
   for (int i = 0; i < l; ++i) o += dims[i].ncol * dims[i].ncol;
   return o;
+}
+
+struct StoreCol {
+  double *col;  // tile + thread
+  int ccol0, nt;
+  __device__ __forceinline__ void operator()(int ccol, double v) const { col[(size_t)(ccol - ccol0 + 1) * nt] = v; }
+};
+
+// raw psi_{l,t}(xv), t < D.ncol, into col[t * nt]
+__device__ __forceinline__ void eval_raw(const DimDesc &D, const double *ka, const double *kb, const double *kc,
+                                         const double *rot, const double *tab, double xv, double *col, int nt) {
+  const StoreCol st{col, D.ccol0, nt};
+  const double c0 = build_dim_any(D, ka, kb, kc, rot, tab, xv, st);
+  col[0] = c0;
+  for (int t = 1; t < D.ncol; ++t) col[(size_t)t * nt] *= c0;
+}
+
+// threads per block and dynamic LDS of the kernels that evaluate one basis tile:
+// [interval tables kIntervalTabMax][reduction 4 * 64][tile lmax * threads]
+inline int eval_threads(uint64_t lmax) { return lmax <= 32 ? 256 : 64; }
+inline size_t eval_lds(uint64_t lmax) {
+  return (kIntervalTabMax + 4 * kMomP2 + lmax * eval_threads(lmax)) * sizeof(double);
 }
 
 // part[k] = sum over the block of acc[k]: butterfly per wave, the waves in order

@@ -32,11 +32,13 @@ FP64_VECTOR_PEAK = 78.6e12  # MI355X data sheet, vector FP64 flop/s
 U = 2.0 ** -53
 T = 5                       # kActiveT: dimensions per block of the output triangle
 # VGPRs, AGPRs, scratch bytes per lane, waves per SIMD (compiler remarks, gfx950)
-RESOURCES = {"k_dim_grad_moments<0>": [154, 0, 0, 3], "k_dim_grad_moments<1>": [256, 2, 0, 1],
-             "k_dim_grad_moments<2>": [256, 2, 0, 1], "k_grad_moments_fin<0|1|2>": [22, 0, 0, 8],
-             "k_active_gbar": [20, 0, 0, 8], "k_active_reduce": [8, 0, 0, 8],
-             "k_active_pairs<8, diagonal>": [146, 0, 0, 3], "k_active_pairs<8, off-diagonal>": [203, 0, 0, 2],
-             "k_active_pairs<24, diagonal>": [163, 0, 0, 3], "k_active_pairs<24, off-diagonal>": [235, 0, 0, 2]}
+RESOURCES = {"k_moments<DerivMeans>": [154, 0, 0, 3], "k_moments<DerivCross>": [256, 2, 0, 1],
+             "k_moments<DerivProducts>": [256, 2, 0, 1], "k_moments_fin<one tile|all pairs|lower pairs>": [22, 0, 0, 8],
+             "k_active_gbar": [20, 0, 0, 8], "k_block_reduce<5, 2, with diagonal>": [8, 0, 0, 8],
+             "k_block_pairs<ActiveOp, 8, diagonal>": [146, 0, 0, 3],
+             "k_block_pairs<ActiveOp, 8, off-diagonal>": [203, 0, 0, 2],
+             "k_block_pairs<ActiveOp, 24, diagonal>": [163, 0, 0, 3],
+             "k_block_pairs<ActiveOp, 24, off-diagonal>": [235, 0, 0, 2]}
 
 
 def ops_active(p, d, q):

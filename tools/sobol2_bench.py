@@ -28,9 +28,12 @@ FP64_VECTOR_PEAK = 78.6e12  # MI355X data sheet, vector FP64 flop/s
 U = 2.0 ** -53
 T = 5                       # kSobol2T: dimensions per block of the output triangle
 # VGPRs, AGPRs, scratch bytes per lane, waves per SIMD (compiler remarks, gfx950)
-RESOURCES = {"k_sobol2_second": [48, 0, 0, 8], "k_sobol2_reduce": [8, 0, 0, 8], "k_interaction_effect": [129, 0, 0, 3],
-             "k_sobol_pairs2<8, diagonal>": [88, 0, 0, 5], "k_sobol_pairs2<8, off-diagonal>": [179, 0, 0, 2],
-             "k_sobol_pairs2<24, diagonal>": [125, 0, 0, 4], "k_sobol_pairs2<24, off-diagonal>": [207, 0, 0, 2]}
+RESOURCES = {"k_sobol2_second": [48, 0, 0, 8], "k_block_reduce<5, 2, no diagonal>": [8, 0, 0, 8],
+             "k_interaction_effect": [129, 0, 0, 3],
+             "k_block_pairs<Sobol2Op, 8, diagonal>": [88, 0, 0, 5],
+             "k_block_pairs<Sobol2Op, 8, off-diagonal>": [179, 0, 0, 2],
+             "k_block_pairs<Sobol2Op, 24, diagonal>": [125, 0, 0, 4],
+             "k_block_pairs<Sobol2Op, 24, off-diagonal>": [207, 0, 0, 2]}
 
 
 def ops_sobol(p, d, q):
