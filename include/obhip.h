@@ -1156,7 +1156,11 @@ int obhip_margadj_full(const obhip_basis *b, const obhip_terms *t, const obhip_m
  * e^{2 sigma} unless asked for.  d_x is column-major n x d (leading dimension n), on the device.
  * Every argument check runs before the first launch and a refused call changes nothing; a Hessian
  * that is not positive definite is OBHIP_ERR_NUMERIC, as the other solve entries report it (the
- * create entries wait for their factorisation). */
+ * create entries wait for their factorisation).
+ * The explicit S = inv(H) = X X^T (pad128(p)^2 doubles, pad128(p) = p rounded up to 128) is formed
+ * by the handle's first design, acquisition or gradient call (obhip_design_select*, obhip_acquire*,
+ * obhip_posterior_var_grad_dev, obhip_acquire_grad*) and stays on the handle until it is destroyed;
+ * the selection entries downdate a copy of their own, the handle's S is never written again. */
 /* d_H: symmetric p x p on the device, copied */
 int obhip_posterior_create_dev(obhip_posterior **out, const obhip_model *m, const obhip_terms *t,
                                const double *d_H, double sigma);

@@ -1,83 +1,33 @@
 // Input gradients of the full-covariance posterior variance and of the acquisition criteria: host side
 // (include/obhip.h, "acquisition gradients").  No reference counterpart.
 //
-//   posterior_inverse   S = inv(H) = X X^T, formed once per handle exactly as the design and acquisition entries
-//                       form theirs per call, kept on the handle and freed with it.
-//   run_acquire_dx      per row chunk the basis at the chunk, B^T term-major by launch_getmat, the stored product
-//                       Y = S B^T by launch_atb in its fixed-order mode (bit-identical rows give bit-identical
+//   run_acquire_dx      the handle's S = inv(H) (posterior_inverse), then per row chunk (for_row_chunks) the stored
+//                       product Y = S B^T by launch_atb in its fixed-order mode (bit-identical rows give bit-identical
 //                       columns of Y wherever they stand and however the call is chunked), then k_acquire_dx.
 // Every check that can refuse a call runs before the first device call.
 #include <cmath>
 
 #include "obhip_internal.h"
+#include "row_chunks.h"
 
 using namespace obhip;
 
-namespace obhip {
-
-// S (pp x pp) = inv(H) = Linv^T Linv with Linv = X^T, as obhip_design_select_dev and obhip_acquire_dev form theirs
-static int form_inverse(const PostFactor &f, DevBuf<double> &S) {
-  const uint64_t p = f.p, pp = f.pp;
-  hipStream_t st = cur_stream();
-  DevBuf<double> Linv;
-  OB_TRY(S.alloc(pp * pp));
-  OB_TRY(Linv.alloc(pp * pp));
-  OB_HIP(hipMemsetAsync(Linv.p, 0, pp * pp * sizeof(double), st));
-  OB_TRY(launch_transpose(f.X.p, pp, Linv.p, pp, p));
-  OB_TRY(launch_atb(kAtbStore, Linv.p, pp, pp, Linv.p, pp, pp, pp, false, S.p, pp));
-  OB_HIP(hipStreamSynchronize(st));  // Linv is a local
-  return 0;
-}
-
-int posterior_inverse(const obhip_posterior &post, const double **S) {
-  std::lock_guard<std::mutex> g(post.S_lock);
-  if (!post.S.p) {
-    const int rc = form_inverse(post.f, post.S);
-    if (rc) {
-      post.S.release();  // never a half-formed inverse on the handle
-      return rc;
-    }
-  }
-  *S = post.S.p;
-  return 0;
-}
-
-}  // namespace obhip
-
 namespace {
 
-constexpr uint64_t kAdxMaxRows = 1ull << 40;  // as the input-gradient predictor
-
-uint64_t pad128(uint64_t v) { return (v + 127) / 128 * 128; }
-
 // rows of a chunk so that B^T and Y (pp x rows doubles each) stay within 1 GiB each
-uint64_t default_chunk_rows(uint64_t pp) {
-  return std::max<uint64_t>(128, ((1ull << 30) / (pp * sizeof(double))) / 128 * 128);
-}
+uint64_t default_chunk_rows(uint64_t pp) { return chunk_rows_for(pp, 1ull << 30); }
 
 int check_handle(const std::string &w, const obhip_posterior *post, const void *x, uint64_t n, uint64_t chunk_rows) {
   if (chunk_rows % 128 != 0) return fail(OBHIP_ERR_INVALID, w + ": chunk_rows must be 0 or a positive multiple of 128");
-  if (n > kAdxMaxRows) return fail(OBHIP_ERR_INVALID, w + ": more than 2^40 rows in one call");
+  if (n > kMaxRowsPerCall) return fail(OBHIP_ERR_INVALID, w + ": more than 2^40 rows in one call");
   if (!x && n > 0) return fail(OBHIP_ERR_INVALID, w + ": null x");
-  if (!post) return fail(OBHIP_ERR_INVALID, w + ": null posterior");
-  OB_TRY(check_compat(post->model, post->terms));
-  if (post->terms->p != post->p || post->p > 65535)
-    return fail(OBHIP_ERR_INVALID, w + ": the posterior and its terms disagree on p (or p > 65535)");
-  return 0;
+  return check_post_handle(w, post, true);
 }
 
 int check_criterion(const std::string &w, const void *theta, int criterion, const double *params, const void *score,
                     const void *gradscore) {
-  if (criterion < OBHIP_ACQ_EI || criterion > OBHIP_ACQ_STRADDLE)
-    return fail(OBHIP_ERR_INVALID, w + ": criterion must be OBHIP_ACQ_EI, _PI, _LCB or _STRADDLE");
-  if (!params) return fail(OBHIP_ERR_INVALID, w + ": params (best, xi, kappa, level) is null");
-  if ((criterion == OBHIP_ACQ_EI || criterion == OBHIP_ACQ_PI) && !std::isfinite(params[0]))
-    return fail(OBHIP_ERR_INVALID, w + ": best must be finite for EI and PI");
-  if (!std::isfinite(params[1])) return fail(OBHIP_ERR_INVALID, w + ": xi must be finite");
-  if (!std::isfinite(params[2]) || params[2] < 0.0)
-    return fail(OBHIP_ERR_INVALID, w + ": kappa must be finite and >= 0");
-  if (criterion == OBHIP_ACQ_STRADDLE && !std::isfinite(params[3]))
-    return fail(OBHIP_ERR_INVALID, w + ": level must be finite for STRADDLE");
+  OB_TRY(check_acq_criterion(w, criterion));
+  OB_TRY(check_acq_params(w, criterion, params));
   if (!theta) return fail(OBHIP_ERR_INVALID, w + ": theta is null");
   if (!score || !gradscore) return fail(OBHIP_ERR_INVALID, w + ": null outputs score / gradscore");
   return 0;
@@ -92,33 +42,18 @@ int run_acquire_dx(const obhip_posterior *post, int crit, const double *d_theta,
   OB_TRY(prepare_predict(om, t, true));
   const double *S = nullptr;
   OB_TRY(posterior_inverse(*post, &S));
-  const uint64_t cmax = chunk_rows ? chunk_rows : default_chunk_rows(pp);
   a.ldo = n;
-  DevBuf<double> Bcm, Ycm, xc;
-  for (uint64_t r0 = 0; r0 < n; r0 += cmax) {
-    const uint64_t nr = std::min(cmax, n - r0), npad = pad128(nr);
-    const double *xsrc = d_x;
-    if (r0 != 0 || nr != n) {
-      OB_TRY(xc.alloc(nr * om.d));
-      OB_HIP(hipMemcpy2DAsync(xc.p, nr * sizeof(double), d_x + r0, n * sizeof(double), nr * sizeof(double), om.d,
-                              hipMemcpyDeviceToDevice, cur_stream()));
-      xsrc = xc.p;
-    }
-    BasisGuard g;
-    OB_TRY(obhip_basis_create_dev(&g.b, &om, xsrc, nr, t.maxlev.data()));
-    OB_TRY(Bcm.alloc(pp * npad));
+  DevBuf<double> Ycm;
+  return for_row_chunks(om, t, d_x, n, chunk_rows ? chunk_rows : default_chunk_rows(pp), pp,
+                        [&](uint64_t r0, uint64_t nr, uint64_t npad, const double *Bcm) -> int {
     OB_TRY(Ycm.alloc(pp * npad));
-    OB_HIP(hipMemsetAsync(Bcm.p, 0, pp * npad * sizeof(double), cur_stream()));
-    OB_TRY(launch_getmat(*g.b, t, Bcm.p, npad));  // B^T: term-major, rows contiguous
     {
       ProfScope ps("acquire_dx_product");
-      OB_TRY(launch_atb(kAtbStoreFixed, S, pp, pp, Bcm.p, npad, npad, pp, false, Ycm.p, npad));  // Y = S B^T
+      OB_TRY(launch_atb(kAtbStoreFixed, S, pp, pp, Bcm, npad, npad, pp, false, Ycm.p, npad));  // Y = S B^T
     }
     a.row0 = r0;
-    OB_TRY(launch_acquire_dx(om, t, crit, d_theta, Ycm.p, npad, d_x + r0, n, nr, a));
-    OB_HIP(hipStreamSynchronize(cur_stream()));  // the chunk's basis goes away
-  }
-  return 0;
+    return launch_acquire_dx(om, t, crit, d_theta, Ycm.p, npad, d_x + r0, n, nr, a);
+  });
 }
 
 AcqDxArgs criterion_args(const double *params, int maximize) {

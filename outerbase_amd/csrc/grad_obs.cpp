@@ -120,7 +120,7 @@ int obhip_design_dx_dev(const obhip_model *m, const obhip_terms *t, const double
   OB_TRY(check_compat(m, t));
   OB_TRY(check_grad_dims("design_dx_dev", m->d, dims, ndims, weights));
   if (ldo < t->p) return fail(OBHIP_ERR_INVALID, "design_dx_dev: ldo below the number of terms");
-  if (n > (1ull << 40)) return fail(OBHIP_ERR_INVALID, "design_dx_dev: more than 2^40 rows in one call");
+  if (n > kMaxRowsPerCall) return fail(OBHIP_ERR_INVALID, "design_dx_dev: more than 2^40 rows in one call");
   if (n == 0) return 0;
   OB_TRY(require_device());
   obhip_terms &tt = *const_cast<obhip_terms *>(t);

@@ -18,6 +18,7 @@
 #include <cmath>
 
 #include "obhip_internal.h"
+#include "acquire_device.h"
 
 namespace obhip {
 
@@ -41,25 +42,6 @@ __device__ __forceinline__ void wave_best(double &score, int64_t &idx) {
       idx = oi;
     }
   }
-}
-
-// the criterion at the signed mean ms and the latent variance d
-template <int CRIT>
-__device__ __forceinline__ double acq_score(double ms, double d, double best, double xi, double kappa, double level) {
-  const double sd = sqrt(fmax(d, 0.0));
-  if (CRIT == OBHIP_ACQ_LCB) return kappa * sd - ms;
-  if (CRIT == OBHIP_ACQ_STRADDLE) return kappa * sd - fabs(ms - level);
-  const double t = best - xi - ms;
-  if (!(sd > 0.0)) {
-    if (sd != sd || t != t) return NAN;
-    if (CRIT == OBHIP_ACQ_PI) return t > 0.0 ? 1.0 : 0.0;
-    return fmax(t, 0.0);
-  }
-  const double u = t / sd;
-  const double Phi = 0.5 * erfc(-u * 0.70710678118654752440);
-  if (CRIT == OBHIP_ACQ_PI) return Phi;
-  const double phi = exp(-0.5 * u * u) * 0.39894228040143267794;
-  return t * Phi + sd * phi;
 }
 
 template <int CRIT>

@@ -14,7 +14,7 @@
 //      order by wave l mod 8, which forms
 //        mu = s Sm    dmu/dx_l = s (rho_l Sm + gm)        d = s Sd    dd/dx_l = 2 s (rho_l Sd + gd)
 //      and, in FP64, d score / dx_l = A dmu~ + C dsd with dsd = dd / (2 sd) (0 where d <= 0) and the two
-//      coefficients A, C of the criterion (acq_coeffs), formed once per row and tile.
+//      coefficients A, C of the criterion (acq_eval), formed once per row and tile.
 // Every output is column-major n x d with leading dimension ldo, 512 contiguous bytes per (tile, dimension).
 // No atomics, a fixed summation order that does not depend on where a row stands: two runs give the same
 // bits, a chunked call those of the unchunked one, twin rows the same results.
@@ -25,6 +25,7 @@
 #include <cmath>
 
 #include "obhip_internal.h"
+#include "acquire_device.h"
 #include "device_dx.h"
 
 namespace obhip {
@@ -33,49 +34,6 @@ namespace {
 
 constexpr int kAdxThreads = 512, kAdxWaves = kAdxThreads / 64;
 constexpr int kAdxRedCols = 2 * 2 * kAdxWaves;  // [buffer][mean | variance][wave] columns of 64 partials
-
-// the score at the signed mean ms and the latent variance dv (kernels_acquire.hip's acq_score, formula for
-// formula) and the coefficients of its gradient: d score = A d(ms) + C d(sd)
-template <int CRIT>
-__device__ __forceinline__ double acq_coeffs(double ms, double dv, const AcqDxArgs &a, double &A, double &C) {
-  const double sd = sqrt(fmax(dv, 0.0));
-  if (CRIT == OBHIP_ACQ_LCB) {
-    A = -1.0;
-    C = a.kappa;
-    return a.kappa * sd - ms;
-  }
-  if (CRIT == OBHIP_ACQ_STRADDLE) {
-    const double df = ms - a.level;
-    A = df > 0.0 ? -1.0 : (df < 0.0 ? 1.0 : (df == 0.0 ? 0.0 : NAN));
-    C = a.kappa;
-    return a.kappa * sd - fabs(df);
-  }
-  const double t = a.best - a.xi - ms;
-  if (!(sd > 0.0)) {
-    C = 0.0;
-    if (sd != sd || t != t) {
-      A = C = NAN;
-      return NAN;
-    }
-    if (CRIT == OBHIP_ACQ_PI) {
-      A = 0.0;
-      return t > 0.0 ? 1.0 : 0.0;
-    }
-    A = t > 0.0 ? -1.0 : 0.0;
-    return fmax(t, 0.0);
-  }
-  const double u = t / sd;
-  const double Phi = 0.5 * erfc(-u * 0.70710678118654752440);
-  const double phi = exp(-0.5 * u * u) * 0.39894228040143267794;
-  if (CRIT == OBHIP_ACQ_PI) {
-    A = -phi / sd;
-    C = -(phi * u) / sd;
-    return Phi;
-  }
-  A = -Phi;
-  C = phi;
-  return t * Phi + sd * phi;
-}
 
 template <int W2, int CRIT, bool HBM>
 __global__ void __launch_bounds__(kAdxThreads)
@@ -146,7 +104,7 @@ k_acquire_dx(const DimDesc *__restrict__ dims, const double *__restrict__ ka, co
     const double mu = fin ? Sm * s : NAN, dv = fin ? Sd * s : NAN;
     double A = 0.0, C = 0.0, hsd = 0.0;  // hsd = 1 / (2 sd), 0 where d <= 0
     if constexpr (MEAN) {
-      const double sc = acq_coeffs<CRIT>(a.sgn * mu, dv, a, A, C);
+      const double sc = acq_eval<CRIT>(a.sgn * mu, dv, a.best, a.xi, a.kappa, a.level, A, C);
       const double sd = sqrt(fmax(dv, 0.0));
       hsd = sd > 0.0 ? 1.0 / (2.0 * sd) : (dv != dv ? NAN : 0.0);
       if (wave == 0 && valid) {

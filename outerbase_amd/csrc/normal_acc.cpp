@@ -203,7 +203,7 @@ int obhip_normal_acc_add_grad_dev(obhip_normal_acc *acc, const double *d_x, uint
     return fail(OBHIP_ERR_INVALID, "normal_acc_add_grad_dev: null accumulator, x, dims or dY, or a sign other than +1 / -1");
   OB_TRY(check_grad_dims("normal_acc_add_grad_dev", acc->model->d, dims, ndims, weights));
   if (lddy < n) return fail(OBHIP_ERR_INVALID, "normal_acc_add_grad_dev: lddy below the rows of the batch");
-  if (n > (1ull << 40)) return fail(OBHIP_ERR_INVALID, "normal_acc_add_grad_dev: more than 2^40 rows in one call");
+  if (n > kMaxRowsPerCall) return fail(OBHIP_ERR_INVALID, "normal_acc_add_grad_dev: more than 2^40 rows in one call");
   if (n == 0) return 0;
   OB_TRY(check_compat(acc->model, acc->terms));
   OB_TRY(check_version(acc, "normal_acc_add_grad_dev"));
@@ -244,7 +244,7 @@ int obhip_normal_acc_add_product_dev(obhip_normal_acc *acc, const double *d_xa, 
   if (na == 0 || nb == 0) return fail(OBHIP_ERR_INVALID, "normal_acc_add_product_dev: a grid batch needs rows on both sides");
   if (!d_xa || !d_xb || !d_Y_raw) return fail(OBHIP_ERR_INVALID, "normal_acc_add_product_dev: null xa, xb or Y");
   if (lda < na) return fail(OBHIP_ERR_INVALID, "normal_acc_add_product_dev: lda below na");
-  if (na > (1ull << 31) || nb > (1ull << 40) || na * nb > (1ull << 48))
+  if (na > (1ull << 31) || nb > kMaxRowsPerCall || na * nb > (1ull << 48))
     return fail(OBHIP_ERR_INVALID, "normal_acc_add_product_dev: more than 2^31 rows in xa, 2^40 in xb or 2^48 pairs");
   OB_TRY(check_compat(acc->model, acc->terms));
   OB_TRY(check_version(acc, "normal_acc_add_product_dev"));

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <ctime>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -506,6 +507,14 @@ struct obhip_basis {
 
 namespace obhip {
 
+// owns a basis that a call makes for itself
+struct BasisGuard {
+  obhip_basis *b = nullptr;
+  ~BasisGuard() { obhip_basis_destroy(b); }
+};
+// rows of one call that the entries with 64-bit row indices and 32-bit tile counts take
+constexpr uint64_t kMaxRowsPerCall = 1ull << 40;
+
 constexpr int kTileRows = 64;
 static_assert(kTileRows == kGramRowTile, "gram_plan.h sizes row chunks in these tiles");
 // LDS of a workgroup on gfx950: what the fused kernels size their tiles against
@@ -638,6 +647,9 @@ struct PostFactor {
   DevBuf<double> X;        // pp x pp row-major, upper triangle = L^-T, zero elsewhere
 };
 int post_factor_build(const double *d_H, uint64_t p, PostFactor &f, bool want_inverse);
+// S (pp x pp, allocated here) = inv(H) = X X^T of a factor built with its inverse; waits for it
+int post_factor_inverse(const PostFactor &f, DevBuf<double> &S);
+int factor_logdet(const PostFactor &f, double *logdet);  // log det H from the diagonal of L; waits
 int post_var_dev(const obhip_model &m, obhip_terms &t, const PostFactor &f, const double *d_x,
                  uint64_t n, double e2sigma, double *d_var);
 // obhip_margadj_full in its two parts, so that a row-sharded likelihood can sum the first over its ranks:
@@ -663,13 +675,17 @@ namespace obhip {
 // *out = a new handle that takes the symmetric p x p d_H over (copied); waits for the factorisation
 int posterior_from_hessian(obhip_posterior **out, const obhip_model *m, const obhip_terms *t, const double *d_H,
                            double sigma);
+// posterior.cpp: *S = the handle's inv(H), formed by post_factor_inverse on first use and read-only from then on:
+// launch_design_pspace downdates its S in place, so the selection entries work on a copy
+int posterior_inverse(const obhip_posterior &post, const double **S);
+// posterior.cpp: what the entries on a handle refuse, in the texts they have always had.  check_post_handle: a null
+// handle, check_compat, then p (cap_p: "... disagree on p (or p > 65535)", else "the terms changed since ...")
+int check_post_handle(const std::string &who, const obhip_posterior *post, bool cap_p);
+int check_acq_criterion(const std::string &who, int criterion);                        // the range
+int check_acq_params(const std::string &who, int criterion, const double *params);   // null, best, xi, kappa, level
 // design.cpp / kernels_design.hip: one greedy step of the sequential design over the candidates (fused: the
 // basis of a 64-row tile in LDS, a = B s and c = B h on the matrix cores, downdate, score and argmax in
 // the epilogue) and the p-space work between two steps
-struct BasisGuard {
-  obhip_basis *b = nullptr;
-  ~BasisGuard() { obhip_basis_destroy(b); }
-};
 // design.cpp: b_i^T Q b_i (norms false) or || X^T b_i ||^2 (norms true) at the n rows of d_x, a stored product
 // and one ascending sum per row.  fixed_order: the stored product by launch_atb's kAtbStoreFixed, and only then do
 // bit-identical rows get bit-identical results wherever they stand (without it: when their 128-row tiles of a
@@ -703,6 +719,29 @@ int launch_design_pick(const DesignStep &s, uint64_t nparts, uint64_t d, uint64_
 // then S -= s s^T / gamma and T -= (s h^T + h s^T) / gamma - s s^T tau / gamma^2
 int launch_design_pspace(int crit, uint64_t p, uint64_t pp, const double *d_b, double *d_S, double *d_T, double *d_sv,
                          double *d_hv, double *d_sh, double *d_scal, double *d_trace, uint64_t step);
+// design.cpp: the working set and the step loop that obhip_design_select_dev and obhip_acquire_dev share
+struct GreedyPicks {
+  obhip_terms *terms = nullptr;
+  uint64_t p = 0, pp = 0, d = 0;
+  DevBuf<double> S;        // pp x pp: a copy of the handle's inverse, downdated by every pick
+  DevBuf<double> vec;      // s | h, the two columns launch_design_pspace writes
+  DevBuf<double> sh;       // its [p][16] block
+  DevBuf<double> scal;     // the step's scalar block, seeded from scal0 by run
+  DevBuf<double> trace;    // k + 1
+  DevBuf<double> bj, xj0;  // the picked row's basis (p) and where the pick kernels gather its x (d)
+  DevBuf<double> pscore;   // nparts partial pairs
+  DevBuf<int64_t> pidx;
+  DevBuf<uint8_t> picked;  // m
+  BasisGuard one;          // the one-row basis b_j is evaluated with
+  std::vector<double> scal0;  // {1, 0, 0, nu, 0, ..}: gamma = 1, nothing to downdate; the entry may fill its own slots
+  // allocates, zeroes and seeds all of the above for m candidates, k picks, nscal scalars and nparts partials
+  int init(const obhip_posterior &post, const double *d_xcand, uint64_t m, uint64_t k, uint64_t nscal,
+           uint64_t nparts);
+  // k steps of pass(step), pick(step), the host wait for the nothing-left flag, b_j and the p-space kernels with
+  // the criterion and T (null: no h), then pass(npicked) for the last pick's downdate; *npicked <= k
+  int run(uint64_t k, int crit, double *d_T, const std::function<int(uint64_t)> &pass,
+          const std::function<int(uint64_t)> &pick, uint64_t *npicked);
+};
 // acquire.cpp / kernels_acquire.hip: acquisition picks (include/obhip.h, "acquisition picks")
 // the step's scalar block: the kDesignScal doubles launch_design_pspace writes, then delta = y* - mu_j and the
 // incumbent (in the sign the criterion is scored with)
@@ -737,8 +776,6 @@ struct AcqDxArgs {
   double *score = nullptr, *gradscore = nullptr;  // n, n x d: required with a criterion
   double *mean = nullptr, *gradmean = nullptr, *var = nullptr, *gradvar = nullptr;  // may be null
 };
-// *S = the handle's inv(H), formed on first use exactly as the design and acquisition entries form theirs
-int posterior_inverse(const obhip_posterior &post, const double **S);
 bool acquire_dx_fused(const obhip_terms &t);  // predict_dx_supports and no OBHIP_FORCE_GENERIC
 uint64_t acquire_dx_lds_bytes(const obhip_terms &t, uint64_t d, bool fused);
 // one chunk: the n rows at d_x (column-major, leading dimension ldx) against their stored product d_Y = S B^T

@@ -17,12 +17,12 @@
 #include <cstring>
 
 #include "obhip_internal.h"
+#include "row_chunks.h"
 #include "vec_ops.h"
 
 using namespace obhip;
 
 namespace obhip {
-static uint64_t pad128(uint64_t v) { return (v + 127) / 128 * 128; }
 
 // f.L = Cholesky factor of H (lower triangle, row-major p x p), f.X = L^-T (pp x pp)
 int post_factor_build(const double *d_H, uint64_t p, PostFactor &f, bool want_inverse) {
@@ -53,43 +53,86 @@ int post_var_dev(const obhip_model &m, obhip_terms &t, const PostFactor &f, cons
   const uint64_t p = f.p, pp = f.pp;
   if (t.p != p) return fail(OBHIP_ERR_INVALID, "posterior factor and terms disagree on p");
   // row chunks so that the term-major design matrix (pp x rows doubles) stays below 8 GB
-  const uint64_t cmax = std::max<uint64_t>(128, ((8ull << 30) / (pp * sizeof(double))) / 128 * 128);
   const uint64_t ntj = pp / 128;
-  DevBuf<double> Bcm, part;
-  for (uint64_t r0 = 0; r0 < n; r0 += cmax) {
-    const uint64_t nr = std::min(cmax, n - r0), npad = pad128(nr);
-    obhip_basis *b = nullptr;
-    // the chunk's rows of x: column-major with leading dimension n -> gather into a compact copy
-    DevBuf<double> xc;
-    const double *xsrc = d_x;
-    if (r0 != 0 || nr != n) {
-      OB_TRY(xc.alloc(nr * m.d));
-      OB_HIP(hipMemcpy2DAsync(xc.p, nr * sizeof(double), d_x + r0, n * sizeof(double),
-                              nr * sizeof(double), m.d, hipMemcpyDeviceToDevice, cur_stream()));
-      xsrc = xc.p;
-    }
-    OB_TRY(obhip_basis_create_dev(&b, &m, xsrc, nr, t.maxlev.data()));
-    struct Guard {
-      obhip_basis *b;
-      ~Guard() { obhip_basis_destroy(b); }
-    } guard{b};
-    OB_TRY(Bcm.alloc(pp * npad));
+  DevBuf<double> part;
+  return for_row_chunks(m, t, d_x, n, chunk_rows_for(pp, 8ull << 30), pp,
+                        [&](uint64_t r0, uint64_t nr, uint64_t npad, const double *Bcm) -> int {
     OB_TRY(part.alloc(ntj * npad));
-    OB_HIP(hipMemsetAsync(Bcm.p, 0, pp * npad * sizeof(double), cur_stream()));
-    OB_TRY(launch_getmat(*b, t, Bcm.p, npad));  // B^T: term-major, rows contiguous
     {
       ProfScope ps("predict_std_gemm");
-      OB_TRY(launch_atb(kAtbNorm, Bcm.p, npad, npad, f.X.p, pp, pp, pp, true, part.p, npad));
+      OB_TRY(launch_atb(kAtbNorm, Bcm, npad, npad, f.X.p, pp, pp, pp, true, part.p, npad));
     }
     const double *pt = part.p;
     double *out = d_var + r0;
-    OB_TRY(vmap(nr, [=] __device__(uint64_t i) {
+    return vmap(nr, [=] __device__(uint64_t i) {
       double s = e2sigma;
       for (uint64_t j = 0; j < ntj; ++j) s += pt[j * npad + i];
       out[i] = s;
-    }));
-    OB_HIP(hipStreamSynchronize(cur_stream()));
+    });
+  });
+}
+
+// inv(H) = L^-T L^-1 = Linv^T Linv with Linv = X^T (row-major, k slow): one Gram-shaped product
+int post_factor_inverse(const PostFactor &f, DevBuf<double> &S) {
+  const uint64_t p = f.p, pp = f.pp;
+  DevBuf<double> Linv;
+  OB_TRY(S.alloc(pp * pp));
+  OB_TRY(Linv.alloc(pp * pp));
+  OB_HIP(hipMemsetAsync(Linv.p, 0, pp * pp * sizeof(double), cur_stream()));
+  OB_TRY(launch_transpose(f.X.p, pp, Linv.p, pp, p));
+  OB_TRY(launch_atb(kAtbStore, Linv.p, pp, pp, Linv.p, pp, pp, pp, false, S.p, pp));
+  OB_HIP(hipStreamSynchronize(cur_stream()));  // Linv is a local
+  return 0;
+}
+
+int posterior_inverse(const obhip_posterior &post, const double **S) {
+  std::lock_guard<std::mutex> g(post.S_lock);
+  if (!post.S.p) {
+    const int rc = post_factor_inverse(post.f, post.S);
+    if (rc) {
+      post.S.release();  // never a half-formed inverse on the handle
+      return rc;
+    }
   }
+  *S = post.S.p;
+  return 0;
+}
+
+int factor_logdet(const PostFactor &f, double *logdet) {
+  const uint64_t p = f.p;
+  std::vector<double> ld(p);
+  OB_HIP(hipMemcpy2DAsync(ld.data(), sizeof(double), f.L.p, (p + 1) * sizeof(double), sizeof(double), p,
+                          hipMemcpyDeviceToHost, cur_stream()));
+  OB_HIP(hipStreamSynchronize(cur_stream()));
+  *logdet = 0;
+  for (double v : ld) *logdet += 2.0 * std::log(v);
+  return 0;
+}
+
+int check_post_handle(const std::string &who, const obhip_posterior *post, bool cap_p) {
+  if (!post) return fail(OBHIP_ERR_INVALID, who + ": null posterior");
+  OB_TRY(check_compat(post->model, post->terms));
+  if (cap_p && (post->terms->p != post->p || post->p > 65535))
+    return fail(OBHIP_ERR_INVALID, who + ": the posterior and its terms disagree on p (or p > 65535)");
+  if (post->terms->p != post->p) return fail(OBHIP_ERR_INVALID, who + ": the terms changed since the handle was made");
+  return 0;
+}
+
+int check_acq_criterion(const std::string &who, int criterion) {
+  if (criterion < OBHIP_ACQ_EI || criterion > OBHIP_ACQ_STRADDLE)
+    return fail(OBHIP_ERR_INVALID, who + ": criterion must be OBHIP_ACQ_EI, _PI, _LCB or _STRADDLE");
+  return 0;
+}
+
+int check_acq_params(const std::string &who, int criterion, const double *params) {
+  if (!params) return fail(OBHIP_ERR_INVALID, who + ": params (best, xi, kappa, level) is null");
+  if ((criterion == OBHIP_ACQ_EI || criterion == OBHIP_ACQ_PI) && !std::isfinite(params[0]))
+    return fail(OBHIP_ERR_INVALID, who + ": best must be finite for EI and PI");
+  if (!std::isfinite(params[1])) return fail(OBHIP_ERR_INVALID, who + ": xi must be finite");
+  if (!std::isfinite(params[2]) || params[2] < 0.0)
+    return fail(OBHIP_ERR_INVALID, who + ": kappa must be finite and >= 0");
+  if (criterion == OBHIP_ACQ_STRADDLE && !std::isfinite(params[3]))
+    return fail(OBHIP_ERR_INVALID, who + ": level must be finite for STRADDLE");
   return 0;
 }
 
@@ -154,23 +197,14 @@ int obhip::margadj_full_parts(const obhip_basis *bc, const obhip_terms *tc, cons
   OB_TRY(dH.upload(H, p * p));
   PostFactor f;
   OB_TRY(post_factor_build(dH.p, p, f, grads));
-  std::vector<double> ld(p);
-  OB_HIP(hipMemcpy2DAsync(ld.data(), sizeof(double), f.L.p, (p + 1) * sizeof(double), sizeof(double), p,
-                          hipMemcpyDeviceToHost, cur_stream()));
-  OB_HIP(hipStreamSynchronize(cur_stream()));
   double logdet = 0;
-  for (double v : ld) logdet += 2.0 * std::log(v);
+  OB_TRY(factor_logdet(f, &logdet));
   *val = -0.5 * logdet;
   if (!grads) return 0;
 
-  // inv(H) = L^-T L^-1 = Linv^T Linv with Linv = X^T (row-major, k slow): one Gram-shaped product
   const uint64_t pp = f.pp, npad = pad128(b.n);
-  DevBuf<double> Linv, Hinv;
-  OB_TRY(Linv.alloc(pp * pp));
-  OB_TRY(Hinv.alloc(pp * pp));
-  OB_HIP(hipMemsetAsync(Linv.p, 0, pp * pp * sizeof(double), cur_stream()));
-  OB_TRY(launch_transpose(f.X.p, pp, Linv.p, pp, p));
-  OB_TRY(launch_atb(kAtbStore, Linv.p, pp, pp, Linv.p, pp, pp, pp, false, Hinv.p, pp));
+  DevBuf<double> Hinv;
+  OB_TRY(post_factor_inverse(f, Hinv));
   std::vector<double> hinv(p);  // diag(inv(H))
   OB_HIP(hipMemcpy2DAsync(hinv.data(), sizeof(double), Hinv.p, (pp + 1) * sizeof(double),
                           sizeof(double), p, hipMemcpyDeviceToHost, cur_stream()));
@@ -231,13 +265,7 @@ int posterior_from_hessian(obhip_posterior **out, const obhip_model *m, const ob
   OB_TRY(q->H.alloc(p * p));
   OB_HIP(hipMemcpyAsync(q->H.p, d_H, p * p * sizeof(double), hipMemcpyDeviceToDevice, cur_stream()));
   OB_TRY(post_factor_build(q->H.p, p, q->f, true));  // OBHIP_ERR_NUMERIC: not positive definite
-  std::vector<double> ld(p);
-  OB_HIP(hipMemcpy2DAsync(ld.data(), sizeof(double), q->f.L.p, (p + 1) * sizeof(double), sizeof(double), p,
-                          hipMemcpyDeviceToHost, cur_stream()));
-  OB_HIP(hipStreamSynchronize(cur_stream()));
-  double logdet = 0;
-  for (double v : ld) logdet += 2.0 * std::log(v);
-  q->logdet = logdet;
+  OB_TRY(factor_logdet(q->f, &q->logdet));
   *out = q.release();
   return 0;
 }
@@ -269,8 +297,7 @@ extern "C" int obhip_posterior_info(const obhip_posterior *post, uint64_t *p, do
 extern "C" int obhip_posterior_var_dev(const obhip_posterior *post, const double *d_x, uint64_t n, double *d_var,
                                        int with_noise) {
   if (!post || (n != 0 && (!d_x || !d_var))) return fail(OBHIP_ERR_INVALID, "posterior_var_dev: null argument");
-  OB_TRY(check_compat(post->model, post->terms));
-  if (post->terms->p != post->p) return fail(OBHIP_ERR_INVALID, "posterior_var_dev: the terms changed since the handle was made");
+  OB_TRY(check_post_handle("posterior_var_dev", post, false));
   OB_TRY(require_device());
   if (n == 0) return 0;
   return post_var_dev(*post->model, *const_cast<obhip_terms *>(post->terms), post->f, d_x, n,
@@ -280,21 +307,15 @@ extern "C" int obhip_posterior_var_dev(const obhip_posterior *post, const double
 extern "C" int obhip_posterior_condition_dev(const obhip_posterior *post, const double *d_x, uint64_t n,
                                              obhip_posterior **out) {
   if (!post || !out || !d_x || n == 0) return fail(OBHIP_ERR_INVALID, "posterior_condition_dev: bad argument");
-  OB_TRY(check_compat(post->model, post->terms));
-  if (post->terms->p != post->p)
-    return fail(OBHIP_ERR_INVALID, "posterior_condition_dev: the terms changed since the handle was made");
+  OB_TRY(check_post_handle("posterior_condition_dev", post, false));
   OB_TRY(require_device());
   obhip_terms &t = *const_cast<obhip_terms *>(post->terms);
   const uint64_t p = post->p;
-  obhip_basis *b = nullptr;
-  OB_TRY(obhip_basis_create_dev(&b, post->model, d_x, n, t.maxlev.data()));
-  struct Guard {
-    obhip_basis *b;
-    ~Guard() { obhip_basis_destroy(b); }
-  } guard{b};
+  BasisGuard b;
+  OB_TRY(obhip_basis_create_dev(&b.b, post->model, d_x, n, t.maxlev.data()));
   DevBuf<double> G;
   OB_TRY(G.alloc(p * p));
-  OB_TRY(launch_gram(*b, t, G.p));
+  OB_TRY(launch_gram(*b.b, t, G.p));
   const double e2 = std::exp(-2.0 * post->sigma);
   const double *H = post->H.p;
   double *g = G.p;

@@ -17,7 +17,6 @@ namespace obhip {
 
 // rows one call takes: the view offsets and tile counts of the kernel are 64-bit, the bound keeps
 // n * d * 8 bytes far inside the address space
-constexpr uint64_t kDxMaxRows = 1ull << 40;
 
 void build_dim_views_host(obhip_terms &t) {
   if (t.dx.voff.size() == t.d + 1) return;
@@ -146,7 +145,7 @@ int obhip_predict_grad_dev(const obhip_model *m, const obhip_terms *t, const dou
   if (!m || !t || !d_theta || !d_grad || (!d_x && n > 0))
     return fail(OBHIP_ERR_INVALID, "predict_grad_dev: null model, terms, theta, x or grad");
   if (d_gradvar && !d_coeffvar) return fail(OBHIP_ERR_INVALID, "predict_grad_dev: gradvar needs coeffvar");
-  if (n > kDxMaxRows) return fail(OBHIP_ERR_INVALID, "predict_grad_dev: more than 2^40 rows in one call");
+  if (n > kMaxRowsPerCall) return fail(OBHIP_ERR_INVALID, "predict_grad_dev: more than 2^40 rows in one call");
   OB_TRY(check_compat(m, t));
   if (n == 0) return 0;
   OB_TRY(require_device());
@@ -160,7 +159,7 @@ int obhip_predict_grad(const obhip_model *m, const obhip_terms *t, const double 
   if (!m || !t || !theta || !grad || (!x && n > 0))
     return fail(OBHIP_ERR_INVALID, "predict_grad: null model, terms, theta, x or grad");
   if (gradvar && !coeffvar) return fail(OBHIP_ERR_INVALID, "predict_grad: gradvar needs coeffvar");
-  if (n > kDxMaxRows) return fail(OBHIP_ERR_INVALID, "predict_grad: more than 2^40 rows in one call");
+  if (n > kMaxRowsPerCall) return fail(OBHIP_ERR_INVALID, "predict_grad: more than 2^40 rows in one call");
   if (ldx < n || ldg < n) return fail(OBHIP_ERR_INVALID, "predict_grad: leading dimension below n");
   OB_TRY(check_compat(m, t));
   if (n == 0) return 0;

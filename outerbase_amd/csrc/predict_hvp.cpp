@@ -15,7 +15,6 @@ using namespace obhip;
 namespace obhip {
 
 namespace {
-constexpr uint64_t kHvpMaxRows = 1ull << 40;  // as obhip_predict_grad_dev
 }
 
 // Second-derivative interval tables, beside build_dx_tables_host (predict_dx.cpp): per interval J of
@@ -98,7 +97,7 @@ static int check_hvp(const char *who, const void *m, const void *t, const void *
   if (!m || !t || !Theta || (n > 0 && (!x || !V))) return fail(OBHIP_ERR_INVALID, w + ": null model, terms, Theta, x or V");
   if (q == 0) return fail(OBHIP_ERR_INVALID, w + ": no response");
   if (W && ldw < n) return fail(OBHIP_ERR_INVALID, w + ": leading dimension of W below n");
-  if (n > kHvpMaxRows) return fail(OBHIP_ERR_INVALID, w + ": more than 2^40 rows in one call");
+  if (n > kMaxRowsPerCall) return fail(OBHIP_ERR_INVALID, w + ": more than 2^40 rows in one call");
   if (!jvp && !hvp) return fail(OBHIP_ERR_INVALID, w + ": neither jvp nor hvp is asked for");
   if ((vjp || hvp) && !W) return fail(OBHIP_ERR_INVALID, w + ": vjp and hvp need W");
   return 0;

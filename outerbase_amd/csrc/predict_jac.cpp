@@ -7,7 +7,6 @@
 using namespace obhip;
 
 namespace {
-constexpr uint64_t kJacMaxRows = 1ull << 40;  // as obhip_predict_grad_dev
 }
 
 extern "C" {
@@ -16,7 +15,7 @@ int obhip_predict_jac_multi_dev(const obhip_model *m, const obhip_terms *t, cons
                                 const double *d_x, uint64_t n, double *d_mean, double *d_jac) {
   if (!m || !t || !d_Theta || !d_x || !d_jac || q == 0)
     return fail(OBHIP_ERR_INVALID, "predict_jac_multi_dev: null model, terms, Theta, x or jac, or no response");
-  if (n > kJacMaxRows) return fail(OBHIP_ERR_INVALID, "predict_jac_multi_dev: more than 2^40 rows in one call");
+  if (n > kMaxRowsPerCall) return fail(OBHIP_ERR_INVALID, "predict_jac_multi_dev: more than 2^40 rows in one call");
   OB_TRY(check_compat(m, t));
   if (n == 0) return 0;
   OB_TRY(require_device());
@@ -30,7 +29,7 @@ int obhip_predict_vjp_multi_dev(const obhip_model *m, const obhip_terms *t, cons
   if (!m || !t || !d_Theta || !d_x || !d_W || !d_out || q == 0)
     return fail(OBHIP_ERR_INVALID, "predict_vjp_multi_dev: null model, terms, Theta, x, W or out, or no response");
   if (ldw < n) return fail(OBHIP_ERR_INVALID, "predict_vjp_multi_dev: leading dimension of W below n");
-  if (n > kJacMaxRows) return fail(OBHIP_ERR_INVALID, "predict_vjp_multi_dev: more than 2^40 rows in one call");
+  if (n > kMaxRowsPerCall) return fail(OBHIP_ERR_INVALID, "predict_vjp_multi_dev: more than 2^40 rows in one call");
   OB_TRY(check_compat(m, t));
   if (n == 0) return 0;
   OB_TRY(require_device());
@@ -41,7 +40,7 @@ int obhip_predict_jac_multi(const obhip_model *m, const obhip_terms *t, const do
                             const double *x, uint64_t n, uint64_t ldx, double *mean, double *jac) {
   if (!m || !t || !Theta || !x || !jac || q == 0)
     return fail(OBHIP_ERR_INVALID, "predict_jac_multi: null model, terms, Theta, x or jac, or no response");
-  if (n > kJacMaxRows) return fail(OBHIP_ERR_INVALID, "predict_jac_multi: more than 2^40 rows in one call");
+  if (n > kMaxRowsPerCall) return fail(OBHIP_ERR_INVALID, "predict_jac_multi: more than 2^40 rows in one call");
   if (ldx < n) return fail(OBHIP_ERR_INVALID, "predict_jac_multi: leading dimension below n");
   OB_TRY(check_compat(m, t));
   if (n == 0) return 0;

@@ -137,7 +137,7 @@ int obhip_product_side_dev(const obhip_model *m, const obhip_terms *t, const uin
   if (side != 0 && side != 1) return fail(OBHIP_ERR_INVALID, "product_side_dev: side must be 0 (A) or 1 (B)");
   if (pitch < t->p) return fail(OBHIP_ERR_INVALID, "product_side_dev: pitch below the number of terms");
   OB_TRY(check_side_columns("product_side_dev", s));
-  if (n > (1ull << 40)) return fail(OBHIP_ERR_INVALID, "product_side_dev: more than 2^40 rows in one call");
+  if (n > kMaxRowsPerCall) return fail(OBHIP_ERR_INVALID, "product_side_dev: more than 2^40 rows in one call");
   if (n == 0) return 0;
   if (!d_x || !d_out) return fail(OBHIP_ERR_INVALID, "product_side_dev: null x or out");
   OB_TRY(require_device());

@@ -21,6 +21,7 @@
 #include <cmath>
 
 #include "obhip_internal.h"
+#include "row_chunks.h"
 
 using namespace obhip;
 
@@ -33,9 +34,7 @@ int check_draws(const char *who, const obhip_posterior *post, const void *theta,
   if (S == 0) return fail(OBHIP_ERR_INVALID, w + ": S = 0, no draws asked for");
   if (!theta) return fail(OBHIP_ERR_INVALID, w + ": d_theta is null");
   if (!z) return fail(OBHIP_ERR_INVALID, w + ": d_z is null");
-  if (!post) return fail(OBHIP_ERR_INVALID, w + ": null posterior");
-  OB_TRY(check_compat(post->model, post->terms));
-  if (post->terms->p != post->p) return fail(OBHIP_ERR_INVALID, w + ": the terms changed since the handle was made");
+  OB_TRY(check_post_handle(w, post, false));
   if (ldz < post->p) return fail(OBHIP_ERR_INVALID, w + ": ldz < p");
   return 0;
 }
@@ -125,25 +124,21 @@ extern "C" int obhip_posterior_extremum_dev(const obhip_posterior *post, const d
   // the unfused route: row chunks so that the paths of 64 draws stay within 1 GiB of scratch
   const uint64_t cmax = (1ull << 30) / (kDrawChunk * sizeof(double));  // a multiple of kColextRows
   const uint64_t nparts = (m + kColextRows - 1) / kColextRows, rows = std::min(m, cmax);
+  const RowChunks chunks{m, cmax};
   DevBuf<double> Theta, path, xc;
   OB_TRY(Theta.alloc(p * kDrawChunk));
   OB_TRY(path.alloc(rows * kDrawChunk));
   OB_TRY(pkey.alloc(nparts * kDrawChunk));
   OB_TRY(pidx.alloc(nparts * kDrawChunk));
-  if (m > cmax) OB_TRY(xc.alloc(rows * d));
   for (uint64_t s0 = 0; s0 < S; s0 += kDrawChunk) {
     const int qc = (int)std::min(kDrawChunk, S - s0);
     OB_TRY(launch_draw(post->f, d_theta, d_z + s0 * ldz, ldz, qc, 0, nullptr, Theta.p));
-    for (uint64_t r0 = 0; r0 < m; r0 += cmax) {
-      const uint64_t nr = std::min(cmax, m - r0);
-      const double *xsrc = d_xcand;
-      if (m > cmax) {  // the chunk's rows of x: leading dimension m -> a compact copy
-        OB_HIP(hipMemcpy2DAsync(xc.p, nr * sizeof(double), d_xcand + r0, m * sizeof(double), nr * sizeof(double), d,
-                                hipMemcpyDeviceToDevice, cur_stream()));
-        xsrc = xc.p;
-      }
-      OB_TRY(sample_paths(om, t, Theta.p, (uint64_t)qc, xsrc, nr, path.p));
-      OB_TRY(launch_sample_colext(path.p, nr, nr, r0, qc, elig.p, sgn, kDrawChunk, pkey.p, pidx.p));
+    for (uint64_t ci = 0; ci < chunks.count(); ++ci) {
+      const RowChunk c = chunks.at(ci);
+      const double *xsrc = nullptr;
+      OB_TRY(gather_rows(xc, d_xcand, m, d, c, &xsrc));
+      OB_TRY(sample_paths(om, t, Theta.p, (uint64_t)qc, xsrc, c.nr, path.p));
+      OB_TRY(launch_sample_colext(path.p, c.nr, c.nr, c.r0, qc, elig.p, sgn, kDrawChunk, pkey.p, pidx.p));
     }
     OB_TRY(launch_sample_pick(pkey.p, pidx.p, nparts, kDrawChunk, qc, sgn, d_index + s0, d_value + s0));
   }

@@ -12,7 +12,6 @@ using namespace obhip;
 
 namespace {
 
-constexpr uint64_t kSobolMaxRows = 1ull << 40;
 constexpr uint64_t kSobolMaxQ = 65535;  // a grid dimension of the per-response kernels
 
 struct Layout {
@@ -58,7 +57,7 @@ int check_q(const char *who, uint64_t q) {
 int check_nodes(const char *who, uint64_t n, uint64_t ldx, bool weights, uint64_t ldw) {
   const std::string w(who);
   if (n == 0) return fail(OBHIP_ERR_INVALID, w + ": no nodes, so no measure");
-  if (n > kSobolMaxRows) return fail(OBHIP_ERR_INVALID, w + ": more than 2^40 nodes in one call");
+  if (n > kMaxRowsPerCall) return fail(OBHIP_ERR_INVALID, w + ": more than 2^40 nodes in one call");
   if (ldx < n) return fail(OBHIP_ERR_INVALID, w + ": leading dimension of the nodes below n");
   if (weights && ldw < n) return fail(OBHIP_ERR_INVALID, w + ": leading dimension of the weights below n");
   return 0;
@@ -404,7 +403,7 @@ int obhip_main_effect_dev(const obhip_model *m, const obhip_terms *t, uint64_t d
   if (!m || !t || !d_g || !d_grid || !d_out)
     return fail(OBHIP_ERR_INVALID, "main_effect_dev: null model, terms, g, grid or out");
   OB_TRY(check_q("main_effect_dev", q));
-  if (G > kSobolMaxRows) return fail(OBHIP_ERR_INVALID, "main_effect_dev: more than 2^40 grid points in one call");
+  if (G > kMaxRowsPerCall) return fail(OBHIP_ERR_INVALID, "main_effect_dev: more than 2^40 grid points in one call");
   OB_TRY(check_compat(m, t));
   if (dim >= m->d) return fail(OBHIP_ERR_INVALID, "main_effect_dev: dimension out of range");
   Layout lay;

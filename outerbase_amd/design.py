@@ -258,8 +258,6 @@ class Posterior:
         so the picks do not move.  -> AcquireResult"""
         import torch
         self._need()
-        if criterion not in ACQUISITIONS:
-            raise ValueError("criterion must be one of %s" % sorted(ACQUISITIONS))
         if lie not in LIES:
             raise ValueError("lie must be one of %s" % sorted(LIES))
         xcand = _rows(self.om, xcand, "xcand")
@@ -269,27 +267,16 @@ class Posterior:
         theta = np.ascontiguousarray(theta, dtype=np.float64)
         if theta.shape != (self.p,):
             raise ValueError("theta must be the p standardised coefficients of one response")
-        if criterion in ("ei", "pi") and best is None:
-            raise ValueError("criterion %r needs best, the incumbent" % criterion)
-        if criterion == "straddle" and level is None:
-            raise ValueError("criterion 'straddle' needs level")
         if lie == "constant" and lie_value is None:
-            if criterion not in ("ei", "pi"):
+            if criterion in ACQUISITIONS and criterion not in ("ei", "pi"):
                 raise ValueError("lie='constant' needs lie_value")
-            lie_value = best
-        best, level = 0.0 if best is None else float(best), 0.0 if level is None else float(level)
-        lie_value, kappa, xi = 0.0 if lie_value is None else float(lie_value), float(kappa), float(xi)
-        if not all(np.isfinite(v) for v in (best, level, lie_value, xi)):
-            raise ValueError("best, level, lie_value and xi must be finite")
-        if not (np.isfinite(kappa) and kappa >= 0):
-            raise ValueError("kappa must be finite and >= 0")
+            lie_value = best                                     # (None: refused below, ei and pi need best)
         if skip is not None:
             skip = np.ascontiguousarray(np.asarray(skip) != 0, dtype=np.uint8)
             if skip.shape != (m,):
                 raise ValueError("skip must have one entry per candidate")
-        sc = self._scale(response)
-        if sc is not None:                                       # raw units -> standardised
-            best, level, lie_value, xi = (best - sc[0]) / sc[1], (level - sc[0]) / sc[1], (lie_value - sc[0]) / sc[1], xi / sc[1]
+        pars, lie_value, sc = self._acquire_args(criterion, best, level, kappa, xi, response,
+                                                 0.0 if lie_value is None else lie_value)
         dev = _stream()
         f64, nan = torch.float64, float("nan")
         dx = _dev_cols(xcand, dev)
@@ -298,7 +285,7 @@ class Posterior:
         index = torch.full((k,), -1, dtype=torch.int64, device=dev)
         score = torch.full((k,), nan, dtype=f64, device=dev)
         score0, mean, var = (torch.full((m,), nan, dtype=f64, device=dev) for _ in range(3))
-        params = (C.c_double * 4)(best, xi, kappa, level)
+        params = (C.c_double * 4)(*pars)
         npk = C.c_uint64(0)
         call("obhip_acquire_dev", self._h, dth.data_ptr(), dx.data_ptr(), m, ACQUISITIONS[criterion], params,
              int(bool(maximize)), LIES[lie], lie_value, None if dk is None else dk.data_ptr(), k, index.data_ptr(),
@@ -306,14 +293,7 @@ class Posterior:
         torch.cuda.synchronize()
         n = npk.value
         score, score0, mean, var = (a.cpu().numpy() for a in (score, score0, mean, var))
-        score = score[:n].copy()
-        if sc is not None:
-            mean, var = sc[0] + sc[1] * mean, sc[1] ** 2 * var
-            if criterion in ("ei", "straddle"):
-                score, score0 = sc[1] * score, sc[1] * score0
-            elif criterion == "lcb":                             # kappa sd - mu: the centre comes back with the sign of -mu
-                off = sc[0] if maximize else -sc[0]
-                score, score0 = sc[1] * score + off, sc[1] * score0 + off
+        mean, var, (score, score0) = self._acquire_raw(sc, criterion, maximize, mean, var, score[:n].copy(), score0)
         return AcquireResult(index=index.cpu().numpy()[:n].copy(), score=score, score0=score0, mean=mean, var=var,
                              criterion=criterion, n_picked=n, k=k)
 
@@ -348,8 +328,9 @@ class Posterior:
         torch.cuda.synchronize()
         return var.cpu().numpy(), grad.cpu().numpy().T.copy()
 
-    def _acquire_grad_args(self, criterion, best, level, kappa, xi, response):
-        """the criterion's parameters, checked and standardised: (best, xi, kappa, level), (centre, scale) or None"""
+    def _acquire_args(self, criterion, best, level, kappa, xi, response, lie_value=None):
+        """the criterion's parameters (and acquire's lie_value), checked and standardised:
+        (best, xi, kappa, level), lie_value, (centre, scale) or None"""
         if criterion not in ACQUISITIONS:
             raise ValueError("criterion must be one of %s" % sorted(ACQUISITIONS))
         if criterion in ("ei", "pi") and best is None:
@@ -357,15 +338,27 @@ class Posterior:
         if criterion == "straddle" and level is None:
             raise ValueError("criterion 'straddle' needs level")
         best, level = 0.0 if best is None else float(best), 0.0 if level is None else float(level)
-        kappa, xi = float(kappa), float(xi)
-        if not all(np.isfinite(v) for v in (best, level, xi)):
-            raise ValueError("best, level and xi must be finite")
+        kappa, xi, lie = float(kappa), float(xi), 0.0 if lie_value is None else float(lie_value)
+        if not all(np.isfinite(v) for v in (best, level, lie, xi)):
+            raise ValueError("best, level%s and xi must be finite" % ("" if lie_value is None else ", lie_value"))
         if not (np.isfinite(kappa) and kappa >= 0):
             raise ValueError("kappa must be finite and >= 0")
         sc = self._scale(response)
         if sc is not None:                                       # raw units -> standardised
-            best, level, xi = (best - sc[0]) / sc[1], (level - sc[0]) / sc[1], xi / sc[1]
-        return (best, xi, kappa, level), sc
+            best, level, lie, xi = (best - sc[0]) / sc[1], (level - sc[0]) / sc[1], (lie - sc[0]) / sc[1], xi / sc[1]
+        return (best, xi, kappa, level), lie, sc
+
+    @staticmethod
+    def _acquire_raw(sc, criterion, maximize, mean, var, *scores):
+        """standardised -> raw units of the response with (centre, scale) sc: -> (mean, var, scores); pi has no unit"""
+        if sc is None:
+            return mean, var, scores
+        if criterion in ("ei", "straddle"):
+            scores = [sc[1] * s for s in scores]
+        elif criterion == "lcb":                                 # kappa sd - mu: the centre comes back with the sign of -mu
+            off = sc[0] if maximize else -sc[0]
+            scores = [sc[1] * s + off for s in scores]
+        return sc[0] + sc[1] * mean, sc[1] ** 2 * var, scores
 
     def acquire_grad(self, x, theta, criterion="ei", best=None, level=None, kappa=1.96, xi=0.0, maximize=False,
                      response=None, chunk_rows=0):
@@ -399,7 +392,7 @@ class Posterior:
         theta = np.ascontiguousarray(theta, dtype=np.float64)
         if theta.shape != (self.p,):
             raise ValueError("theta must be the p standardised coefficients of one response")
-        pars, sc = self._acquire_grad_args(criterion, best, level, kappa, xi, response)
+        pars, _, sc = self._acquire_args(criterion, best, level, kappa, xi, response)
         n, d = x.shape
         if n == 0:
             z1, z2 = np.zeros(0), np.zeros((0, d))
@@ -416,12 +409,11 @@ class Posterior:
         torch.cuda.synchronize()
         score, mean, var = (a.cpu().numpy() for a in (score, mean, var))
         grad, gmean, gvar = (a.cpu().numpy().T.copy() for a in (grad, gmean, gvar))
-        if sc is not None:
-            mean, gmean, var, gvar = sc[0] + sc[1] * mean, sc[1] * gmean, sc[1] ** 2 * var, sc[1] ** 2 * gvar
-            if criterion in ("ei", "straddle"):
-                score, grad = sc[1] * score, sc[1] * grad
-            elif criterion == "lcb":                             # kappa sd - mu: the centre comes back with the sign of -mu
-                score, grad = sc[1] * score + (sc[0] if maximize else -sc[0]), sc[1] * grad
+        mean, var, (score,) = self._acquire_raw(sc, criterion, maximize, mean, var, score)
+        if sc is not None:                                       # the gradients take the scales, not the centre
+            gmean, gvar = sc[1] * gmean, sc[1] ** 2 * gvar
+            if criterion != "pi":
+                grad = sc[1] * grad
         return AcquireGradResult(score=score, grad=grad, mean=mean, grad_mean=gmean, var=var, grad_var=gvar,
                                  criterion=criterion)
 

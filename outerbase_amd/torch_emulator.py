@@ -222,7 +222,7 @@ else:
             theta = np.ascontiguousarray(theta, dtype=np.float64)
             if theta.shape != (post.p,):
                 raise ValueError("theta must be the p standardised coefficients of one response")
-            self._params, _ = post._acquire_grad_args(criterion, best, level, kappa, xi, None)
+            self._params, _, _ = post._acquire_args(criterion, best, level, kappa, xi, None)
             self._post, self._crit, self._maximize = post, design.ACQUISITIONS[criterion], int(bool(maximize))
             self._chunk_rows = post._chunk_rows(chunk_rows)
             self.criterion, self.d = criterion, int(post.om.d)

@@ -408,3 +408,33 @@ def test_refused_calls_change_nothing_and_select_is_what_it_was():
         assert lib.obhip_posterior_var_grad_dev(post._h, None, 0, 0, 0, None, None) == 0
         torch.cuda.synchronize()
         assert bool(torch.isnan(a).all())
+
+
+def test_the_cached_inverse_is_never_downdated_and_the_copy_is_the_fresh_product():
+    """d5 p=130 n = m = 300: pp = 256, so the padding of S is live, and 300 rows are three 128-row tiles, the last
+    ragged.  Handle A forms the inverse with its first acquire_grad (chunk_rows = 128), then selects (maxvar), acquires
+    (ei, constant liar), selects (imse, 64 reference rows) -- three picks each, every pick a downdate of the entry's
+    own copy of S -- and calls var_grad and acquire_grad again.  Handle B, fresh from the same Hessian, runs the
+    selections and the acquisition first: it is their first call that forms the inverse, and the gradients come last.
+    Every output of every call is the same on both, bit for bit, and so are A's first and last acquire_grad."""
+    name = "d5 p=130"
+    c = R.case(name)[0]
+    cfg = next(b["cfg"] for b in (R.built(name, ci) for ci in range(8))
+               if b["cfg"].criterion == A.EI and not b["cfg"].maximize)
+    assert c.x.shape == (300, 5) and len(c.terms) == 130
+    ei = dict(criterion="ei", best=cfg.best, xi=cfg.xi)
+    picks = lambda post: (post.select(c.x, 3, criterion="maxvar"),
+                          post.acquire(c.x, c.theta, k=3, lie="constant", **ei),
+                          post.select(c.x, 3, criterion="imse", reference=c.x[:64]))
+    with posterior_of(c) as pa, posterior_of(c) as pb:
+        first = pa.acquire_grad(c.x, c.theta, chunk_rows=128, **ei)
+        got_a = picks(pa) + (pa.var_grad(c.x), pa.acquire_grad(c.x, c.theta, **ei))
+        got_b = picks(pb) + (pb.var_grad(c.x), pb.acquire_grad(c.x, c.theta, **ei))
+    fields = lambda r: r if isinstance(r, tuple) else tuple(v for _, v in sorted(vars(r).items()))
+    count = 0
+    for ra, rb in zip(got_a + (first,), got_b + (got_a[-1],)):
+        for va, vb in zip(fields(ra), fields(rb)):
+            assert np.array_equal(va, vb, equal_nan=True) if isinstance(va, np.ndarray) else va == vb
+            count += isinstance(va, np.ndarray)
+    assert count == 4 + 5 + 4 + 2 + 6 + 6
+    assert all(len(r.index) == 3 for r in got_a[:3])

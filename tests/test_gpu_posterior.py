@@ -11,8 +11,11 @@ test_posterior_ref_host.py holds that route to the same tolerance at every shape
 failures these shapes must be able to see).  Each check prints one line -- C, err / bound and err /
 tolerance of the device and of the float64 route -- the rows of the table in DESIGN.md section 6.
 
-Not exercised: the row-chunk loop of post_var_dev (r0 != 0), which engages only when the term-major design
-matrix would pass 8 GB."""
+The row-chunk frame that post_var_dev, row_forms_dev and the acquisition gradients share (csrc/row_chunks.h) runs
+with more than one chunk on a GPU through test_gpu_acquire_grad.py (chunk_rows = 128); its arithmetic is walked on
+the host by test_row_chunks_host.py.  Still not run on a GPU: post_var_dev's and row_forms_dev's own epilogues at
+r0 != 0 (the partial sums and row sums written at d_var + r0), because their caps -- 8 GiB and 1 GiB per term-major
+block -- cannot be reached at test sizes and no switch is added for it."""
 import ctypes as C
 import functools
 import math
