@@ -1337,6 +1337,56 @@ int obhip_acquire_grad(const obhip_posterior *post, const double *theta, const d
 int obhip_acquire_grad_layout(const obhip_posterior *post, int *fused, uint64_t *lds_bytes,
                               uint64_t *default_chunk_rows);
 
+/* ---- term-count path (no reference counterpart) --------------------------------------------
+ * The terms of a handle stand in list order (selectterms: by prior variance), so the model of the
+ * first k terms has H_k = H[:k,:k] with factor L_k = L[:k,:k]: the factor of the whole list nests
+ * every prefix.  With G = e^{-2 sigma} B^T y (y standardised), U = L^-1 G = X^T G and, at a row with
+ * basis b, z = X^T b (z_j depends on b_1 .. b_j only):
+ *   theta_k = X[:k,:k] U[:k],   mean_k = sum_{j <= k} z_j U_j,   v_k = b_k^T inv(H_k) b_k = sum_{j <= k} z_j^2,
+ *   log p(y | k) = -(n/2) log 2 pi - n sigma - 1/2 e^{-2 sigma} y^T y
+ *                  + 1/2 sum_{j <= k} U_j^2 - sum_{j <= k} log L_jj + 1/2 sum_{j <= k} log prec_j.
+ * Checkpoints are k_c = min((c + 1) step, p), c = 0 .. K - 1, K = ceil(p / step); step >= p gives the
+ * one checkpoint k = p.  Row scores per checkpoint and response are sums over the n given rows, with
+ * nu = e^{2 sigma}, r = y - mean_k, h = v_k / nu:
+ *   loo = 0 (rows not in the fit):        e = r,           s2 = nu + v_k
+ *   loo = 1 (rows of the fit, each once): e = r / (1 - h), s2 = nu / (1 - h)
+ *   sse = sum r^2,  spe = sum e^2,  lpd = sum [-1/2 log(2 pi s2) - 1/2 e^2 / s2],  sumv = sum v_k.
+ * No row is left out of any sum and a row that is not finite propagates as the formulas say.  The
+ * leave-one-out scores hold the standardisation of the response (centre and scale) fixed: the row left
+ * out still counts in them.  One factor and one pass over the rows give every prefix: per row chunk the
+ * stored product Z = B X (the pass of obhip_posterior_var_dev, every entry summed in one fixed order)
+ * and one kernel that walks a row's columns in ascending order (csrc/kernels_term_path.hip).  No
+ * atomics: rows are summed per 128-row tile in a fixed order and tiles in ascending order in groups
+ * whose size does not depend on the chunking, so two calls give the same bits and a chunked call the
+ * bits of the unchunked one.  chunk_rows: 0 = the library's choice, otherwise a positive multiple of 128.
+ * The rules of the posterior block hold: every argument check runs before the first launch and a
+ * refused call changes nothing.  q <= 65534, p <= 65535, n <= 2^40. */
+/* K, the rows of a chunk that chunk_rows stands for and the bytes of pooled scratch a scores call
+ * takes (Z, the tile partials and the group sums); any output may be NULL.  Host only. */
+int obhip_term_path_layout(uint64_t p, uint64_t q, uint64_t step, uint64_t n, uint64_t chunk_rows,
+                           uint64_t *K, uint64_t *chunk_rows_used, uint64_t *scratch_bytes);
+/* G = e^{-2 sigma} B^T y_std (p x q, column-major) of the rows acc holds (minus those of minus), standardised
+   exactly as obhip_normal_acc_solve_dev does; d_meansd q triples */
+int obhip_normal_acc_rhs_dev(const obhip_normal_acc *acc, const obhip_normal_acc *minus, double sigma,
+                             double *d_G, double *d_meansd);
+/* d_diag (p) = the diagonal of the handle's H, copied: what obhip_normal_acc_solve_dev returns as d_diagH for
+   a handle made by obhip_normal_acc_posterior_dev of the same rows, sigma and rho */
+int obhip_posterior_hessian_diag_dev(const obhip_posterior *post, double *d_diag);
+/* d_U (p x q, column-major) = X^T G: U_jc = sum_{i <= j} X_ij G_ic, i ascending */
+int obhip_posterior_path_coef_dev(const obhip_posterior *post, const double *d_G, uint64_t q, double *d_U);
+/* Theta_k = X[:k,:k] U[:k]: Theta_ic = sum_{i <= j < k} X_ij U_jc, j ascending; zeros behind row k */
+int obhip_posterior_path_theta_dev(const obhip_posterior *post, const double *d_U, uint64_t q, uint64_t k,
+                                   double *d_Theta /* p x q */);
+/* host in, host out: prec (p), yty (q, standardised), out K x q (out[c * q + j]); n_rows = the n of
+ * the formula.  Host arithmetic over diag L, U and prec in one ascending order. */
+int obhip_posterior_path_evidence(const obhip_posterior *post, const double *d_U, uint64_t q, const double *prec,
+                                  const double *yty, uint64_t n_rows, uint64_t step, double *out);
+/* d_Y n x q column-major (ldy); d_meansd NULL: Y is standardised already; d_scores K x q x 3 (sse, spe, lpd:
+   d_scores[(c * q + j) * 3 + s]) in standardised units, d_sumv K; n = 0: zeros */
+int obhip_posterior_path_scores_dev(const obhip_posterior *post, const double *d_U, uint64_t q, const double *d_x,
+                                    uint64_t n, const double *d_Y, uint64_t ldy, const double *d_meansd,
+                                    uint64_t step, int loo, uint64_t chunk_rows, double *d_scores, double *d_sumv);
+
 /* ---- the model layer: lpdf, loglik_*, logpr_gauss, lpdfvec, predictor ------------------
  * Module rows src/interfaceR.cpp:696-762; classes src/fit.h:23-361; arithmetic
  * src/fit.cpp:37-612 and src/lpdfs/{loglik_std,loglik_gauss,loglik_gda,logpr_gauss}.cpp.

@@ -24,7 +24,7 @@ from .product import (CalibrationLoglik, fit_newton_product, predict_product, pr
                       product_fit_layout, product_grad_layout, product_layout, product_loglik, product_loglik_grad,
                       product_side)
 from .driver import HotPath, MultiHotPath
-from .stream import (CVResult, NewtonAccumulator, cv_folds, cv_newton_multi, design_dx,
+from .stream import (CVResult, NewtonAccumulator, TermPathResult, cv_folds, cv_newton_multi, design_dx,
                      fit_newton_grad)
 
 __all__ = [
@@ -45,4 +45,5 @@ __all__ = [
     "predict_product", "product_loglik", "product_layout", "CalibrationLoglik",
     "predict_product_grad", "product_loglik_grad", "product_grad_layout", "TorchCalibration",
     "fit_newton_product", "product_side", "product_fit_layout",
+    "TermPathResult",
 ]

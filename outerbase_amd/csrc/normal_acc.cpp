@@ -365,6 +365,27 @@ int obhip_normal_acc_solve_dev(const obhip_normal_acc *acc, const obhip_normal_a
   return solve_columns(p, d_H, d_cholws, rhs.p + p, q - 1, 1.0, d_Theta + p, (char *)d_workspace + single);
 }
 
+// G = e^{-2 sigma} B^T y_std and the moments of the rows in acc (without those of minus): the right-hand sides
+// obhip_normal_acc_solve_dev solves for, by the same kernel (the term-count path substitutes them itself)
+int obhip_normal_acc_rhs_dev(const obhip_normal_acc *acc, const obhip_normal_acc *minus, double sigma, double *d_G,
+                             double *d_meansd) {
+  if (!acc || !d_G || !d_meansd || !std::isfinite(sigma)) return fail(OBHIP_ERR_INVALID, "normal_acc_rhs_dev: bad argument");
+  if (minus && (minus->model != acc->model || !same_terms(minus->terms, acc->terms) || minus->p != acc->p || minus->q != acc->q))
+    return fail(OBHIP_ERR_INVALID, "normal_acc_rhs_dev: the accumulators differ in model, terms or responses");
+  OB_TRY(check_compat(acc->model, acc->terms));
+  OB_TRY(check_version(acc, "normal_acc_rhs_dev"));
+  if (minus) OB_TRY(check_version(minus, "normal_acc_rhs_dev"));
+  if (minus && (minus->rows > acc->rows || minus->geq > acc->geq))
+    return fail(OBHIP_ERR_STATE, "normal_acc_rhs_dev: more rows to take out than the accumulator holds");
+  const uint64_t left = acc->rows - (minus ? minus->rows : 0);
+  if (left < 2)
+    return fail(OBHIP_ERR_STATE, "normal_acc_rhs_dev: " + std::to_string(left) +
+                                     " rows left, the standard deviation of a response needs two");
+  OB_TRY(require_device());
+  const double *d_minus = minus && (minus->rows > 0 || minus->geq > 0) ? minus->st.p : nullptr;
+  return launch_acc_rhs(acc->p, acc->q, acc->st.p, d_minus, std::exp(-2.0 * sigma), d_G, d_meansd);
+}
+
 // the posterior of the rows in acc (without those of minus): H as obhip_normal_acc_solve_dev forms it
 int obhip_normal_acc_posterior_dev(const obhip_normal_acc *acc, const obhip_normal_acc *minus, double sigma, double rho,
                                    obhip_posterior **out) {

@@ -328,6 +328,99 @@ class Posterior:
         torch.cuda.synchronize()
         return var.cpu().numpy(), grad.cpu().numpy().T.copy()
 
+    # -- the term-count path (include/obhip.h, "term-count path") ------------------------------
+    def _path_dev(self, A, what):
+        """A (p x q, or p) -> device tensor (q, p): column-major p x q"""
+        import torch
+        A = np.asarray(A, dtype=np.float64)
+        A = A[:, None] if A.ndim == 1 else A
+        if A.ndim != 2 or A.shape[0] != self.p or A.shape[1] == 0:
+            raise ValueError("%s must be p x q" % what)
+        return torch.from_numpy(np.ascontiguousarray(A.T)).to(_stream())
+
+    def term_path_coef(self, G):
+        """U = L^-1 G (p x q) for the right-hand sides G = e^{-2 sigma} B^T y (p x q, y standardised): the
+        coefficients of the path, U[:k] those of the model of the first k terms."""
+        import torch
+        self._need()
+        dG = self._path_dev(G, "G")
+        dU = torch.empty_like(dG)
+        call("obhip_posterior_path_coef_dev", self._h, dG.data_ptr(), dG.shape[0], dU.data_ptr())
+        torch.cuda.synchronize()
+        return dU.cpu().numpy().T.copy()
+
+    def term_path_theta(self, U, k):
+        """The coefficients theta_k = inv(H[:k,:k]) G[:k] of the model of the first k terms (p x q, zeros behind
+        row k) from U = term_path_coef(G)."""
+        import torch
+        self._need()
+        dU = self._path_dev(U, "U")
+        dT = torch.empty_like(dU)
+        call("obhip_posterior_path_theta_dev", self._h, dU.data_ptr(), dU.shape[0], int(k), dT.data_ptr())
+        torch.cuda.synchronize()
+        return dT.cpu().numpy().T.copy()
+
+    def term_path_evidence(self, U, prec, yty, n_rows, step=16):
+        """log p(y | first k terms) at every checkpoint k = step, 2 step, ..., p (K x q) for the STANDARDISED
+        response: prec (p) the prior precisions of the terms, yty (q) = y^T y of the standardised response over
+        the n_rows rows of the fit."""
+        self._need()
+        dU = self._path_dev(U, "U")
+        q = dU.shape[0]
+        prec = np.ascontiguousarray(prec, dtype=np.float64)
+        yty = np.ascontiguousarray(np.atleast_1d(yty), dtype=np.float64)
+        if prec.shape != (self.p,) or yty.shape != (q,):
+            raise ValueError("prec must have p entries and yty q")
+        K = C.c_uint64(0)
+        call("obhip_term_path_layout", self.p, q, int(step), 0, 0, C.byref(K), None, None)
+        out = np.empty((K.value, q))
+        call("obhip_posterior_path_evidence", self._h, dU.data_ptr(), q, prec.ctypes.data, yty.ctypes.data, int(n_rows),
+             int(step), out.ctypes.data)
+        return out
+
+    def _term_path_scores_dev(self, dU, dx, n, dY, dmeansd, step, loo, chunk_rows):
+        """device tensors in (dU (q, p), dx (d, n), dY (q, n), dmeansd (q, 3) or None) -> scores (K, q, 3), sumv (K)"""
+        import torch
+        q = dU.shape[0]
+        K = C.c_uint64(0)
+        call("obhip_term_path_layout", self.p, q, int(step), n, chunk_rows, C.byref(K), None, None)
+        scores = torch.empty((K.value, q, 3), dtype=torch.float64, device=dU.device)
+        sumv = torch.empty(K.value, dtype=torch.float64, device=dU.device)
+        call("obhip_posterior_path_scores_dev", self._h, dU.data_ptr(), q, None if n == 0 else dx.data_ptr(), n,
+             None if n == 0 else dY.data_ptr(), n, None if dmeansd is None else dmeansd.data_ptr(), int(step),
+             int(bool(loo)), chunk_rows, scores.data_ptr(), sumv.data_ptr())
+        torch.cuda.synchronize()
+        return scores.cpu().numpy(), sumv.cpu().numpy()
+
+    def term_path_scores(self, U, x, Y, step=16, loo=False, chunk_rows=0, meansd=None):
+        """The scores of the model of the first k terms at every checkpoint k = step, 2 step, ..., p, summed over
+        the rows x (n x d) with responses Y (n x q) -> (scores (K x q x 3): sse, spe, lpd; sumv (K)), standardised
+        units.  loo=False: rows that are not in the fit, e = r = y - mean_k, s^2 = e^{2 sigma} + v_k.  loo=True: rows
+        of the fit, each once: the leave-one-out residual e = r / (1 - h) and variance e^{2 sigma} / (1 - h),
+        h = v_k e^{-2 sigma}, the standardisation of the response held fixed.  Y is standardised already unless
+        meansd (q x 3: centre, scale, rows) is given.  One factor and one pass over the rows serve every k;
+        chunk_rows as in var_grad: the result does not depend on it, bit for bit."""
+        import torch
+        self._need()
+        x = _rows(self.om, x, "x")
+        chunk_rows = self._chunk_rows(chunk_rows)
+        dU = self._path_dev(U, "U")
+        q, n = dU.shape[0], x.shape[0]
+        Y = np.asarray(Y, dtype=np.float64)
+        Y = Y[:, None] if Y.ndim == 1 else Y
+        if Y.shape != (n, q):
+            raise ValueError("Y must be n x q")
+        dev = dU.device
+        dm = None
+        if meansd is not None:
+            meansd = np.ascontiguousarray(meansd, dtype=np.float64)
+            if meansd.shape != (q, 3):
+                raise ValueError("meansd must be q x 3")
+            dm = torch.from_numpy(meansd).to(dev)
+        dx = _dev_cols(x, dev) if n else None
+        dY = torch.from_numpy(np.ascontiguousarray(Y.T)).to(dev) if n else None
+        return self._term_path_scores_dev(dU, dx, n, dY, dm, step, loo, chunk_rows)
+
     def _acquire_args(self, criterion, best, level, kappa, xi, response, lie_value=None):
         """the criterion's parameters (and acquire's lie_value), checked and standardised:
         (best, xi, kappa, level), lie_value, (centre, scale) or None"""

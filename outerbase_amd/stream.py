@@ -300,6 +300,143 @@ class NewtonAccumulator:
         torch.cuda.synchronize()
         return Posterior(self.om, self._t, h, meansd.cpu().numpy().copy())
 
+    def term_path(self, sigma=None, rho=DEFAULT_RHO, minus=None, step=16, x=None, Y=None, loo=False, chunk_rows=0):
+        """How many terms?  The terms of the accumulator stand in list order (selectterms sorts by prior
+        variance), so every prefix of the list is a model of its own; this scores the model of the first k terms
+        for every checkpoint k = step, 2 step, ..., p from ONE factorisation and ONE pass over the rows
+        (include/obhip.h, "term-count path"): the factor of the whole list nests the factor of every prefix.
+
+        Always: the log evidence log p(y | k) of the rows in the accumulator (without those of minus).  With rows
+        x (n x d) and their raw responses Y (n x q) also the row scores per checkpoint: loo=False for rows that
+        are NOT in the fit (hold-out error and log score), loo=True for the rows of the fit themselves, each
+        once (PRESS, the leave-one-out log score and the hat trace), the standardisation of the responses held
+        fixed.  sigma=None: log(0.01).  chunk_rows bounds the workspace of the row pass: 0 = the library's choice,
+        otherwise a positive multiple of 128; the result does not depend on it, bit for bit.  -> TermPathResult
+        (close it, or use it as a context manager: it keeps the factor on the device for fit(k))."""
+        import torch
+        from .design import Posterior
+        if sigma is None:
+            sigma = math.log(0.01)
+        sigma, rho, step = float(sigma), float(rho), int(step)
+        if step < 1:
+            raise ValueError("step must be at least 1")
+        chunk_rows = Posterior._chunk_rows(chunk_rows)
+        if (x is None) != (Y is None):
+            raise ValueError("x and Y come together")
+        if x is not None:
+            x, Y = self._check(x, Y)
+        if self.grad_rows or (minus is not None and minus.grad_rows):
+            raise ValueError("the evidence of the term-count path is that of value rows: the accumulator holds gradient rows")
+        self._need()
+        if minus is not None:
+            if not isinstance(minus, NewtonAccumulator):
+                raise TypeError("minus must be a NewtonAccumulator")
+            minus._need()
+        dev = _stream()
+        p, q, f64 = self.p, self.q, torch.float64
+        mh = None if minus is None else minus._h
+        # the right-hand sides and the moments first: what refuses a fit (too few rows, a changed model) refuses here
+        dG = torch.empty((q, p), dtype=f64, device=dev)
+        dmeansd = torch.empty((q, 3), dtype=f64, device=dev)
+        call("obhip_normal_acc_rhs_dev", self._h, mh, sigma, dG.data_ptr(), dmeansd.data_ptr())
+        h = C.c_void_p()
+        call("obhip_normal_acc_posterior_dev", self._h, mh, sigma, rho, C.byref(h))     # the one factorisation
+        post = Posterior(self.om, self._t, h, dmeansd.cpu().numpy().copy())
+        try:
+            ddiag = torch.empty(p, dtype=f64, device=dev)
+            call("obhip_posterior_hessian_diag_dev", post._h, ddiag.data_ptr())
+            diagH = ddiag.cpu().numpy()
+            dU = torch.empty_like(dG)
+            call("obhip_posterior_path_coef_dev", post._h, dG.data_ptr(), q, dU.data_ptr())
+            K = C.c_uint64(0)
+            call("obhip_term_path_layout", p, q, step, 0, 0, C.byref(K), None, None)
+            K = K.value
+            sizes = np.minimum((np.arange(K, dtype=np.int64) + 1) * step, p)
+            ms = post.meansd
+            rows = ms[:, 2]
+            prec = np.ascontiguousarray(1.0 / (self.om.getvar(self._t.array) * math.exp(2 * rho)))
+            yty = np.ascontiguousarray(rows - 1.0)      # of the standardised response: sd has the n - 1 denominator
+            ev = np.empty((K, q))
+            call("obhip_posterior_path_evidence", post._h, dU.data_ptr(), q, prec.ctypes.data, yty.ctypes.data,
+                 int(rows[0]), step, ev.ctypes.data)
+            res = TermPathResult(self.om, self._t, post, dU, sizes, ev, diagH, sigma, rho, bool(loo))
+            if x is not None:
+                n = x.shape[0]
+                dx = torch.from_numpy(np.ascontiguousarray(x.T)).to(dev) if n else None
+                dY = torch.from_numpy(np.ascontiguousarray(Y.T)).to(dev) if n else None
+                sc, sumv = post._term_path_scores_dev(dU, dx, n, dY, dmeansd, step, loo, chunk_rows)
+                sd = ms[:, 1]
+                res.n = n
+                res.sse = sc[:, :, 0] * sd[None, :] ** 2
+                res.spe = sc[:, :, 1] * sd[None, :] ** 2
+                res.lpd = sc[:, :, 2] - n * np.log(sd)[None, :]
+                res.rmse = np.sqrt(res.spe / n) if n else np.full((K, q), np.nan)
+                res.dof = sumv / math.exp(2 * sigma) if loo else None
+            return res
+        except BaseException:
+            post.close()
+            raise
+
+
+class TermPathResult:
+    """The path over the number of terms (NewtonAccumulator.term_path).
+
+    sizes (K): the checkpoints k = step, 2 step, ..., p.  log_evidence (K x q): log p(y | first k terms) of the
+    rows of the fit -- for the STANDARDISED response (y - centre) / scale, as the fit sees it: add -n log(scale)
+    for the raw response; the difference between two sizes does not depend on that.  With rows given: sse (K x q)
+    = sum (y - mean_k)^2; spe = the sum of squared prediction errors (loo: PRESS, else sse); lpd = the sum of the
+    log predictive densities (loo: each row's by the fit without it); rmse = sqrt(spe / n) -- all in RAW units --
+    and dof (K) = the hat trace sum_i h_i under loo, else None.  Without rows they are None.  The leave-one-out
+    scores hold the centre and scale of the responses fixed."""
+
+    def __init__(self, om, t, post, dU, sizes, log_evidence, diagH, sigma, rho, loo):
+        self.om, self._t, self._post, self._dU = om, t, post, dU
+        self.sizes, self.log_evidence = sizes, log_evidence
+        self._diagH, self.sigma, self.rho, self.loo = diagH, sigma, rho, loo
+        self.n = 0
+        self.sse = self.spe = self.lpd = self.rmse = self.dof = None
+
+    def close(self):
+        if getattr(self, "_post", None) is not None:
+            self._post.close()
+        self._post = self._dU = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def best(self, by="evidence", response=None):
+        """The size that is best by "evidence" (largest), "lpd" (largest) or "spe" (smallest) for one response,
+        or for the mean over the responses (response=None).  The lowest size wins a tie."""
+        table = {"evidence": (self.log_evidence, 1.0), "lpd": (self.lpd, 1.0), "spe": (self.spe, -1.0)}
+        if by not in table:
+            raise ValueError("by must be one of %s" % sorted(table))
+        a, sign = table[by]
+        if a is None:
+            raise ValueError("no rows were given: only the evidence is there")
+        s = sign * (a.mean(axis=1) if response is None else a[:, int(response)])
+        return int(self.sizes[int(np.argmax(s))])       # (argmax: the first among equals)
+
+    def fit(self, k):
+        """The MultiFit of the first k terms (1 <= k <= p, a checkpoint or not), as fit_newton_multi on terms[:k]
+        and the same rows gives it: the coefficients come from the factor the path has."""
+        import torch
+        if self._post is None:
+            raise RuntimeError("the path is closed")
+        k = int(k)
+        if not 1 <= k <= self._t.p:
+            raise ValueError("k must be between 1 and p")
+        _stream()
+        dT = torch.empty_like(self._dU)
+        call("obhip_posterior_path_theta_dev", self._post._h, self._dU.data_ptr(), self._dU.shape[0], k, dT.data_ptr())
+        torch.cuda.synchronize()
+        theta = dT.cpu().numpy().T[:k].copy()
+        return MultiFit(self.om, obmod._Terms(self.om, self._t.array[:k]), theta, self._post.meansd.copy(),
+                        self._diagH[:k].copy(), self.sigma, self.rho)
+
 
 def _check_grad_x(om, x, dims, weights):
     x = np.asarray(x, dtype=np.float64)
