@@ -1387,6 +1387,68 @@ int obhip_posterior_path_scores_dev(const obhip_posterior *post, const double *d
                                     uint64_t n, const double *d_Y, uint64_t ldy, const double *d_meansd,
                                     uint64_t step, int loo, uint64_t chunk_rows, double *d_scores, double *d_sumv);
 
+/* ---- conditional moments (no reference counterpart) ----------------------------------------
+ * The mean and the variance of the fitted mean over some inputs (the noise dimensions E) at fixed
+ * values of the others (the control dimensions S, the complement of E), in closed form from the
+ * moment tables of obhip_dim_moments_dev.  Notation of the sensitivity block and of
+ * obhip_predict_grad_dev: f(x) = sum_k theta_k prod_l psi_{l,t_kl}(x_l), raw psi_l = R_l; tables m_l,
+ * C_l, A_l = C_l + m_l m_l^T.  dims_e names E: 0-based, strictly ascending, 1 <= |E| <= d - 1 (the
+ * convention of dims_b in the product block).  The noise inputs are independent and follow the
+ * discrete product measure of the tables; only the tables of the dimensions in E are read.
+ * For row i with control inputs x_i,S and response j:
+ *   P_ik = prod_{l in S} R_{l,t_kl}(x_il)   (the A side of obhip_product_side_dev with dims_b = dims_e)
+ *   M_ij = E[f_j | x_S]   = sum_k theta_kj P_ik prod_{l in E} m_l[t_kl]
+ *   W_ij = Var[f_j | x_S] = sum_{k,k'} theta_kj theta_k'j P_ik P_ik'
+ *                             sum_{l in E} (prod_{i in E, i<l} A_i) C_l (prod_{i in E, i>l} m_i m_i)
+ * with the table entries at [t_kl, t_k'l]: the bracket prod A - prod m m is formed telescoped, as
+ * obhip_sobol_dev forms V, never as a difference of two products.  Level 0 is not the constant
+ * function: a term set whose terms all have level 0 on E still has a small positive variance.
+ * The terms are grouped by their level tuples on E: G <= p groups, numbered in the order of their
+ * first term, g(k) the group of term k.  With c_ij[g] = sum_{k in g} theta_kj P_ik (ascending k),
+ * mE[g] = prod_{l in E} m_l[.] and K[g,g'] the bracket on the groups' tuples,
+ *   M_ij = c_ij^T mE,   W_ij = c_ij^T K c_ij = sum_g c_ij[g] Y_ij[g],   Y_ij = K c_ij (g' ascending),
+ * and for l in S, with rho_l, r'_lt and E_kl of obhip_predict_grad_dev restricted to S,
+ *   dM_ij/dx_il = sum_k theta_kj mE[g(k)] dP_ik/dx_il,   dW_ij/dx_il = 2 sum_k theta_kj Y_ij[g(k)] dP_ik/dx_il.
+ * A row costs O(p |S| + G^2), the G^2 part on the FP64 matrix cores; nothing of size n p exists
+ * and the workspace is that of one row chunk.  Fixed summation order, no atomics: two calls give
+ * the same bits, a chunked call those of the unchunked one, and each output requested alone the
+ * bits it has when all are requested.  A row with a coordinate that is not finite gets NaN.
+ * Refused with OBHIP_ERR_INVALID before any device call, nothing written: a NULL required
+ * argument; dims_e unsorted, repeated, out of range, empty or naming all d dimensions; chunk_rows
+ * not a multiple of 128 (or above 2^28); a level above 255, d above 255, q above 65535, p above 2^24
+ * (the limits of the Sobol passes); tables of the noise dimensions beyond the LDS of a workgroup
+ * (3 x 8 x (sum over E of L_l^2 + 1) bytes above 160 KB: only those tables are held); more than 2^31
+ * (term, control dimension) pairs with a factor; n above 2^40 (that of
+ * obhip_predict_grad_dev); more than 65535 used basis columns on S; more than 16384 groups.  n = 0
+ * is a no-op. */
+/* the number of groups, the group of every term (p entries, or NULL), the used columns of the S
+ * side (the ones column included) and whether the row kernels keep the tile of S in LDS (at most 8
+ * factors per term on S and a derivative tile within the LDS budget; otherwise, and under
+ * OBHIP_FORCE_GENERIC, the same arithmetic runs from a pooled HBM tile).  Any output may be NULL.
+ * Host only. */
+int obhip_conditional_layout(const obhip_terms *t, const uint32_t *dims_e, uint64_t ndims_e, uint64_t *n_groups,
+                             uint32_t *group_of, uint64_t *mu_s, int *fused);
+/* d_mE (G) and d_K (G x G, leading dimension G): K is symmetric to the bit, every unordered pair of
+ * groups is formed once and written to both places */
+int obhip_conditional_tables_dev(const obhip_terms *t, const uint32_t *dims_e, uint64_t ndims_e,
+                                 const double *d_mean_tab, const double *d_cov_tab, double *d_mE, double *d_K);
+/* d_Theta p x q column-major; d_xs n x |S| column-major (leading dimension n), the columns in
+ * ascending order of dimension -- what obhip_predict_product_dev takes for xa; d_mean, d_var n x q
+ * column-major; d_gradmean, d_gradvar [(j |S| + a) n + i] for response j, the a-th dimension of S and
+ * row i.  Any of the four outputs may be NULL.  chunk_rows: 0 = the library's choice, otherwise a
+ * positive multiple of 128; it bounds the workspace and changes no bit of any output. */
+int obhip_conditional_moments_dev(const obhip_model *m, const obhip_terms *t, const double *d_Theta, uint64_t q,
+                                  const uint32_t *dims_e, uint64_t ndims_e, const double *d_mean_tab,
+                                  const double *d_cov_tab, const double *d_xs, uint64_t n, uint64_t chunk_rows,
+                                  double *d_mean, double *d_var, double *d_gradmean, double *d_gradvar);
+/* host in, host out; xs with leading dimension ldx, the outputs compact as above */
+int obhip_conditional_tables(const obhip_terms *t, const uint32_t *dims_e, uint64_t ndims_e, const double *mean_tab,
+                             const double *cov_tab, double *mE, double *K);
+int obhip_conditional_moments(const obhip_model *m, const obhip_terms *t, const double *Theta, uint64_t q,
+                              const uint32_t *dims_e, uint64_t ndims_e, const double *mean_tab, const double *cov_tab,
+                              const double *xs, uint64_t n, uint64_t ldx, uint64_t chunk_rows, double *mean,
+                              double *var, double *gradmean, double *gradvar);
+
 /* ---- the model layer: lpdf, loglik_*, logpr_gauss, lpdfvec, predictor ------------------
  * Module rows src/interfaceR.cpp:696-762; classes src/fit.h:23-361; arithmetic
  * src/fit.cpp:37-612 and src/lpdfs/{loglik_std,loglik_gauss,loglik_gda,logpr_gauss}.cpp.

@@ -15,8 +15,9 @@ from .obmod import (covf, covf_mat25, covf_mat25ang, covf_mat25pow, gethyp, getp
 from .fitting import BFGS_lpdf, BFGS_std, obfit, obpred, obpred_grad
 from .multi import MultiFit, fit_newton_multi
 from .glm import GlmFit, fit_glm
-from .sensitivity import (ActiveSubspaceResult, GradMoments, InputMoments, ShapleyResult, Sobol2Result, SobolResult,
-                          active_subspace, input_grad_moments, input_moments, interaction_effects, main_effects,
+from .sensitivity import (ActiveSubspaceResult, ConditionalResult, GradMoments, InputMoments, ShapleyResult,
+                          Sobol2Result, SobolResult, active_subspace, conditional_layout, conditional_moments,
+                          conditional_tables, input_grad_moments, input_moments, interaction_effects, main_effects,
                           shapley, sobol, sobol2, sym_eigh, uniform_nodes)
 from .design import AcquireGradResult, AcquireResult, DesignResult, Posterior, ThompsonResult
 from .torch_emulator import TorchAcquisition, TorchCalibration, TorchEmulator
@@ -46,4 +47,5 @@ __all__ = [
     "predict_product_grad", "product_loglik_grad", "product_grad_layout", "TorchCalibration",
     "fit_newton_product", "product_side", "product_fit_layout",
     "TermPathResult",
+    "ConditionalResult", "conditional_layout", "conditional_moments", "conditional_tables",
 ]

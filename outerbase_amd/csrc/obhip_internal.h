@@ -970,6 +970,10 @@ struct ProductSplit {
 };
 // dims_b: 1 to d - 1 entries, strictly ascending, each < d -- refused with OBHIP_ERR_INVALID otherwise
 int make_split(const char *who, const obhip_terms &t, const uint32_t *dims_b, uint64_t ndims_b, ProductSplit &s);
+// one side's tables against the column layout of t.pred_md (after prepare_predict): cpos maps a compact column to the
+// side's used column or -1, cols holds p x w right-aligned used-column indices, padded with column 0
+void side_tables(const obhip_terms &t, const ProductSplit &s, const std::vector<int> &side, uint64_t w,
+                 std::vector<int32_t> &cpos, std::vector<uint16_t> &cols);
 // the device tables of the split (t.product), cached on the terms for the last split and column layout asked for
 int ensure_product_tables(const obhip_model &m, obhip_terms &t, const ProductSplit &s);
 // kernels_product_fit.hip / product_fit.cpp: the Newton fit on gridded data (include/obhip.h, "Newton fit on

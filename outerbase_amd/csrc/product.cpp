@@ -58,7 +58,7 @@ int make_split(const char *who, const obhip_terms &t, const uint32_t *dims_b, ui
 
 }  // namespace obhip
 
-namespace {
+namespace obhip {
 
 // one side's tables against the column layout of t.pred_md: its used columns are numbered 1, 2, .. in the
 // order of the side's dimensions and, within a dimension, of the levels
@@ -88,10 +88,6 @@ void side_tables(const obhip_terms &t, const ProductSplit &s, const std::vector<
     }
   }
 }
-
-}  // namespace
-
-namespace obhip {
 
 // the device tables of the split, cached on the terms for the last split and column layout asked for
 int ensure_product_tables(const obhip_model &m, obhip_terms &t, const ProductSplit &s) {

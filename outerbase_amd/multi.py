@@ -261,6 +261,22 @@ class MultiFit:
         res.eigenvalues = res.eigenvalues * s2[None, :]
         return res
 
+    def conditional(self, x, noise_dims, nodes, weights=None, grad=False):
+        """Mean and variance of every response over the noise inputs noise_dims (independent, the product measure of
+        nodes / weights) at the control inputs of the rows x (n x d or n x |S|), in raw units: ConditionalResult
+        with mean = y_cent + y_sca M, var times y_sca^2 and, with grad=True, grad_mean times y_sca and grad_var
+        times y_sca^2 (sensitivity.conditional_moments)."""
+        from . import sensitivity
+        mom = sensitivity.input_moments(self.om, self._t, nodes, weights)
+        res = sensitivity.conditional_moments(self.om, self._t, self.coeff, mom, noise_dims, x, grad=grad)
+        s2 = self.y_sca * self.y_sca
+        res.mean = self.y_cent[None, :] + self.y_sca[None, :] * res.mean
+        res.var = res.var * s2[None, :]
+        if grad:
+            res.grad_mean = res.grad_mean * self.y_sca[None, None, :]
+            res.grad_var = res.grad_var * s2[None, None, :]
+        return res
+
     def interaction_effects(self, dim_i, dim_j, grid_i, grid_j, nodes, weights=None):
         """the interaction surface of every response on grid_i x grid_j (Gi x Gj x q), in raw units (times y_sca)"""
         from . import sensitivity

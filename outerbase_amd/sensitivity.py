@@ -419,3 +419,91 @@ def active_subspace(om, terms, Theta, gmoments, scale=None):
          g.dmean_dev.data_ptr(), g.cross_dev.data_ptr(), g.dd_dev.data_ptr(), out.data_ptr(), ws.data_ptr(), wsb.value)
     torch.cuda.synchronize()
     return ActiveSubspaceResult(out.cpu().numpy(), d, scale)
+
+
+class ConditionalResult:
+    """mean, var (n x q): E[f | x_S] and Var[f | x_S] over the noise inputs at the control inputs of every row;
+    grad_mean, grad_var (n x |S| x q, or None): their derivatives by the control inputs, [i, a, j] by the a-th of
+    control_dims; control_dims: the dimensions that are not noise, ascending."""
+
+    def __init__(self, mean, var, grad_mean, grad_var, control_dims):
+        self.mean, self.var, self.grad_mean, self.grad_var = mean, var, grad_mean, grad_var
+        self.control_dims = control_dims
+
+
+def _check_noise_dims(d, noise_dims):
+    """-> (dims_e uint32, control_dims int64)"""
+    de = np.atleast_1d(np.asarray(noise_dims)).astype(np.int64)
+    if de.ndim != 1 or de.size < 1 or de.size > d - 1:
+        raise ValueError("noise_dims must name 1 to d - 1 dimensions")
+    if np.any(de < 0) or np.any(de >= d) or np.any(np.diff(de) <= 0):
+        raise ValueError("noise_dims must be strictly ascending dimension indices (0-based)")
+    return np.ascontiguousarray(de, dtype=np.uint32), np.setdiff1d(np.arange(d), de)
+
+
+def conditional_layout(om, terms, noise_dims):
+    """{"n_groups", "group_of" (p), "mu_s", "fused", "control_dims"} of the split into noise and control dimensions:
+    the groups of terms by their levels on the noise dimensions, numbered in the order of their first term, the used
+    basis columns of the control side and whether the row kernels keep its tile in LDS -- obhip_conditional_layout
+    (host only)."""
+    t = obmod._terms_of(om, terms)
+    de, ctrl = _check_noise_dims(t.d, noise_dims)
+    G, mu, fused = C.c_uint64(0), C.c_uint64(0), C.c_int(0)
+    gof = np.empty(t.p, dtype=np.uint32)
+    call("obhip_conditional_layout", t._h, de.ctypes.data, de.size, C.byref(G), gof.ctypes.data, C.byref(mu),
+         C.byref(fused))
+    return {"n_groups": int(G.value), "group_of": gof.astype(np.int64), "mu_s": int(mu.value),
+            "fused": bool(fused.value), "control_dims": ctrl}
+
+
+def conditional_tables(om, terms, moments, noise_dims):
+    """(mE (G), K (G x G)) of the groups under the measure of `moments`: the product of the means and the telescoped
+    covariance bracket on the groups' level tuples -- obhip_conditional_tables_dev."""
+    t = obmod._terms_of(om, terms)
+    de, _ = _check_noise_dims(t.d, noise_dims)
+    G = conditional_layout(om, t, noise_dims)["n_groups"]
+    torch, dev = _device()
+    mE = torch.empty(G, dtype=torch.float64, device=dev)
+    K = torch.empty((G, G), dtype=torch.float64, device=dev)
+    call("obhip_conditional_tables_dev", t._h, de.ctypes.data, de.size, moments.mean_dev.data_ptr(),
+         moments.cov_dev.data_ptr(), mE.data_ptr(), K.data_ptr())
+    torch.cuda.synchronize()
+    return mE.cpu().numpy(), K.cpu().numpy()
+
+
+def conditional_moments(om, terms, Theta, moments, noise_dims, x, grad=False, chunk_rows=0):
+    """ConditionalResult of the responses Theta (p x q, or p) at the rows x: the mean and the variance of the fitted
+    mean over the noise inputs, which are independent and follow the measure of `moments`, with the other inputs
+    held at the row's values; grad=True: also their gradients by the control inputs.  x: n x d (the noise columns
+    are ignored) or n x |S| (the control dimensions ascending).  chunk_rows: 0 or a positive multiple of 128, the
+    rows worked on at a time; it changes no bit of the result -- obhip_conditional_moments_dev."""
+    t = obmod._terms_of(om, terms)
+    Theta = _check_theta(t, Theta)
+    de, ctrl = _check_noise_dims(t.d, noise_dims)
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] not in (t.d, ctrl.size):
+        raise ValueError("x must be n x d or n x |S|")
+    if x.shape[1] == t.d:
+        x = x[:, ctrl]
+    chunk_rows = int(chunk_rows)
+    if chunk_rows < 0 or chunk_rows % 128:
+        raise ValueError("chunk_rows must be 0 or a positive multiple of 128")
+    n, q, ns = x.shape[0], Theta.shape[1], ctrl.size
+    if n == 0:
+        z, g = np.zeros((0, q)), np.zeros((0, ns, q))
+        return ConditionalResult(z, z.copy(), g if grad else None, g.copy() if grad else None, ctrl)
+    torch, dev = _device()
+    f64 = torch.float64
+    dx = torch.from_numpy(np.ascontiguousarray(x.T)).to(dev)
+    dth = torch.from_numpy(np.ascontiguousarray(Theta.T)).to(dev)
+    mean = torch.empty((q, n), dtype=f64, device=dev)
+    var = torch.empty((q, n), dtype=f64, device=dev)
+    gm = torch.empty((q, ns, n), dtype=f64, device=dev) if grad else None
+    gv = torch.empty((q, ns, n), dtype=f64, device=dev) if grad else None
+    call("obhip_conditional_moments_dev", om._h, t._h, dth.data_ptr(), q, de.ctypes.data, de.size,
+         moments.mean_dev.data_ptr(), moments.cov_dev.data_ptr(), dx.data_ptr(), n, chunk_rows, mean.data_ptr(),
+         var.data_ptr(), gm.data_ptr() if grad else None, gv.data_ptr() if grad else None)
+    torch.cuda.synchronize()
+    return ConditionalResult(mean.cpu().numpy().T, var.cpu().numpy().T,
+                             gm.permute(2, 1, 0).cpu().numpy() if grad else None,
+                             gv.permute(2, 1, 0).cpu().numpy() if grad else None, ctrl)
