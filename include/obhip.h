@@ -362,6 +362,18 @@ int obhip_gram_dedup_table_dev(const obhip_terms *t, int64_t *d_src);
  * (in kept wave tiles) instead.  Any out pointer may be NULL. */
 int obhip_gram_dedup_quads_info(const obhip_terms *t, uint64_t *wave_tiles, uint64_t *dropped, uint64_t *blocks_per_split,
                                 int *engaged);
+/* The panel Gram may stage and multiply its columns in an order of its own -- the terms in a stable sort by their
+ * number of factors -- under which more wave tiles consist of repeats alone; which of them go is then decided by a
+ * sequential pass from the farthest wave tile inwards.  Nothing a caller sees changes order: G, B^T y, the prior
+ * diagonal and every report are in the caller's term coordinates.  A launch takes the order when its packed plan
+ * saves a block per row split against the plan the launch would otherwise run and four launches save more modelled
+ * time than the one-off set-up takes; OBHIP_GRAM_ORDER=1 forces it, =0 forbids it.  engaged: the term set's latest
+ * Gram launch ran in Gram order (forced: the next one will); dropped, blocks_per_split: of its plan (0 while not
+ * engaged); setup_ms: host wall time of the set-up, 0 while none has run.  While engaged,
+ * obhip_gram_dedup_quads_info and obhip_gram_dedup_table_dev report this plan, in term coordinates.  Any out
+ * pointer may be NULL. */
+int obhip_gram_order_info(const obhip_terms *t, int *engaged, uint64_t *dropped, uint64_t *blocks_per_split,
+                          double *setup_ms);
 /* bytes of device workspace obhip_newton_solve_dev needs for p terms */
 int obhip_newton_workspace_bytes(uint64_t p, uint64_t *bytes);
 /* One Newton step from coeff = 0 of lpdfvec(loglik_std, logpr_gauss)

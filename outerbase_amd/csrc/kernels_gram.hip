@@ -35,11 +35,19 @@ __device__ __forceinline__ uint64_t tri_row(uint64_t i, uint64_t p) { return i *
 // quadrants of its tile pair one after the other: 36 workgroups at p = 1024 (BASELINE configs[1]),
 // each a chain of 4 x 16 x nsplit dependent loads -- 0.22 ms for 67 MB.  Same sums in the same order
 // per element; only who computes them changed.
+//
+// PERM: the partials are in Gram order (gram_order.h), entry (gi, gj) of them belongs to the terms a = perm[gi]
+// and b = perm[gj].  It goes to (min, max) of the two -- the upper triangle, where `acc` reads and the packed
+// sink has its row -- and its mirror is written by the same thread from the same register: G stays exactly
+// symmetric.  prec and diagH are indexed by the term.  The stores are scattered (consecutive columns of Gram
+// order are terms apart); without PERM the kernel is what it was, instruction for instruction.
 constexpr int kRedRows = 16;  // rows of a quadrant per workgroup
+template <bool PERM>
 __global__ void __launch_bounds__(256)
 k_gram_reduce(const double *__restrict__ part, int npairs, int nsplit, int nb, int p,
               double *__restrict__ G, int acc, int packed, int form, double e2,
-              const double *__restrict__ prec, double *__restrict__ diagH, const uint8_t *__restrict__ skip) {
+              const double *__restrict__ prec, double *__restrict__ diagH, const uint8_t *__restrict__ skip,
+              const uint32_t *__restrict__ perm) {
   __shared__ double S[kRedRows * 65];  // the slice, so that the mirror goes out in row segments too
   // skip: per tile pair one bit per quadrant (2 row + column) that no wave wrote partials of: k_gram_fill
   // copies its entries (a skipped tile pair has all four set)
@@ -63,6 +71,23 @@ k_gram_reduce(const double *__restrict__ part, int npairs, int nsplit, int nb, i
 #pragma unroll 8
     for (int k = 0; k < nsplit; ++k) s += part[((uint64_t)k * npairs + blockIdx.x) * (kGT * kGT) + e];
     const bool in = gi0 + r < p && gj0 + c < p;
+    if constexpr (PERM) {
+      if (in && !(dq && c < r)) {
+        const uint64_t a = perm[gi0 + r], b = perm[gj0 + c], i = min(a, b), j = max(a, b);
+        double *g = packed ? &G[tri_row(i, p) + (j - i)] : &G[i * p + j];
+        if (acc) s += *g;
+        if (form) {
+          s *= e2;
+          if (i == j) {
+            s += prec[i];
+            if (diagH) diagH[i] = s;
+          }
+        }
+        *g = s;
+        if (!packed && i != j) G[j * p + i] = s;
+      }
+      continue;
+    }
     if (in && !(dq && c < r)) {  // the entry (gi0 + r, gj0 + c), j >= i
       const uint64_t i = (uint64_t)(gi0 + r), j = (uint64_t)(gj0 + c);
       double *g = packed ? &G[tri_row(i, p) + (j - i)] : &G[i * p + j];
@@ -78,7 +103,7 @@ k_gram_reduce(const double *__restrict__ part, int npairs, int nsplit, int nb, i
     }
     S[(r - r0) * 65 + c] = s;
   }
-  if (packed) return;  // no mirror, and S is not read
+  if (PERM || packed) return;  // no mirror (PERM: written above), and S is not read
   __syncthreads();
   // mirrored: G[gj0 + r][gi0 + r0 + cc] = S[cc][r], strictly below the diagonal of G only; a thread
   // takes column cc of the slice (16 consecutive doubles of a row of G per 16 threads)
@@ -92,13 +117,17 @@ k_gram_reduce(const double *__restrict__ part, int npairs, int nsplit, int nb, i
 }  // namespace
 
 int launch_gram_reduce(const double *part, int npairs, int nsplit, int nb, int p, const GramSink &sink,
-                       bool accumulate, bool last, const uint8_t *skip) {
+                       bool accumulate, bool last, const uint8_t *skip, const uint32_t *perm) {
   ProfScope ps("gram_reduce");
   const int form = sink.form && last ? 1 : 0;
   if (form && !sink.prec) return fail(OBHIP_ERR_INVALID, "gram sink: form without the prior precisions");
-  hipLaunchKernelGGL(k_gram_reduce, dim3((unsigned)npairs, 4 * (64 / kRedRows)), dim3(256), 0, cur_stream(), part, npairs,
-                     nsplit, nb, p, sink.out, accumulate ? 1 : 0, sink.packed ? 1 : 0, form, sink.e2,
-                     sink.prec, sink.diagH, skip);
+  const dim3 grid((unsigned)npairs, 4 * (64 / kRedRows));
+  if (perm)
+    hipLaunchKernelGGL(k_gram_reduce<true>, grid, dim3(256), 0, cur_stream(), part, npairs, nsplit, nb, p, sink.out,
+                       accumulate ? 1 : 0, sink.packed ? 1 : 0, form, sink.e2, sink.prec, sink.diagH, skip, perm);
+  else
+    hipLaunchKernelGGL(k_gram_reduce<false>, grid, dim3(256), 0, cur_stream(), part, npairs, nsplit, nb, p, sink.out,
+                       accumulate ? 1 : 0, sink.packed ? 1 : 0, form, sink.e2, sink.prec, sink.diagH, skip, nullptr);
   OB_HIP(hipGetLastError());
   return 0;
 }
@@ -120,6 +149,7 @@ int launch_gram(const obhip_basis &b, obhip_terms &t, double *d_G) {
 
 int launch_gram_to(const obhip_basis &b, obhip_terms &t, const GramSink &sink, GramFuse *fuse) {
   OB_TRY(t.prepare(b.md.cap, b.md.dims_h));
+  t.order.last_launch = 0;  // (launch_gram_panel records an ordered launch)
   if (g_gram_backend == 3) {
     if (!gram_mfma4_supports(t))
       return fail(OBHIP_ERR_INVALID,

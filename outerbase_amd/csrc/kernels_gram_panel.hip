@@ -450,13 +450,24 @@ struct RowView {
   }
 };
 
-int materialize_any(const obhip_basis &b, obhip_terms &t, double *d_B, GramFuse *fuse = nullptr) {
-  if (t.Mu > 280 || getenv("OBHIP_FORCE_GENERIC")) return launch_materialize_generic(b, t, d_B);
+bool materialize_lane_row() {
   static const bool lane_row = getenv("OBHIP_MATERIALIZE_LANE_ROW") != nullptr;
-  if (!lane_row && materialize_tl_supports(t)) {
+  return lane_row;
+}
+// the staging kernel that takes a column order (k_materialize_tl reads its columns from a table) serves t
+bool order_stageable(const obhip_terms &t) {
+  return !(t.Mu > 280 || getenv("OBHIP_FORCE_GENERIC")) && !materialize_lane_row() && materialize_tl_supports(t);
+}
+
+int materialize_any(const obhip_basis &b, obhip_terms &t, double *d_B, GramFuse *fuse = nullptr,
+                    const GramOrder *order = nullptr) {
+  if (order && !order_stageable(t)) return fail(OBHIP_ERR_INVALID, "materialize: no staging kernel takes a column order here");
+  if (t.Mu > 280 || getenv("OBHIP_FORCE_GENERIC")) return launch_materialize_generic(b, t, d_B);
+  if (!materialize_lane_row() && materialize_tl_supports(t)) {
     // the fit's B^T y rides along (whole basis only: the chunked path passes no request)
     const bool f = fuse && fuse->y && fuse->g && !fuse->done;
-    OB_TRY(launch_materialize_tl(b, t, d_B, f ? fuse->y : nullptr, f ? fuse->g : nullptr));
+    if (order) OB_TRY(gram_order_cols(t));
+    OB_TRY(launch_materialize_tl(b, t, d_B, f ? fuse->y : nullptr, f ? fuse->g : nullptr, order));
     if (f) fuse->done = true;
     return 0;
   }
@@ -517,23 +528,30 @@ int print_gram_dbg(const unsigned long long *dbgout) {
   return 0;
 }
 
-}  // namespace
-
-// partial tiles of B^T B over the ntiles row tiles of d_B, reduced into the sink:
-// switches -> dedup -> plan -> table -> launch -> reduce -> fill
-int gram_of_staged(obhip_basis &b, const double *d_B, uint64_t ntiles, obhip_terms &t, const GramSink &sink,
-                   bool accumulate, bool last) {
-  const GramSwitches sw{};
+// What a launch over ntiles row tiles runs with the columns in the terms' own order: switches -> dedup -> plan
+// (-> the plan at wave-tile granularity)
+struct GramLaunch {
+  GramSwitches sw{};
+  const GramDedup *dd = nullptr;
+  const uint8_t *skip = nullptr;
+  GramShape shape;
+  GramPlan plan{1, false};
+  const GramDedup::Quads *quads = nullptr;
+};
+int plan_gram_launch(obhip_basis &b, obhip_terms &t, uint64_t ntiles, GramLaunch &L, bool own_order) {
+  const GramSwitches &sw = L.sw;
   // tile pairs that only repeat entries of other pairs get no task (gram_dedup.hip; analysed on the
   // term set's first Gram)
-  const GramDedup *dd = nullptr;
-  OB_TRY(gram_dedup_get(t, &dd));
-  const uint8_t *skip = dd ? dd->skip.data() : nullptr;
-  const GramShape shape = {(int)((t.p + kGT - 1) / kGT), ntiles, 2 * (uint64_t)device_cus(b.device), sw.diag4};
-  const int nb = shape.nb, npairs = (int)gram_npairs(nb);
+  const GramDedup *&dd = L.dd;
+  if (own_order) OB_TRY(gram_dedup_get(t, &dd));
+  const uint8_t *&skip = L.skip;
+  skip = dd ? dd->skip.data() : nullptr;
+  GramShape &shape = L.shape;
+  shape = {(int)((t.p + kGT - 1) / kGT), ntiles, 2 * (uint64_t)device_cus(b.device), sw.diag4};
   // the plan: the split as if no pair were skipped (gram_choose_split says why), the dealing for the mask
   // at that split, kept with the analysis; a forced value replaces either
-  GramPlan plan = split_of_shape(shape);
+  GramPlan &plan = L.plan;
+  plan = split_of_shape(shape);
   if (sw.nsplit) plan.nsplit = std::max<uint64_t>(1, std::min<uint64_t>(gram_max_split(shape), atoi(sw.nsplit)));
   if (skip) {
     GramDedup::Dealing &d = t.dedup.dealing;
@@ -547,9 +565,52 @@ int gram_of_staged(obhip_basis &b, const double *d_B, uint64_t ntiles, obhip_ter
   if (sw.continuous) plan.continuous = atoi(sw.continuous) != 0;
   // the plan at wave-tile granularity in place of all that, when it pays or is forced (gram_quads_get): the same
   // split, its own dealing, the four wave bytes of every block beside the task table
-  const GramDedup::Quads *quads = nullptr;
-  OB_TRY(gram_quads_get(t, shape, plan, skip, dd ? dd->sig : 0, &quads));
-  if (quads) plan.continuous = sw.continuous ? plan.continuous : quads->continuous;
+  if (own_order) OB_TRY(gram_quads_get(t, shape, plan, skip, dd ? dd->sig : 0, &L.quads));
+  if (L.quads) plan.continuous = sw.continuous ? plan.continuous : L.quads->continuous;
+  return 0;
+}
+
+// Whether the Gram of (b, t) over launches of ntiles row tiles stages its columns in Gram order (gram_order_get):
+// decided against the plan the launch would otherwise run, priced by gram_cost on its task table
+int order_of_launch(obhip_basis &b, obhip_terms &t, uint64_t ntiles, const GramOrder **order) {
+  *order = nullptr;
+  if (gram_order_mode() == 0 || !order_stageable(t)) return 0;
+  GramLaunch L;
+  OB_TRY(plan_gram_launch(b, t, ntiles, L, true));
+  // (priced only when the decision kept with the order is for another launch)
+  auto price = [&](double &cost, int &blocks) {
+    std::vector<uint64_t> tab;
+    std::vector<uint32_t> wbytes;
+    if (L.quads)
+      gram_quads_table(L.shape.nb, (int)L.plan.nsplit, L.plan.continuous, L.quads->keep.data(), tab, wbytes);
+    else
+      build_task_order(L.shape.nb, (int)L.plan.nsplit, L.sw.diag4, L.plan.continuous, L.skip, tab);
+    cost = gram_table_cost(L.shape, L.plan.nsplit, L.plan.continuous, tab);
+    blocks = (int)((tab.size() - (size_t)std::count(tab.begin(), tab.end(), kAtbNoTask)) / L.plan.nsplit);
+  };
+  return gram_order_get(t, L.shape, L.plan, L.quads ? L.quads->sig : L.dd ? L.dd->sig : 0, price, order);
+}
+
+}  // namespace
+
+// partial tiles of B^T B over the ntiles row tiles of d_B, reduced into the sink:
+// switches -> dedup -> plan -> table -> launch -> reduce -> fill
+int gram_of_staged(obhip_basis &b, const double *d_B, uint64_t ntiles, obhip_terms &t, const GramSink &sink,
+                   bool accumulate, bool last, const GramOrder *order) {
+  GramLaunch L;
+  OB_TRY(plan_gram_launch(b, t, ntiles, L, order == nullptr));
+  if (order) {  // d_B is in Gram order: the order's own packed plan, at the same split
+    L.quads = &order->quads;
+    L.plan.continuous = L.sw.continuous ? L.plan.continuous : order->quads.continuous;
+  }
+  const GramSwitches &sw = L.sw;
+  const GramDedup *dd = L.dd;
+  const uint8_t *skip = L.skip;
+  const GramDedup::Quads *quads = L.quads;
+  const GramShape &shape = L.shape;
+  const GramPlan &plan = L.plan;
+  const int nb = shape.nb, npairs = (int)gram_npairs(nb);
+  const uint32_t *perm = order ? order->perm_dev.p : nullptr;
   // the table: built and uploaded when anything it depends on has changed
   obhip_basis::GramTable &tb = b.gram_table;
   const GramKey tkey = {{nb, 0, 0, sw.diag4}, plan.nsplit, quads ? quads->sig : dd ? dd->sig : 0, plan.continuous ? 1 : 0};
@@ -578,42 +639,47 @@ int gram_of_staged(obhip_basis &b, const double *d_B, uint64_t ntiles, obhip_ter
   }));
   if (dbgout) OB_TRY(print_gram_dbg(dbgout));
   OB_TRY(launch_gram_reduce(part, npairs, (int)plan.nsplit, nb, (int)t.p, sink, accumulate, last,
-                            quads ? quads->qskip_dev.p : dd ? dd->skip_dev.p : nullptr));
+                            quads ? quads->qskip_dev.p : dd ? dd->skip_dev.p : nullptr, perm));
   // the skipped pairs' (dropped wave tiles') entries from their sources in the sink: after every reduction (of
   // a row chunk too: the sources then hold the sums so far, the copies likewise), formed values when the
   // reduction formed the Hessian
-  if (quads) return launch_gram_fill_quads(*quads, (int)t.p, sink);
+  if (quads) return launch_gram_fill_quads(*quads, (int)t.p, sink, perm);
   return dd ? launch_gram_fill(*dd, (int)t.p, sink) : 0;
 }
 
 // d_B: n_pad x p_pad doubles, row-major (= column-major p_pad x n_pad); padding rows are 0
-int launch_materialize_rows(const obhip_basis &b, obhip_terms &t, double *d_B, GramFuse *fuse) {
+int launch_materialize_rows(const obhip_basis &b, obhip_terms &t, double *d_B, GramFuse *fuse, const GramOrder *order) {
   OB_TRY(t.prepare(b.md.cap, b.md.dims_h));
   ProfScope ps("materialize_B");
-  return materialize_any(b, t, d_B, fuse);
+  return materialize_any(b, t, d_B, fuse, order);
 }
 
 // b.bmat = row-major design matrix of (b, t); kept until the basis is rebuilt or other
 // terms need the buffer
-int ensure_bmat(obhip_basis &b, obhip_terms &t, GramFuse *fuse) {
-  if (b.bmat_terms == t.uid && t.uid != 0) return 0;
+int ensure_bmat(obhip_basis &b, obhip_terms &t, GramFuse *fuse, const GramOrder *order) {
+  const uint64_t want = order ? order->serial : 0;
+  if (b.bmat_terms == t.uid && t.uid != 0 && b.bmat_order == want) return 0;
   OB_TRY(t.prepare(b.md.cap, b.md.dims_h));
   if (!gram_panel_supports(b, t))
     return fail(OBHIP_ERR_INVALID, "not enough free HBM for the n x p design matrix");
   const size_t need = (size_t)b.n_pad * t.p_pad;
   if (b.bmat.n < need) OB_TRY(b.bmat.alloc(need));
   b.bmat_terms = 0;
-  OB_TRY(launch_materialize_rows(b, t, b.bmat.p, fuse));
+  OB_TRY(launch_materialize_rows(b, t, b.bmat.p, fuse, order));
   b.bmat_terms = t.uid;
+  b.bmat_order = want;
   return 0;
 }
 
 int launch_gram_panel(const obhip_basis &bc, obhip_terms &t, const GramSink &sink, GramFuse *fuse) {
   obhip_basis &b = const_cast<obhip_basis &>(bc);
   const uint64_t ntiles = b.n_pad / kTileRows;
+  const GramOrder *order = nullptr;
   if (gram_panel_supports(b, t)) {
-    OB_TRY(ensure_bmat(b, t, fuse));
-    return gram_of_staged(b, b.bmat.p, ntiles, t, sink, false, true);
+    OB_TRY(order_of_launch(b, t, ntiles, &order));
+    t.order.last_launch = order ? 1 : 0;
+    OB_TRY(ensure_bmat(b, t, fuse, order));
+    return gram_of_staged(b, b.bmat.p, ntiles, t, sink, false, true, order);
   }
   // Not enough memory for all rows at once: stage and contract row chunks one after the
   // other, the later ones accumulating into G.  Chunk = a quarter of the free HBM (at most
@@ -627,14 +693,18 @@ int launch_gram_panel(const obhip_basis &bc, obhip_terms &t, const GramSink &sin
     return fail(OBHIP_ERR_HIP, "not enough free HBM for even one row chunk of the design matrix");
   b.bmat_terms = 0;  // the buffer no longer holds the whole matrix of any terms
   if (b.bmat.n < (size_t)ctiles * kTileRows * t.p_pad) OB_TRY(b.bmat.alloc((size_t)ctiles * kTileRows * t.p_pad));
+  // one order for all chunks (decided at the size of a full chunk): the sink accumulates in term coordinates
+  // either way, but a source must hold the sums of the same chunks as its copies
+  OB_TRY(order_of_launch(b, t, ctiles, &order));
+  t.order.last_launch = order ? 1 : 0;
   for (uint64_t t0 = 0; t0 < ntiles; t0 += ctiles) {
     const uint64_t nt = std::min(ctiles, ntiles - t0);
     RowView view(b, t0, nt);
     {
       ProfScope ps("materialize_B");
-      OB_TRY(materialize_any(view.v, t, b.bmat.p));
+      OB_TRY(materialize_any(view.v, t, b.bmat.p, nullptr, order));
     }
-    OB_TRY(gram_of_staged(b, b.bmat.p, nt, t, sink, t0 != 0, t0 + nt >= ntiles));
+    OB_TRY(gram_of_staged(b, b.bmat.p, nt, t, sink, t0 != 0, t0 + nt >= ntiles, order));
   }
   return 0;
 }

@@ -93,15 +93,16 @@ k_aty_multi(const double *__restrict__ B, uint64_t ldb, uint64_t n, const double
       }
 }
 
-// out[j * ldo + k] = sum over the splits, in ascending order
+// out[j * ldo + k] = sum over the splits, in ascending order (perm: column k of the staged matrix is term
+// perm[k], whose row of out the sum belongs to)
 __global__ void __launch_bounds__(256)
 k_aty_reduce(const double *__restrict__ part, int nsplit, int qw, uint64_t ldb, int p, int q,
-             double *__restrict__ out, uint64_t ldo) {
+             double *__restrict__ out, uint64_t ldo, const uint32_t *__restrict__ perm) {
   const int k = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
   if (k >= p || j >= q) return;
   double s = 0.0;
   for (int sp = 0; sp < nsplit; ++sp) s += part[((uint64_t)sp * qw + j) * ldb + k];
-  out[(uint64_t)j * ldo + k] = s;
+  out[(uint64_t)j * ldo + (perm ? perm[k] : (uint32_t)k)] = s;
 }
 
 // ---- triangular solves with up to 64 right-hand sides ------------------------------------------
@@ -407,9 +408,13 @@ uint64_t multi_solve_scratch_bytes(uint64_t p) {
 }
 
 // d_out (p x q, column-major, leading dimension ldo) = B^T Y from the staged design matrix of
-// (b, t), which the caller has made sure is resident
+// (b, t), which the caller has made sure is resident -- in the terms' own column order or in their Gram order
+// (obhip_basis::bmat_order), whose sums the reduction scatters to their terms: no second staging, and no pass
+// over the basis per response
 int launch_aty_multi(obhip_basis &b, const obhip_terms &t, const double *d_Y, uint64_t ldy, uint64_t q,
                      double *d_out, uint64_t ldo) {
+  const uint32_t *perm = b.bmat_order != 0 && b.bmat_order == t.order.serial ? t.order.perm_dev.p : nullptr;
+  if (b.bmat_order != 0 && !perm) return fail(OBHIP_ERR_INVALID, "aty_multi: the staged matrix is in another order");
   ProfScope ps("aty_multi");
   const uint64_t ldb = t.p_pad, n = b.n;
   const int ncu = device_cus(b.device);
@@ -428,7 +433,7 @@ int launch_aty_multi(obhip_basis &b, const obhip_terms &t, const double *d_Y, ui
     if (nqb == 2) OB_TRY(run_aty<2>(b.bmat.p, ldb, n, Yc, ldy, qc, rows_per, (int)nsplit, (double *)part));
     if (nqb == 4) OB_TRY(run_aty<4>(b.bmat.p, ldb, n, Yc, ldy, qc, rows_per, (int)nsplit, (double *)part));
     hipLaunchKernelGGL(k_aty_reduce, dim3((unsigned)((t.p + 255) / 256), (unsigned)qc), dim3(256), 0, cur_stream(),
-                       (const double *)part, (int)nsplit, 16 * nqb, ldb, (int)t.p, qc, d_out + q0 * ldo, ldo);
+                       (const double *)part, (int)nsplit, 16 * nqb, ldb, (int)t.p, qc, d_out + q0 * ldo, ldo, perm);
     OB_HIP(hipGetLastError());
   }
   return 0;

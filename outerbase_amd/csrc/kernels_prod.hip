@@ -938,10 +938,12 @@ __global__ void k_mm_tl_sum(const double *__restrict__ part, int pblocks, uint64
 // out[k] = sum over the row splits of part[split][k]: a block takes 64 terms, its 16 waves
 // every 16th split each (coalesced 512-byte reads), LDS tree over the waves.  Fixed order,
 // so the result does not depend on the launch.
+// PERM: the partials are in the Gram's column order (gram_order.h), the sum of column k belongs to term perm[k].
 constexpr int kRedThreads = 1024;
+template <bool PERM>
 __global__ void __launch_bounds__(kRedThreads)
 k_tmm_reduce(const double *__restrict__ part, int nsplit, uint64_t p_pad, int p,
-             double *__restrict__ out) {
+             double *__restrict__ out, const uint32_t *__restrict__ perm) {
   __shared__ double red[kRedThreads / 64][64];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int k = blockIdx.x * 64 + lane;
@@ -960,7 +962,8 @@ k_tmm_reduce(const double *__restrict__ part, int nsplit, uint64_t p_pad, int p,
     double tot = 0.0;
 #pragma unroll
     for (int q = 0; q < kRedThreads / 64; ++q) tot += red[q][lane];
-    out[k] = tot;
+    if constexpr (PERM) out[perm[k]] = tot;
+    else out[k] = tot;
   }
 }
 
@@ -1005,14 +1008,17 @@ size_t hm_tl_lds_bytes(const obhip_terms &t) {
 
 // d_out (p) = the sum of the row-split partials part[nsplit][p_pad]; with `then` q = e2 d_out + prec pv as well
 int reduce_partials(const double *part, uint64_t nsplit, const obhip_terms &t, double *d_out,
-                    const HmThen *then = nullptr) {
+                    const HmThen *then = nullptr, const uint32_t *perm = nullptr) {
   const dim3 grid((unsigned)((t.p + 63) / 64));
-  if (then)
+  if (perm)
+    hipLaunchKernelGGL(k_tmm_reduce<true>, grid, dim3(kRedThreads), 0, cur_stream(), part, (int)nsplit, t.p_pad, (int)t.p,
+                       d_out, perm);
+  else if (then)
     hipLaunchKernelGGL(k_tmm_reduce_q, grid, dim3(kRedThreads), 0, cur_stream(), part, (int)nsplit, t.p_pad,
                        (int)t.p, d_out, then->e2, then->prec, then->pv, then->q);
   else
-    hipLaunchKernelGGL(k_tmm_reduce, grid, dim3(kRedThreads), 0, cur_stream(), part, (int)nsplit, t.p_pad, (int)t.p,
-                       d_out);
+    hipLaunchKernelGGL(k_tmm_reduce<false>, grid, dim3(kRedThreads), 0, cur_stream(), part, (int)nsplit, t.p_pad, (int)t.p,
+                       d_out, nullptr);
   OB_HIP(hipGetLastError());
   return 0;
 }
@@ -1182,9 +1188,11 @@ int tmm_tl_supports(const obhip_terms &t) {
 bool materialize_tl_supports(const obhip_terms &t) { return tmm_tl_supports(t) != 0; }
 
 // d_B: n_pad x p_pad doubles, row-major; t prepared by the caller.  d_y (n, may be null): also
-// d_g (p) = B^T y, from the products the copy forms anyway.
+// d_g (p) = B^T y, from the products the copy forms anyway.  order (may be null): column k of d_B is term
+// order->perm[k] -- the kernel reads the column table in that order (gram_order_cols has gathered it) -- and the
+// reduction of the partial sums writes d_g[perm[k]].
 int launch_materialize_tl(const obhip_basis &b, obhip_terms &t, double *d_B, const double *d_y,
-                          double *d_g) {
+                          double *d_g, const GramOrder *order) {
   const int w2 = (int)(t.W / 2);
   const int npair = units_per_lane(t.p_pad, (uint64_t)kTlWaves * 128, tl_max_pairs(w2));
   const uint64_t tpb = (uint64_t)kTlWaves * npair * 128;
@@ -1195,6 +1203,8 @@ int launch_materialize_tl(const obhip_basis &b, obhip_terms &t, double *d_B, con
   double *ypart = nullptr;
   if (d_y) OB_TRY(const_cast<obhip_basis &>(b).workspace(rs.nsplit * t.p_pad * sizeof(double), (void **)&ypart));
   const bool pf = t.Mu <= (uint64_t)kTlWaves * kTlPre;
+  ProdTabs tabs = prod_tabs(b, t);
+  if (order) tabs.cols = (const uint32_t *)order->cols.p;
   OB_TRY(pick<1, 2, 3, 4>(w2, [&](auto W2) {
     return pick<4, 2, 1>(npair, [&](auto NP) {
       if constexpr (NP() > tl_max_pairs(W2())) return no_kernel();
@@ -1202,12 +1212,12 @@ int launch_materialize_tl(const obhip_basis &b, obhip_terms &t, double *d_B, con
         return pick_bool(pf, [&](auto PF) {
           return pick_bool(d_y != nullptr, [&](auto WY) {
             return launch_prod(k_materialize_tl<W2(), NP(), PF(), WY()>, grid, dim3(kTlThreads), tmm_tl_lds_bytes(t),
-                               prod_tabs(b, t), b.n, ntiles, rs.tps, t.p_pad, d_B, d_y, ypart);
+                               tabs, b.n, ntiles, rs.tps, t.p_pad, d_B, d_y, ypart);
           });
         });
     });
   }));
-  if (d_y) OB_TRY(reduce_partials(ypart, rs.nsplit, t, d_g));
+  if (d_y) OB_TRY(reduce_partials(ypart, rs.nsplit, t, d_g, nullptr, order ? order->perm_dev.p : nullptr));
   return 0;
 }
 

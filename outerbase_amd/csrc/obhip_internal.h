@@ -22,6 +22,7 @@
 #include "../../include/obhip.h"
 #include "launch_plan.h"
 #include "gram_plan.h"
+#include "gram_order.h"
 
 namespace obhip {
 
@@ -313,6 +314,22 @@ struct GramDedup {
     DevBuf<uint32_t> src;        // ndrop x 64 x 64 sources, in kept wave tiles
   } quads;
 };
+// The order in which the panel Gram stages and multiplies the columns of these terms (gram_order.h): a stable
+// sort by the number of factors, under which more wave tiles repeat.  It belongs to the term set, is built on
+// first use and changes nothing a caller sees: every result comes out in term coordinates.
+struct GramOrder {
+  bool tried = false;             // perm, inv and perm_dev are built
+  bool identity = true;           // the sort changes nothing
+  uint64_t serial = 0;            // non-zero once built: what obhip_basis::bmat_order records of a staged matrix
+  int last_launch = -1;           // the term set's latest launch_gram_to ran in Gram order (1) or not (0); -1: none yet
+  std::vector<uint32_t> perm;     // perm[k] = the term staged as column k
+  std::vector<uint32_t> inv;      // inv[perm[k]] = k
+  DevBuf<uint32_t> perm_dev;      // p_pad entries, the padding columns stay where they are (last)
+  DevBuf<uint16_t> cols;          // obhip_terms::cols with its rows in Gram order (gathered before every staging)
+  // the analysis at wave-tile granularity in Gram coordinates, dropped by the sequential pass; its key, engaged,
+  // continuous, blocks and setup_ms are those of the order (blocks_pairs: of the plan it competes with)
+  GramDedup::Quads quads;
+};
 }  // namespace obhip
 
 struct obhip_terms {
@@ -410,6 +427,7 @@ struct obhip_terms {
   uint64_t prec_version = 0;
   double prec_rho = 0.0;
   obhip::GramDedup dedup;             // redundant tile pairs of the panel Gram (levels only: no cap in its key)
+  obhip::GramOrder order;             // the column order of the panel Gram and its plan (levels only)
   // Sobol passes (sobol.cpp; levels only): the levels as bytes, [p][d], and per dimension l
   // L_l = maxlev[l] + 1, its offset in a packed mean table and in a packed cov table ([3][d] ints)
   obhip::DevBuf<uint8_t> sobol_lev;
@@ -484,6 +502,7 @@ struct obhip_basis {
   obhip::DevBuf<double> bmat;   // row-major design matrix [n_pad][p_pad], staging of the
                                 // materialised-B Gram kernel (allocated on first use)
   uint64_t bmat_terms = 0;      // uid of the terms bmat currently holds (0: none)
+  uint64_t bmat_order = 0;      // GramOrder::serial of the column order it holds them in (0: the terms' own)
   struct GramTable {            // XCD-aware (tile pair, row split) task order of that kernel ...
     obhip::GramKey key;         // ... and what it was built for (no shape: no table)
     obhip::DevBuf<uint64_t> tab;
@@ -607,8 +626,9 @@ int launch_gram(const obhip_basis &b, obhip_terms &t, double *d_G);
 int launch_gram_to(const obhip_basis &b, obhip_terms &t, const GramSink &sink, GramFuse *fuse = nullptr);
 // skip (device, may be null): per tile pair one bit per quadrant (2 row + column) whose partials were never
 // written and that is left alone (0x0f: the whole pair)
+// perm (device, may be null): the partials are in Gram order, entry (gi, gj) belongs to terms perm[gi], perm[gj]
 int launch_gram_reduce(const double *part, int npairs, int nsplit, int nb, int p, const GramSink &sink,
-                       bool accumulate, bool last, const uint8_t *skip = nullptr);
+                       bool accumulate, bool last, const uint8_t *skip = nullptr, const uint32_t *perm = nullptr);
 // gram_dedup.hip: *out = the redundant tile pairs of t's term set, nullptr when there are none (or
 // OBHIP_GRAM_DEDUP=0); launch_gram_fill copies their entries from their sources in the sink
 int gram_dedup_get(obhip_terms &t, const GramDedup **out);
@@ -618,17 +638,31 @@ int launch_gram_fill(const GramDedup &dd, int p, const GramSink &sink);
 // time than its set-up took), nullptr otherwise; launch_gram_fill_quads copies the dropped wave tiles' entries
 int gram_quads_get(obhip_terms &t, const GramShape &shape, const GramPlan &plan, const uint8_t *skip, uint64_t skip_sig,
                    const GramDedup::Quads **out);
-int launch_gram_fill_quads(const GramDedup::Quads &q, int p, const GramSink &sink);
+int launch_gram_fill_quads(const GramDedup::Quads &q, int p, const GramSink &sink, const uint32_t *perm = nullptr);
+// the column order of t's Gram (OBHIP_GRAM_ORDER): *out = &t.order when the launch of this shape at this split is
+// to stage and multiply its columns in Gram order -- forced, or the ordered packed plan saves a block per split
+// against the plan the launch would otherwise take (price_other: its gram_cost and blocks per split, asked for only
+// when a decision has to be taken) and kGramOrderLaunches launches save more modelled time than the set-up costs;
+// nullptr otherwise
+int gram_order_get(obhip_terms &t, const GramShape &shape, const GramPlan &plan, uint64_t other_sig,
+                   const std::function<void(double &, int &)> &price_other, const GramOrder **out);
+int gram_order_mode();  // 1 forced, 0 forbidden, -1 the model decides
+int gram_order_cols(obhip_terms &t);  // t.order.cols = t.cols with its rows in Gram order
 void set_gram_backend(int b);
 int get_gram_backend();
 // kernels_gram_panel.hip
-int launch_materialize_rows(const obhip_basis &b, obhip_terms &t, double *d_B, GramFuse *fuse = nullptr);
-int ensure_bmat(obhip_basis &b, obhip_terms &t, GramFuse *fuse = nullptr);  // b.bmat = design matrix of (b, t)
+// order (may be null): the columns in that order, and the fused B^T y scattered back to the terms
+int launch_materialize_rows(const obhip_basis &b, obhip_terms &t, double *d_B, GramFuse *fuse = nullptr,
+                            const GramOrder *order = nullptr);
+// b.bmat = design matrix of (b, t) with its columns in `order` (null: the terms' own); staged anew when it holds
+// other terms or another order
+int ensure_bmat(obhip_basis &b, obhip_terms &t, GramFuse *fuse = nullptr, const GramOrder *order = nullptr);
 bool gram_panel_supports(const obhip_basis &b, const obhip_terms &t);
 // partial tiles of B^T B over the ntiles x 64 rows staged at d_B (pitch p_pad), reduced into the sink; holder
 // lends its device, workspace and task table (grad_obs.cpp stages rows of its own)
+// order: the one d_B was staged in (launch_gram_panel alone passes one: the other callers stage rows of their own)
 int gram_of_staged(obhip_basis &holder, const double *d_B, uint64_t ntiles, obhip_terms &t, const GramSink &sink,
-                   bool accumulate, bool last);
+                   bool accumulate, bool last, const GramOrder *order = nullptr);
 // C = A^T Bm on the matrix cores (kernels_gram_panel.hip): kAtbNorm = row norms of C into
 // out[J * ldo + i] per 128-column tile J, kAtbStore = C stored row-major with ldo, kAtbStoreFixed = the same with
 // every entry summed over k in one order wherever it stands (kAtbStore rotates a tile's start by its indices);
@@ -873,7 +907,7 @@ int grad_tmm_host(obhip_basis &b, obhip_terms &t, bool squared, const double *d_
 uint64_t newton_workspace_bytes(uint64_t p);
 bool materialize_tl_supports(const obhip_terms &t);
 int launch_materialize_tl(const obhip_basis &b, obhip_terms &t, double *d_B, const double *d_y = nullptr,
-                          double *d_g = nullptr);
+                          double *d_g = nullptr, const GramOrder *order = nullptr);
 int launch_newton_solve(uint64_t p, double *d_H, const double *d_rhs,
                         double *d_theta, void *d_ws, uint64_t ws_bytes);
 int launch_form_hessian(uint64_t p, double *d_G, const double *d_prec,

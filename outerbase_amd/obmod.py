@@ -299,6 +299,14 @@ class _Terms:
         call("obhip_terms_info", self._h, C.byref(p), C.byref(d), C.byref(nnz), C.byref(mx))
         return dict(p=p.value, d=d.value, nnz_total=nnz.value, max_nnz=mx.value)
 
+    def gram_order_info(self):
+        """the panel Gram's own column order (obhip_gram_order_info): engaged, dropped wave tiles, blocks per
+        row split, set-up time in ms"""
+        engaged, dropped, blocks, ms = C.c_int(), C.c_uint64(), C.c_uint64(), C.c_double()
+        call("obhip_gram_order_info", self._h, C.byref(engaged), C.byref(dropped), C.byref(blocks), C.byref(ms))
+        return dict(engaged=bool(engaged.value), dropped=dropped.value, blocks_per_split=blocks.value,
+                    setup_ms=ms.value)
+
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None and _lib.lib is not None:
             _lib.lib.obhip_terms_destroy(self._h)
