@@ -1290,6 +1290,70 @@ int obhip_acquire(const obhip_posterior *post, const double *theta, const double
                   const uint8_t *skip, uint64_t k, int64_t *index, double *score, double *score0,
                   double *mean, double *var, uint64_t *n_picked);
 
+/* ---- acquisition over several responses (no reference counterpart) -------------------------
+ * The picks of obhip_acquire_dev for q responses fitted from one Gram and one factor: d_Theta (p x q,
+ * leading dimension p) holds their standardised coefficients.  They share H, hence the latent variance
+ * d_i and the downdate vector a_i, and given the data their coefficient posteriors are independent:
+ * feasibility probabilities multiply and a pick still costs one pass of the one-response predictor.
+ * Per response r (host arrays of q entries): roles[r] OBHIP_ROLE_OBJECTIVE, _CONSTRAINT or _NONE
+ * (carried along, not scored); signs[r] = +1 or -1 (an objective: -1 maximises; a constraint:
+ * +1 is f_r <= limits[r], -1 is f_r >= limits[r]); limits[r]: a constraint's limit, the incumbent of the
+ * CEI / CPI objective (signs[r] * limits[r] finite or +inf: "no feasible run yet"), the reference
+ * coordinate of an EHVI objective (finite).  With ms_r = signs[r] mu_r, cs_r = signs[r] limits[r],
+ * Psi(c; ms, d) = OBHIP_ACQ_EI's score at best = c, xi = 0 and P(c; ms, d) = OBHIP_ACQ_PI's likewise
+ * (both with their sd = 0 branches):
+ *   pof = prod over the constraints, ascending r from 1.0, of P(cs_r; ms_r, d)
+ *   OBHIP_MACQ_CEI   one objective   EI(ms, d, best, xi) pof; while best = +inf: pof
+ *   OBHIP_MACQ_CPI   one objective   PI(ms, d, best, xi) pof; likewise
+ *   OBHIP_MACQ_POF   no objective, at least one constraint   pof
+ *   OBHIP_MACQ_EHVI  two objectives (1) and (2) in response order, reference point (cs_(1), cs_(2)):
+ *                    the expected improvement of the hypervolume the front dominates inside the box,
+ *                    pof sum_{s=1..F+1} [Psi(u_s; ms_1, d) - Psi(u_{s-1}; ms_1, d)] Psi(c_s; ms_2, d),
+ *                    u_1 < .. < u_F the front's first coordinates, u_{F+1} = r1, Psi(u_0) = 0, c_1 = r2,
+ *                    c_{s+1} the second coordinate of front point s; the strips are summed in ascending s.
+ * front0 (host, F0 x 2 row-major pairs in the caller's sign, any order, finite; EHVI only) is
+ * normalised point by point by the front rule: a point not strictly inside the box or with a front
+ * point <= it in both signed coordinates changes nothing; otherwise every front point >= it in both
+ * leaves and it is inserted in order.  After pick j every response gets a value -- OBHIP_LIE_BELIEVER:
+ * y*_r = mu_jr; OBHIP_LIE_CONSTANT: y*_r = lie_value[r] (host, q finite entries) -- and with gamma and a_i
+ * of obhip_acquire_dev mu_ir += a_i (y*_r - mu_jr) / gamma for every r and d_i -= a_i^2 / gamma once.  The
+ * pick is believed feasible when signs[r] y*_r <= cs_r for every constraint; only then CEI / CPI take
+ * best = min(best, signs y*_obj) and EHVI enters the signed point into the front by the same rule.
+ * Tie rule, eligibility, d_skip and non-finite scores are obhip_acquire_dev's; one host wait per pick;
+ * no atomics: two calls give the same bits.  q = 1, CEI without a constraint and a finite incumbent
+ * returns the bits of obhip_acquire_dev with OBHIP_ACQ_EI (CPI: OBHIP_ACQ_PI).
+ * Out: d_index, d_score (k), *n_picked as obhip_acquire_dev; d_score0, d_pof0 (m, may be NULL): the
+ * score and the feasibility factor at the first step; d_mean (m x q, leading dimension m) and d_var (m)
+ * after all fantasies (may be NULL); front_out (host, 2 (F0 + k) doubles, pairs in the caller's sign,
+ * ascending in the signed first coordinate) with *n_front, and *best_out (the final incumbent of CEI /
+ * CPI in the caller's sign), each may be NULL.  Refused with OBHIP_ERR_INVALID before any device call:
+ * q outside 1 .. 16, a number of objectives the criterion does not take, F0 + k > 2048, a reference
+ * point, xi, front point or lie value that is not finite, an incumbent that is neither finite nor +inf
+ * in the signed sense.  The rules of the posterior block hold. */
+enum { OBHIP_MACQ_CEI = 0, OBHIP_MACQ_CPI = 1, OBHIP_MACQ_POF = 2, OBHIP_MACQ_EHVI = 3 };
+enum { OBHIP_ROLE_OBJECTIVE = 0, OBHIP_ROLE_CONSTRAINT = 1, OBHIP_ROLE_NONE = 2 };
+int obhip_acquire_multi_dev(const obhip_posterior *post, const double *d_Theta, uint64_t q,
+                            const double *d_xcand, uint64_t m, int criterion, const int32_t *roles,
+                            const double *signs, const double *limits, double xi,
+                            const double *front0, uint64_t F0, int lie, const double *lie_value,
+                            const uint8_t *d_skip /* m or NULL */, uint64_t k, int64_t *d_index,
+                            double *d_score, double *d_score0, double *d_pof0, double *d_mean,
+                            double *d_var, double *front_out, uint64_t *n_front, double *best_out,
+                            uint64_t *n_picked);
+/* the same on host buffers; Theta p x q with leading dimension p, xcand m x d column-major with leading
+ * dimension m, mean m x q with leading dimension m */
+int obhip_acquire_multi(const obhip_posterior *post, const double *Theta, uint64_t q, const double *xcand,
+                        uint64_t m, int criterion, const int32_t *roles, const double *signs,
+                        const double *limits, double xi, const double *front0, uint64_t F0, int lie,
+                        const double *lie_value, const uint8_t *skip, uint64_t k, int64_t *index,
+                        double *score, double *score0, double *pof0, double *mean, double *var,
+                        double *front_out, uint64_t *n_front, double *best_out, uint64_t *n_picked);
+/* host only: *lds_bytes = the LDS of one workgroup of the update kernel for q responses, this criterion
+ * and a front of at most front_cap (= F0 + k) points; *max_q = 16, *max_front = 2048.  q, criterion or
+ * front_cap outside those limits are refused.  Any pointer may be NULL. */
+int obhip_acquire_multi_layout(uint64_t q, int criterion, uint64_t front_cap, uint64_t *lds_bytes,
+                               uint64_t *max_q, uint64_t *max_front);
+
 /* ---- acquisition gradients (no reference counterpart) --------------------------------------
  * The latent variance d_i = b_i^T inv(H) b_i (the full posterior covariance, what the design and
  * acquisition entries score with), the latent mean mu_i = b_i^T theta, an acquisition criterion and

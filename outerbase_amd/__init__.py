@@ -19,7 +19,7 @@ from .sensitivity import (ActiveSubspaceResult, ConditionalResult, GradMoments, 
                           Sobol2Result, SobolResult, active_subspace, conditional_layout, conditional_moments,
                           conditional_tables, input_grad_moments, input_moments, interaction_effects, main_effects,
                           shapley, sobol, sobol2, sym_eigh, uniform_nodes)
-from .design import AcquireGradResult, AcquireResult, DesignResult, Posterior, ThompsonResult
+from .design import AcquireGradResult, AcquireMultiResult, AcquireResult, DesignResult, Posterior, ThompsonResult
 from .torch_emulator import TorchAcquisition, TorchCalibration, TorchEmulator
 from .product import (CalibrationLoglik, fit_newton_product, predict_product, predict_product_grad,
                       product_fit_layout, product_grad_layout, product_layout, product_loglik, product_loglik_grad,
@@ -48,4 +48,5 @@ __all__ = [
     "fit_newton_product", "product_side", "product_fit_layout",
     "TermPathResult",
     "ConditionalResult", "conditional_layout", "conditional_moments", "conditional_tables",
+    "AcquireMultiResult",
 ]

@@ -60,4 +60,26 @@ __device__ __forceinline__ double acq_score(double ms, double dv, double best, d
   return acq_eval<CRIT>(ms, dv, best, xi, kappa, level, A, C);
 }
 
+// the argmax of the pick kernels (kernels_acquire.hip, kernels_acquire_multi.hip): one comparison everywhere, so the
+// result does not depend on the order in which pairs meet
+constexpr int64_t kNoIndex = INT64_MAX;
+
+// (score, index) a beats b: the larger score, the lower index among equals
+__device__ __forceinline__ bool beats(double sa, int64_t ia, double sb, int64_t ib) {
+  return sa > sb || (sa == sb && ia < ib);
+}
+
+// the 64 lanes of a wave -> every lane holds the wave's best pair
+__device__ __forceinline__ void wave_best(double &score, int64_t &idx) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const double os = __shfl_xor(score, off, 64);
+    const int64_t oi = __shfl_xor((long long)idx, off, 64);
+    if (beats(os, oi, score, idx)) {
+      score = os;
+      idx = oi;
+    }
+  }
+}
+
 }  // namespace obhip

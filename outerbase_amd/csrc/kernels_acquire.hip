@@ -24,26 +24,6 @@ namespace obhip {
 
 namespace {
 
-constexpr int64_t kNoIndex = INT64_MAX;
-
-// (score, index) a beats b: the larger score, the lower index among equals
-__device__ __forceinline__ bool beats(double sa, int64_t ia, double sb, int64_t ib) {
-  return sa > sb || (sa == sb && ia < ib);
-}
-
-// the 64 lanes of a wave -> every lane holds the wave's best pair
-__device__ __forceinline__ void wave_best(double &score, int64_t &idx) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const double os = __shfl_xor(score, off, 64);
-    const int64_t oi = __shfl_xor((long long)idx, off, 64);
-    if (beats(os, oi, score, idx)) {
-      score = os;
-      idx = oi;
-    }
-  }
-}
-
 template <int CRIT>
 __global__ void __launch_bounds__(256)
 k_acq_update(uint64_t n, const double *__restrict__ a, const double *__restrict__ scal, double sgn, double xi,

@@ -800,6 +800,33 @@ int launch_acq_update(const AcqStep &s, double *d_score0);
 // the partial pairs -> the step's pick: index and score appended at slot `step`, the row marked, x_j gathered
 // into d_xj, delta and the incumbent into scal; no eligible candidate: scal[5] = 1 and nothing else written
 int launch_acq_pick(const AcqStep &s, uint64_t d, uint64_t step, int64_t *d_index, double *d_score, double *d_xj);
+// acquire_multi.cpp / kernels_acquire_multi.hip: acquisition picks over several responses (include/obhip.h,
+// "acquisition over several responses").  The state block of a call, in doubles: per response
+// (16 slots each) delta = y* - mu_j, the sign g, the signed limit cs (a constraint's limit, an EHVI objective's
+// reference coordinate), the lie value and the role; the signed incumbent of CEI / CPI; F; the front's first
+// coordinates (ascending) and second coordinates, kMacqFrontCap + 1 slots each (acquire_front.h)
+constexpr int kMacqDelta = 0, kMacqSign = 16, kMacqLimit = 32, kMacqLie = 48, kMacqRole = 64, kMacqBest = 80,
+              kMacqF = 81, kMacqU = 82, kMacqC = kMacqU + 2048 + 1, kMacqState = kMacqC + 2048 + 1;
+struct MacqStep {
+  int crit = 0, lie = 0, q = 0, obj1 = -1, obj2 = -1;  // the objectives' response indices, -1: none
+  uint64_t n = 0, front_cap = 0;   // front_cap: F never exceeds it during the call (the LDS of the update kernel)
+  double xi = 0.0;
+  const double *x = nullptr;       // candidates, column-major n x d
+  const double *a = nullptr;       // n: b_i^T s of the previous pick (zeros before the first)
+  const uint8_t *elig = nullptr;   // n: launch_sample_elig's map
+  uint8_t *picked = nullptr;       // n
+  double *mean = nullptr, *dvar = nullptr;  // n x q (leading dimension n), n
+  double *scal = nullptr;          // kDesignScal doubles
+  double *mst = nullptr;           // kMacqState doubles
+  double *part_score = nullptr;    // per workgroup of 256 rows
+  int64_t *part_idx = nullptr;
+};
+uint64_t macq_update_lds_bytes(int crit, uint64_t front_cap);
+// downdate of every candidate by the previous pick (q means, one variance), its score, one (best score, lowest
+// index) pair per workgroup; d_score0, d_pof0 (may be null): every row's score and feasibility factor as formed
+int launch_macq_update(const MacqStep &s, double *d_score0, double *d_pof0);
+// the partial pairs -> the step's pick as launch_acq_pick, the q deltas, the incumbent or the front into mst
+int launch_macq_pick(const MacqStep &s, uint64_t d, uint64_t step, int64_t *d_index, double *d_score, double *d_xj);
 // acquire_dx.cpp / kernels_acquire_dx.hip: input gradients of the latent variance and of the acquisition criteria
 // (include/obhip.h, "acquisition gradients")
 constexpr int kAdxNone = -1;  // no criterion: the variance and its gradient only

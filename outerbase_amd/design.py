@@ -26,7 +26,10 @@ improvement, a confidence bound or the straddle contour criterion of the latent 
 every pick the run there is given a value without being made (the kriging believer or a constant liar) and
 every candidate's mean and variance are downdated on the device (csrc/kernels_acquire.hip).  var_grad and
 acquire_grad give the latent variance, the same four criteria and their gradients by the inputs at any rows
-(csrc/kernels_acquire_dx.hip): what a gradient ascent from the best candidates needs.
+(csrc/kernels_acquire_dx.hip): what a gradient ascent from the best candidates needs.  acquire_multi picks over the
+q responses of one fit, which share the latent variance: an objective among the inputs that keep the other responses
+within their limits (constrained expected improvement, probability of improvement, probability of feasibility), or the
+trade-off curve of two responses (expected hypervolume improvement); csrc/kernels_acquire_multi.hip.
 
 torch holds the device memory; all arithmetic is in libobhip.
 """
@@ -40,6 +43,7 @@ from ._lib import call, lib
 CRITERIA = {"maxvar": 0, "imse": 1}
 ACQUISITIONS = {"ei": 0, "pi": 1, "lcb": 2, "straddle": 3}
 LIES = {"believer": 0, "constant": 1}
+MULTI_ACQUISITIONS = {"cei": 0, "cpi": 1, "pof": 2, "ehvi": 3}
 
 
 def _stream():
@@ -86,6 +90,19 @@ class AcquireResult:
     picked; score0 (m): every candidate's criterion at the first step, eligible or not; mean, var (m): the latent
     mean and variance (without the noise) of every candidate after all fantasies; criterion.  Fewer than k
     picks: no eligible candidate was left."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+class AcquireMultiResult:
+    """index (n_picked): the picked candidates in order; score (n_picked): each one's criterion when it was picked;
+    score0, pof0 (m): every candidate's criterion and feasibility factor at the first step, eligible or not; mean
+    (m x q): the latent means of every candidate after all fantasies; var (m): their shared latent variance in
+    standardised units (without the noise) and scale (q): response j's raw variance is scale[j]**2 * var; front
+    (F x 2, ehvi): the front after all fantasies, ascending in the signed first objective; best (cei, cpi): the final
+    incumbent, infinite while no pick was believed feasible; criterion.  Fewer than k picks: no eligible candidate
+    was left."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -296,6 +313,162 @@ class Posterior:
         mean, var, (score, score0) = self._acquire_raw(sc, criterion, maximize, mean, var, score[:n].copy(), score0)
         return AcquireResult(index=index.cpu().numpy()[:n].copy(), score=score, score0=score0, mean=mean, var=var,
                              criterion=criterion, n_picked=n, k=k)
+
+    # -- acquisition over several responses --------------------------------------------------
+    def _acquire_multi_args(self, q, objective, maximize, constraints, criterion, best, ref, front, xi, lie, lie_value):
+        """acquire_multi's arguments, checked and standardised: (criterion, objs, roles, signs, limits, xi, front
+        (F0 x 2), lie_value (q), scales (q x 2: centre, scale))"""
+        if lie not in LIES:
+            raise ValueError("lie must be one of %s" % sorted(LIES))
+        if not 1 <= q <= 16:
+            raise ValueError("acquire_multi takes 1 to 16 responses")
+        if objective is None:
+            objs = []
+        elif np.ndim(objective) == 0:
+            objs = [int(objective)]
+        else:
+            objs = [int(j) for j in objective]
+        if criterion is None:
+            criterion = {0: "pof", 1: "cei", 2: "ehvi"}.get(len(objs))
+        if criterion not in MULTI_ACQUISITIONS:
+            raise ValueError("criterion must be one of %s" % sorted(MULTI_ACQUISITIONS))
+        need = {"cei": 1, "cpi": 1, "pof": 0, "ehvi": 2}[criterion]
+        if len(objs) != need:
+            raise ValueError("criterion %r takes %d objectives, %d given" % (criterion, need, len(objs)))
+        if len(objs) == 2 and not objs[0] < objs[1]:
+            raise ValueError("the two objectives are given in ascending response order")
+        mx = [bool(v) for v in (maximize if np.ndim(maximize) else [maximize] * len(objs))]
+        if len(mx) != len(objs):
+            raise ValueError("maximize: one flag, or one per objective")
+        if self.meansd is None:
+            scales = np.tile([0.0, 1.0], (q, 1))
+        else:
+            if np.shape(self.meansd)[0] != q:
+                raise ValueError("the posterior carries meansd of %d responses, Theta has %d" % (np.shape(self.meansd)[0], q))
+            scales = np.array([self._scale(j) for j in range(q)])
+        roles, signs, limits = np.full(q, 2, dtype=np.int32), np.ones(q), np.zeros(q)
+        std = lambda j, v: (float(v) - scales[j, 0]) / scales[j, 1]
+        for j, g in zip(objs, mx):
+            if not 0 <= j < q:
+                raise ValueError("objective %d is not one of the %d responses" % (j, q))
+            roles[j], signs[j] = 0, -1.0 if g else 1.0
+        for con in constraints:
+            j, op, lim = con
+            j = int(j)
+            if not 0 <= j < q or roles[j] != 2:
+                raise ValueError("constraint on response %r: not a response, or named twice" % (j,))
+            if op not in ("<=", ">="):
+                raise ValueError("a constraint is (j, '<=' | '>=', limit)")
+            if not np.isfinite(lim):
+                raise ValueError("a constraint's limit must be finite")
+            roles[j], signs[j], limits[j] = 1, 1.0 if op == "<=" else -1.0, std(j, lim)
+        if criterion == "pof" and not np.any(roles == 1):
+            raise ValueError("criterion 'pof' needs at least one constraint")
+        xi = float(xi)
+        if not np.isfinite(xi):
+            raise ValueError("xi must be finite")
+        fr = np.zeros((0, 2))
+        if criterion in ("cei", "cpi"):
+            j = objs[0]
+            if best is None:                                     # no feasible run yet: +inf in the signed sense
+                limits[j] = signs[j] * np.inf
+            else:
+                if not np.isfinite(best):
+                    raise ValueError("best must be finite, or None: no feasible run yet")
+                limits[j] = std(j, best)
+            xi = xi / scales[j, 1]
+        elif best is not None:
+            raise ValueError("best belongs to criteria 'cei' and 'cpi'")
+        if criterion == "ehvi":
+            if ref is None or np.shape(ref) != (2,) or not np.all(np.isfinite(ref)):
+                raise ValueError("criterion 'ehvi' needs ref, the finite reference point of the two objectives")
+            for a, j in enumerate(objs):
+                limits[j] = std(j, ref[a])
+            if front is not None:
+                fr = np.array(front, dtype=np.float64).reshape(-1, 2) if np.size(front) else fr
+                if not np.all(np.isfinite(fr)):
+                    raise ValueError("the front's points must be finite")
+                fr = np.column_stack([(fr[:, a] - scales[j, 0]) / scales[j, 1] for a, j in enumerate(objs)])
+        elif ref is not None or front is not None:
+            raise ValueError("ref and front belong to criterion 'ehvi'")
+        lv = np.zeros(q)
+        if lie == "constant":
+            if lie_value is None or np.shape(lie_value) != (q,) or not np.all(np.isfinite(lie_value)):
+                raise ValueError("lie='constant' needs lie_value, one finite value per response")
+            lv = np.array([std(j, lie_value[j]) for j in range(q)])
+        return criterion, objs, roles, signs, limits, xi, np.ascontiguousarray(fr), lv, scales
+
+    def acquire_multi(self, xcand, Theta, k=1, objective=None, maximize=False, constraints=(), criterion=None, best=None,
+                      ref=None, front=None, xi=0.0, lie="believer", lie_value=None, skip=None):
+        """Pick k of the candidate rows xcand (m x d) one after the other by a criterion over the q responses with
+        the standardised coefficients Theta (p x q, MultiFit.coeff) of one fit: they share the latent variance and,
+        given the data, are independent, so feasibility probabilities multiply.  objective: a response index, a pair
+        of indices (ascending) or None; maximize: one flag, or one per objective; constraints: triples
+        (j, "<=" | ">=", limit).  criterion (None: inferred from objective):
+          "cei"   one objective: expected improvement on best times the probability that every constraint holds;
+                  best=None: no feasible run yet, the score is that probability alone until a pick is believed feasible;
+          "cpi"   the same with the probability of improvement;
+          "pof"   no objective: the probability that every constraint holds;
+          "ehvi"  two objectives: the expected improvement of the hypervolume dominated by front (F0 x 2 points of the
+                  two objectives, any order, dominated points allowed) inside the box of the reference point ref,
+                  times that probability.
+        After a pick every response gets a value without the run being made -- lie="believer": its mean;
+        lie="constant": lie_value (q) -- and all means and the variance are conditioned on it; only a pick whose values
+        meet every constraint moves the incumbent or enters the front.  skip, ties and eligibility as acquire.  On a
+        posterior that carries meansd limits, best, ref, front, xi and lie_value are given in raw units of their
+        response and standardised on the way in; mean, front and best come back raw (var is shared by the responses
+        and stays standardised: response j's raw variance is scale[j]**2 * var), cei scores are multiplied by the objective's scale and ehvi scores by the product of the
+        two (cpi and pof have no unit).  All scales are positive, so the picks do not move.  -> AcquireMultiResult"""
+        import torch
+        self._need()
+        xcand = _rows(self.om, xcand, "xcand")
+        m, k = xcand.shape[0], int(k)
+        if m == 0 or k < 1:
+            raise ValueError("acquire_multi needs candidates and k >= 1")
+        Theta = np.asarray(Theta, dtype=np.float64)
+        if Theta.ndim == 1:
+            Theta = Theta[:, None]
+        if Theta.ndim != 2 or Theta.shape[0] != self.p:
+            raise ValueError("Theta must be p x q: the standardised coefficients of q responses")
+        q = Theta.shape[1]
+        criterion, objs, roles, signs, limits, xi, fr, lv, scales = self._acquire_multi_args(
+            q, objective, maximize, constraints, criterion, best, ref, front, xi, lie, lie_value)
+        F0 = len(fr)
+        if criterion == "ehvi" and F0 + k > 2048:
+            raise ValueError("front and k together must not exceed 2048 points")
+        if skip is not None:
+            skip = np.ascontiguousarray(np.asarray(skip) != 0, dtype=np.uint8)
+            if skip.shape != (m,):
+                raise ValueError("skip must have one entry per candidate")
+        dev = _stream()
+        f64, nan = torch.float64, float("nan")
+        dx = _dev_cols(xcand, dev)
+        dth = torch.from_numpy(np.ascontiguousarray(Theta.T)).to(dev)           # column-major p x q
+        dk = torch.from_numpy(skip).to(dev) if skip is not None else None
+        index = torch.full((k,), -1, dtype=torch.int64, device=dev)
+        score = torch.full((k,), nan, dtype=f64, device=dev)
+        score0, pof0, var = (torch.full((m,), nan, dtype=f64, device=dev) for _ in range(3))
+        mean = torch.full((q, m), nan, dtype=f64, device=dev)
+        fout = np.full((F0 + k, 2), np.nan)
+        nf, npk, bout = C.c_uint64(0), C.c_uint64(0), C.c_double(nan)
+        call("obhip_acquire_multi_dev", self._h, dth.data_ptr(), q, dx.data_ptr(), m, MULTI_ACQUISITIONS[criterion],
+             roles.ctypes.data, signs.ctypes.data, limits.ctypes.data, xi, fr.ctypes.data if F0 else None, F0, LIES[lie],
+             lv.ctypes.data, None if dk is None else dk.data_ptr(), k, index.data_ptr(), score.data_ptr(),
+             score0.data_ptr(), pof0.data_ptr(), mean.data_ptr(), var.data_ptr(), fout.ctypes.data, C.byref(nf),
+             C.byref(bout), C.byref(npk))
+        torch.cuda.synchronize()
+        n = npk.value
+        score, score0, pof0, var = (a.cpu().numpy() for a in (score, score0, pof0, var))
+        mean = mean.cpu().numpy().T * scales[:, 1] + scales[:, 0]                  # m x q, raw
+        unit = {"cei": scales[objs[0], 1] if objs else 1.0, "ehvi": np.prod(scales[objs, 1]) if objs else 1.0}.get(criterion, 1.0)
+        fo, bo = None, None
+        if criterion == "ehvi":
+            fo = fout[:nf.value] * scales[objs, 1] + scales[objs, 0]
+        if criterion in ("cei", "cpi"):
+            bo = bout.value * scales[objs[0], 1] + scales[objs[0], 0]
+        return AcquireMultiResult(index=index.cpu().numpy()[:n].copy(), score=unit * score[:n], score0=unit * score0,
+                                  pof0=pof0, mean=mean, var=var, scale=scales[:, 1].copy(), front=fo, best=bo,
+                                  criterion=criterion, n_picked=n, k=k)
 
     # -- acquisition gradients ---------------------------------------------------------------
     @staticmethod
